@@ -7,9 +7,14 @@ Workload (BASELINE.json configs[1]): batch 16 per GPU, 4 s cli
 samples, text 60), bf16 compute, random-init weights of configs/s2.json, synthetic data.  Weak scaling: the per-GPU
 batch is fixed, gradients are all-reduced over RCCL.
 metric: audio-seconds/sec trained (s2) = N * B * clip_seconds / step_time (`value`); the s1 half of the combined
-BASELINE metric (tokens/sec of the AR GPT micro-step at batch 32 x 1024, configs[2]) is measured in the same run and
+BASELINE metric (tokens/sec of the AR GPT micro-step at batch 32 x 1024, configs[2]) is measured in the same run (--full) and
 reported as the `s1` sub-object with its own roofline (attention kernel vs the MFMA peak) and CPU baseline.
 Started bare with --gpus N > 1 (no WORLD_SIZE) it launches its own N ranks.
+A plain run times the s2 step only.  --full adds what the headline does not need: the s1 leg, the per-kernel roofline
+legs and the CPU baselines (and the combined metric string).  --dump-outputs DIR writes what the last timed step computed
+(losses, activations it returns, a fixed sample of the updated parameters) as DIR/<name>.npy, for output-for-output
+comparison of two builds.  With it, the last timed step starts from the seeded start state (TrainState), outside the
+clock, so that what it computes depends on the arguments alone.
 """
 import argparse
 import json
@@ -61,6 +66,75 @@ def synth_s2_batch(B, T, t_text, device, seed):
     return wav, ssl, text, lengths, tl
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of a larger output: a fixed, seeded sample
+DUMP_LIMIT = 64 << 20          # bytes written in all by one run
+_dumped = {}                   # path -> bytes written by this run
+
+
+def dump_outputs(out_dir, arrays, prefix=""):
+    """arrays: {name: tensor}.  Each goes to out_dir/<prefix><name>.npy as float32 (float64 if it is float64); one with
+    more than DUMP_SAMPLE elements is flattened and sampled at indices drawn from a fixed seed, so two runs (or two
+    builds) write the same positions."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx]
+        a = t.numpy()
+        path = os.path.join(out_dir, f"{prefix}{name}.npy")
+        _dumped[path] = a.nbytes
+        if sum(_dumped.values()) > DUMP_LIMIT:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {prefix}{name}")
+        np.save(path, a)
+
+
+class TrainState:
+    """Everything an s2 training step reads besides its batch and writes for the next step: both parameter arenas, the
+    AdamW moments and step counters, the dropout counter and the loss scaler.  The step sums some gradients with fp32
+    atomics, so two runs agree to rounding after one step but not after many: GAN training with AdamW grows last-bit
+    differences into visible ones within a few steps.  --dump-outputs therefore runs its last timed step from this
+    snapshot of the seeded start, which makes what it dumps a function of the arguments alone."""
+
+    def __init__(self, eng):
+        from easevoice_trainer_amd.hip.enc import rng_counter
+
+        self.eng = eng
+        self.tensors = [eng.rt_g.arena.param, eng.rt_d.arena.param, rng_counter(eng.device), eng.scaler._scale,
+                        eng.scaler._tracker]
+        for opt in (eng.optim_g, eng.optim_d):
+            self.tensors += [opt.exp_avg, opt.exp_avg_sq, opt._step_dev]
+        self.saved = [t.clone() for t in self.tensors]
+        self.counts = [opt.step_count for opt in (eng.optim_g, eng.optim_d)]
+
+    def restore(self):
+        for t, v in zip(self.tensors, self.saved):
+            t.copy_(v)
+        for opt, n in zip((self.eng.optim_g, self.eng.optim_d), self.counts):
+            opt.step_count = n
+            opt.arena.updates += 1          # parameters were written from outside: the next prepare() refolds them
+        self.eng.rt_g.prepare(force=True)
+        self.eng.rt_d.prepare(force=True)
+
+
+def s2_outputs(eng, out):
+    """what a caller of S2Engine.step receives from one step, plus the parameters that step updated"""
+    arrays = {k: getattr(out, k) for k in ("disc", "gen", "fm", "mel", "kl", "kl_ssl", "gen_all", "grad_sumsq_d",
+                                          "grad_sumsq_g") if getattr(out, k) is not None}
+    for k, v in out.extras.items():
+        if isinstance(v, (list, tuple)):
+            arrays.update({f"{k}_{i}": x for i, x in enumerate(v)})
+        elif v is not None:
+            arrays[k] = v
+    arrays["params_g"] = eng.rt_g.arena.param
+    arrays["params_d"] = eng.rt_d.arena.param
+    return arrays
+
+
 def _lanes_note(eng):
     """which independent sub-models of the step run on branch streams (hip/disc.py switches)"""
     from easevoice_trainer_amd.hip import disc as HD
@@ -109,6 +183,7 @@ def run_s2(args, world, rank, local):
     def step():
         return eng.step(ssl, spec, lengths, wav, text, tl)
 
+    start = TrainState(eng) if args.dump_outputs else None
     for _ in range(max(args.warmup, 4 if use_graphs else 0)):   # graph mode: 2 eager + capture + 1 replay first
         out = step()
     if world > 1:
@@ -118,12 +193,21 @@ def run_s2(args, world, rank, local):
         reducer.timing = dev.type == "cuda"        # HIP events around every wait for the side stream: the exposed part
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            # the dumped step starts from the seeded start state, outside the clock (see TrainState)
+            torch.cuda.synchronize()
+            dt_before = time.perf_counter() - t0
+            start.restore()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter() - dt_before
         out = step()
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, s2_outputs(eng, out))
     comm = None
     if reducer is not None:
         comm = reducer.comm_report(args.steps)      # this rank's view; the line is rank 0's
@@ -163,20 +247,29 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", default="both", choices=["both", "s2", "s1"],
-                    help="both (default): the s2 line with the s1 leg as its `s1` sub-object")
+    ap.add_argument("--workload", default=None, choices=["both", "s2", "s1"],
+                    help="both: the s2 line with the s1 leg as its `s1` sub-object (default with --full; s2 without)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"],
                     help="f16: the reference's fp16_run mode (IEEE-half build of the library + device-side GradScaler), s2 leg")
     ap.add_argument("--batch", type=int, default=16, help="s2 batch per GPU (BASELINE config 2: 16)")
     ap.add_argument("--s1-batch", type=int, default=32, help="s1 batch per GPU (BASELINE config 3: 32)")
     ap.add_argument("--clip-seconds", type=int, default=4)
     ap.add_argument("--graphs", type=int, default=1, help="1: replay the s2 step as HIP graphs (default), 0: eager launches")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline / cpu_baseline legs (use under rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the s1 leg, the roofline and cpu_baseline legs (off: the s2 step only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the roofline / cpu_baseline legs (use under rocprofv3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses, activations, sampled updated parameters) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--dp-program", type=int, default=0, choices=[0, 1, 2],
                     help="one GPU only. 1: run the data-parallel (cut, nine-graph) program without collectives -- the cost of "
                          "the decomposition itself next to the default three-phase program; 2: the same with the collectives "
                          "issued on a one-rank RCCL group (side stream, between the graph replays)")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "both" if args.full else "s2"
+    extras = args.full and not args.no_extras
     if args.dp_program and args.gpus == 1:
         os.environ["EVT_DP_CUT" if args.dp_program == 1 else "EVT_DP_FORCE"] = "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -197,7 +290,7 @@ def main():
             # several ranks a leg that fails on ONE rank would leave the others waiting in a collective -- they are
             # reported by the N = 1 run only
             res["roofline_note"] = "kernel roofline and cpu_baseline are reported by the N = 1 run"
-        elif not args.no_extras:
+        elif extras:
             try:
                 from tools import bench_extras
 
@@ -210,7 +303,10 @@ def main():
         from tools import bench_s1
 
         try:
-            s1 = bench_s1.run(args, world, rank, local, extras=not args.no_extras and world == 1)
+            dump = None
+            if args.dump_outputs and rank == 0:
+                dump = lambda arrays: dump_outputs(args.dump_outputs, arrays, prefix="s1_")
+            s1 = bench_s1.run(args, world, rank, local, extras=extras and world == 1, dump=dump)
         except Exception as e:
             if res is None:
                 raise

@@ -4,7 +4,8 @@ read-only through oracle/refshim.py):
   s2_c1_adamw.pt  the C1 run of make_golden.py continued by ONE optimiser step of both networks with the reference's
                   torch.optim.AdamW set-up (src/train/sovits.py:285-319: four generator groups, three at
                   text_low_lr_rate; betas/eps of configs/s2.json) -- gradients and post-step values of selected
-                  parameters, and fp64 checksums of every top-level module's post-step weights
+                  parameters, and fp64 checksums of every top-level module's post-step weights (the generator's
+                  gradients and post-step values in s2_c1_adamw_grads_g.pt / s2_c1_adamw_after_g.pt)
   s2_c2.pt        BASELINE config 2 shapes (B = 16, 4 s clips, text 60), fp32: the seven loss terms, a strided sample of
                   y_hat, y_hat_mel, gradient sums per module and gradient slices
   s1_c3.pt        BASELINE config 3 sequence shape (256 phonemes + 768 semantic tokens) at B = 2 (the CPU reference needs
@@ -95,6 +96,8 @@ def make_adamw():
 
     MG.make_s2(tag="_noise", hook=hook, hook_d=hook_d)
     path = os.path.join(HERE, "s2_c1_adamw.pt")
+    for k in ("grads_g", "after_g"):      # files of their own: each fixture file stays under 1 MiB
+        torch.save(res.pop(k), os.path.join(HERE, f"s2_c1_adamw_{k}.pt"))
     torch.save(res, path)
     print("wrote", path, "ssl_proj unchanged:", res["ssl_proj_unchanged"], "|g|^2", res["grad_sumsq_g"], res["grad_sumsq_d"])
 

@@ -129,10 +129,18 @@ def test_whole_step_c2_vs_reference(gpu, dtype):
     assert rel(out.extras["d_logits"][0][:, :16], gold["d_logits_head"][0]) < (1e-3 if f32 else 8e-2)
 
 
+def _adamw_gold():
+    """s2_c1_adamw.pt with the two generator dicts kept in files of their own (each fixture file stays under 1 MiB)"""
+    gold = torch.load(os.path.join(HERE, "golden", "s2_c1_adamw.pt"), weights_only=False)
+    for k in ("grads_g", "after_g"):
+        gold[k] = torch.load(os.path.join(HERE, "golden", f"s2_c1_adamw_{k}.pt"), weights_only=False)
+    return gold
+
+
 def test_adamw_kernel_vs_torch_adamw(gpu):
     """evt_adamw_flat_dev on the reference's OWN gradients == torch.optim.AdamW's post-step weights (1e-6 relative),
     for parameters of all four generator groups and of D; evt_sumsq == sum of the squared gradients fed in"""
-    gold = torch.load(os.path.join(HERE, "golden", "s2_c1_adamw.pt"), weights_only=False)
+    gold = _adamw_gold()
     eng = _engine(gpu, torch.float32)
     opt_g, opt_d = eng.build_optimizers()
     hy = gold["hyper"]
@@ -165,7 +173,7 @@ def test_whole_step_then_adamw_vs_reference(gpu):
     the first AdamW step moves every element by lr * g / (|g| + eps), so the two agree wherever the gradient's sign does;
     checked per selected tensor (>= 99.5 % of the elements within 2e-6 of max|w|) and through fp64 checksums of every
     top-level module (the sum of squares moves by < 1e-6 relative)"""
-    gold = torch.load(os.path.join(HERE, "golden", "s2_c1_adamw.pt"), weights_only=False)
+    gold = _adamw_gold()
     c1 = torch.load(os.path.join(HERE, "golden", "s2_c1.pt"), weights_only=False)
     eng = _engine(gpu, torch.float32)
     opt_g, opt_d = eng.build_optimizers()

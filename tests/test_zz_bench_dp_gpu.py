@@ -19,7 +19,7 @@ def test_bench_two_ranks_one_device(gpu):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
-           "--clip-seconds", "2", "--s1-batch", "2"]          # no --no-extras: with N > 1 the extra legs switch themselves off
+           "--clip-seconds", "2", "--s1-batch", "2", "--full"]  # no --no-extras: with N > 1 the extra legs switch themselves off
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

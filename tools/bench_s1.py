@@ -116,7 +116,8 @@ def attention_roofline(eng, batch, B, Lq, dtype_name, n_micro=2, x_len=256):
     return out
 
 
-def run(args, world, rank, local, extras=True):
+def run(args, world, rank, local, extras=True, dump=None):
+    """dump: called with {name: tensor} of the last timed micro-step (its loss and accuracy, the updated parameters)"""
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
     on_gpu = torch.cuda.is_available()
@@ -157,6 +158,8 @@ def run(args, world, rank, local, extras=True):
         torch.distributed.barrier()
     sync()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump(dict(loss=loss, top3_acc=acc, params=eng.arena.param))
     comm = reducer.comm_report(args.steps) if reducer is not None else None
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
