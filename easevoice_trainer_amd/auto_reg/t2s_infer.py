@@ -8,6 +8,9 @@ Same token sequence as the reference for the same sampling noise; a different ex
   * token steps: five launches per block (csrc/s1_decode.hip: in-projection, cache attention, out-projection, two for
     the MLP) + logits + one for sampling / embedding / counters, all reading their per-step state (cache length, step
     index, token count) from device memory, captured once into a HIP graph and replayed per token.  The host reads the stop flag every `poll` steps; tokens decoded past the stop are discarded.
+  * batches: a session of up to four rows runs the kernels above; 5..32 rows share ONE wide session (one prompt pass,
+    one step loop) whose linear layers read every weight once per step for all rows (csrc/s1_decode_rows.hip) and whose
+    sampler keys each row's noise by a row-seed table, so a row draws what it drew in a group of four.
 The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
 import ctypes as C
 import os
@@ -66,14 +69,16 @@ class DecodeSession:
         self.stop = torch.full((B,), -1, dtype=torch.int32, device=device)
         self.x_lens, self.x_len = None, 0      # key-padding of a batch of texts (infer_panel_batch_infer); None = no padding
         self.x_lens_buf = z(B, dt=torch.int32)
+        self.wide = B > T2SInfer.MAX_ROWS       # 5..32 rows: evt_dec_gemm_rows / evt_dec_sample_rows
+        self.row_seed = z(B, 2, dt=torch.int32)  # (seed, lane) per row of a wide session, written by T2SInfer._decode
         self.graph, self.graph_key = None, None
 
     # ---- launches ----
     def _gemv(self, w, bias, a, r, g, b, eps, x_out, y, relu=0):
         N, K = w.shape
-        L.check(L.lib().evt_dec_gemv(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
-                                     C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu), L.stream_ptr()),
-                "evt_dec_gemv")
+        fn = "evt_dec_gemm_rows" if self.wide else "evt_dec_gemv"
+        L.check(getattr(L.lib(), fn)(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
+                                     C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu), L.stream_ptr()), fn)
 
     def _sample_embed_advance(self, W, sp, noise, pe, dpos):
         """sampling, append, embedding of the new token and the counter update: one launch for one sequence, three for a
@@ -86,8 +91,13 @@ class DecodeSession:
                 L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha), xs, L.ptr(self.xa), self.E, pe.size(0), dpos, L.stream_ptr()),
                 "evt_dec_sample_embed")
             return
-        L.check(lib.evt_dec_sample(C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.ctr), L.ptr(noise),
-                                   L.ptr(self.stop), None, self.B, L.stream_ptr()), "evt_dec_sample")
+        if self.wide:
+            L.check(lib.evt_dec_sample_rows(C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.ctr), L.ptr(noise),
+                                            L.ptr(self.stop), None, L.ptr(self.row_seed), self.B, L.stream_ptr()),
+                    "evt_dec_sample_rows")
+        else:
+            L.check(lib.evt_dec_sample(C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.ctr), L.ptr(noise),
+                                       L.ptr(self.stop), None, self.B, L.stream_ptr()), "evt_dec_sample")
         L.check(lib.evt_dec_embed(L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha), xs, L.ptr(self.y), L.ptr(self.ctr), L.ptr(self.xa),
                                   self.B, self.E, self.ymax, pe.size(0), L.stream_ptr()), "evt_dec_embed")
         L.check(lib.evt_dec_advance(L.ptr(self.ctr), dpos, L.stream_ptr()), "evt_dec_advance")
@@ -102,7 +112,9 @@ class DecodeSession:
         """one token: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + one launch for sampling /
         embedding / counters = 122 launches.  fused_qkv puts the in-projection into the attention launch (98 launches):
         16 workgroups then stream all of W_qkv, which is slower on the device (measured 696 vs 614 us per token under
-        graph replay) but faster when the HOST is the bottleneck (eager launches: 959 vs 1210 us)."""
+        graph replay) but faster when the HOST is the bottleneck (eager launches: 959 vs 1210 us).  A wide session never
+        fuses: every (row, head) workgroup would stream its head's rows of W_qkv again."""
+        fused_qkv = fused_qkv and not self.wide
         prev = None
         for i, w in enumerate(W.layers):
             ln = (None, None, None, 0.0, None) if prev is None else (self.u, prev["g2"], prev["be2"], prev["eps2"], self.xa)
@@ -128,11 +140,13 @@ class T2SInfer:
     def __init__(self, model):
         self.model = model
         self._w, self._sessions, self._dense = None, {}, None
+        self._wide = []            # keys of the wide sessions held, least recently used first
 
     def weights(self, dtype):
         if self._w is None or self._w[0] != dtype or self._w[1].stamp != _Weights.stamp_of(self.model):
             self._w = (dtype, _Weights(self.model, dtype))
             self._sessions.clear()          # captured graphs hold pointers into the old copies
+            self._wide.clear()
         return self._w[1]
 
     def dense(self, dtype, device):
@@ -166,13 +180,24 @@ class T2SInfer:
         return run
 
     def session(self, B, Lneed, yneed, dtype, device):
+        """sessions of <= MAX_ROWS rows are kept per shape; of the wide ones (up to 3.2 GB of bf16 cache at B = 32,
+        Lmax = 2048) only the WIDE_SESSIONS most recently used, a dropped one taking its captured graph with it"""
         Lmax, ymax = -(-Lneed // 512) * 512, -(-yneed // 512) * 512
         key = (B, Lmax, ymax, dtype, str(device))
+        if B > self.MAX_ROWS:
+            if key in self._wide:
+                self._wide.remove(key)
+            else:
+                while len(self._wide) >= self.WIDE_SESSIONS:
+                    del self._sessions[self._wide.pop(0)]
+            self._wide.append(key)
         if key not in self._sessions:
             self._sessions[key] = DecodeSession(self.model, B, Lmax, ymax, dtype, device)
         return self._sessions[key]
 
-    MAX_ROWS = 4      # rows per session (kMaxB of csrc/s1_decode.hip); larger batches run in groups
+    MAX_ROWS = 4        # rows of a session on the kernels of csrc/s1_decode.hip (kMaxB); also the seed group of a row
+    WIDE_ROWS = 32      # rows of a wide session (csrc/s1_decode_rows.hip); larger batches run in groups of 32
+    WIDE_SESSIONS = 2   # wide sessions kept at once
 
     @torch.no_grad()
     def _decode(self, xs, berts, prompts, no_eos_steps, top_k, top_p, early_stop_num, temperature, repetition_penalty,
@@ -229,9 +254,14 @@ class T2SInfer:
         if prompts is not None:
             S.y[:, :y_len].copy_(prompts)
         # the sampling seed is device state like the counters (a new one per call must not force a re-capture); without
-        # an explicit seed it is drawn from torch's CPU generator, so torch.manual_seed makes a run repeatable
-        seed = int(seed if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()) & 0x7FFFFFFF
-        S.ctr.copy_(torch.tensor([src_len, 0, y_len, y_len, seed, 0, 0, 0], dtype=torch.int32))
+        # an explicit seed it is drawn from torch's CPU generator, so torch.manual_seed makes a run repeatable.  A wide
+        # session gives row b what row b % 4 of a group of four drew: group g seeded seed + 4g, or the g-th draw
+        G = self.MAX_ROWS
+        draws = [int(seed + G * g if seed is not None else torch.randint(0, 2 ** 31 - 1, (1,)).item()) & 0x7FFFFFFF
+                 for g in range(-(-B // G) if S.wide else 1)]
+        if S.wide:
+            S.row_seed.copy_(torch.tensor([[draws[b // G], b % G] for b in range(B)], dtype=torch.int32))
+        S.ctr.copy_(torch.tensor([src_len, 0, y_len, y_len, draws[0], 0, 0, 0], dtype=torch.int32))
         S.stop.fill_(-1)
         padded = min(x_lens) < x_len
         if padded:
@@ -302,16 +332,19 @@ class T2SInfer:
         """t2s_model.py:563-730, the TTS default (parallel_infer=True): texts of different lengths decoded together.
         x: list of id vectors, bert_feature: list of [1024, n].  Rows are independent (padded text positions are masked
         as keys, a finished row only leaves the batch), so instead of compacting the batch whenever a row meets EOS, all
-        rows of a group keep stepping through the same graph and each row's tokens are cut at its own stop.  Kept
+        rows of a group keep stepping through the same graph and each row's tokens are cut at its own stop.  Up to
+        WIDE_ROWS texts are one group (one prompt pass, one session), more run in groups of WIDE_ROWS.  Kept
         differences to infer_panel_naive: the EOS column is dropped at step 0 only, the returned index is idx - 1 for an
-        EOS stop and idx for the early stop."""
+        EOS stop and idx for the early stop.  `seed` (or torch's CPU generator) gives row r the noise of row r % 4 of a
+        group seeded seed + 4 * (r // 4), as when every four rows were decoded on their own."""
         if prompts is None:
             return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
                                                   early_stop_num=early_stop_num, temperature=temperature, noise=noise,
                                                   seed=seed, poll=poll)
         ys, idxs = [], []
-        for g0 in range(0, len(x), self.MAX_ROWS):
-            rows = list(range(g0, min(len(x), g0 + self.MAX_ROWS)))
+        step = self.WIDE_ROWS if len(x) > self.MAX_ROWS else self.MAX_ROWS
+        for g0 in range(0, len(x), step):
+            rows = list(range(g0, min(len(x), g0 + step)))
             nz = noise if noise is None or noise.dim() == 2 else noise[:, rows]
             ybuf, last, eos, y_len = self._decode([x[r] for r in rows], [bert_feature[r] for r in rows], prompts[rows], 1,
                                                   top_k, top_p, early_stop_num, temperature, repetition_penalty, noise=nz,

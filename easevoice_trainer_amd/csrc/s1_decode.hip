@@ -430,7 +430,7 @@ struct EmbedArgs {          // optional tail of dec_sample: x_next and the count
 
 __global__ __launch_bounds__(1024) void dec_sample(evt_sample_params p, const float* __restrict__ logits, long* y,
                                                    int* ctr, const float* __restrict__ noise, int* stop_idx,
-                                                   float* probs_out, EmbedArgs ea) {
+                                                   float* probs_out, EmbedArgs ea, const int* __restrict__ row_seed) {
   __shared__ float sv[kSortN];
   __shared__ int si[kSortN];
   __shared__ float cur[kSortN];
@@ -440,6 +440,9 @@ __global__ __launch_bounds__(1024) void dec_sample(evt_sample_params p, const fl
   __shared__ float wsum[16];
   const int tid = threadIdx.x, b = blockIdx.x, V = p.V;
   const int idx = ctr[EVT_DEC_IDX], ycount = ctr[EVT_DEC_YCOUNT];
+  // built-in noise of this row: (seed, lane) from the row-seed table, else (ctr[SEED], b)
+  const unsigned nseed = row_seed ? (unsigned)row_seed[2 * b] : (unsigned)ctr[EVT_DEC_SEED];
+  const unsigned nlane = row_seed ? (unsigned)row_seed[2 * b + 1] : (unsigned)b;
   const int Ve = idx < p.no_eos_steps ? V - 1 : V;     // "at least 10 tokens otherwise not stop", t2s_model.py:833
   const float* lg = logits + (long)b * V;
   long* yb = y + (long)b * p.ymax;
@@ -540,7 +543,7 @@ __global__ __launch_bounds__(1024) void dec_sample(evt_sample_params p, const fl
         q = noise[((long)idx * p.noise_rows + (p.noise_rows > 1 ? b : 0)) * V + v];
       } else {
         const unsigned hsh =
-            mix32s(mix32s((p.seed ^ (unsigned)ctr[EVT_DEC_SEED]) + (unsigned)idx * 0x9E3779B9u) ^ ((unsigned)b << 16) ^ (unsigned)v);
+            mix32s(mix32s((p.seed ^ nseed) + (unsigned)idx * 0x9E3779B9u) ^ (nlane << 16) ^ (unsigned)v);
         q = -logf(((float)(hsh >> 8) + 0.5f) * (1.0f / 16777216.0f));
       }
       const float s = pr / q;
@@ -653,7 +656,20 @@ int evt_dec_sample(const evt_sample_params* p, const float* logits, int64_t* y, 
   evt_sample_params sp = *p;
   if (sp.noise_rows < 1) sp.noise_rows = 1;
   hipLaunchKernelGGL(dec_sample, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
-                     (int*)stop_idx, probs_out, none);
+                     (int*)stop_idx, probs_out, none, (const int*)nullptr);
+  return evt_check_launch();
+}
+
+int evt_dec_sample_rows(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr,
+                        const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed, int32_t B,
+                        void* stream) {
+  if (!p || !logits || !y || !ctr || !stop_idx || !row_seed || B <= 0) return EVT_EINVAL;
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
+  EmbedArgs none{};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  hipLaunchKernelGGL(dec_sample, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
+                     (int*)stop_idx, probs_out, none, (const int*)row_seed);
   return evt_check_launch();
 }
 
@@ -666,7 +682,7 @@ int evt_dec_sample_embed(const evt_sample_params* p, const float* logits, int64_
   evt_sample_params sp = *p;
   sp.noise_rows = 1;
   hipLaunchKernelGGL(dec_sample, dim3(1), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
-                     (int*)stop_idx, (float*)nullptr, ea);
+                     (int*)stop_idx, (float*)nullptr, ea, (const int*)nullptr);
   return evt_check_launch();
 }
 

@@ -675,13 +675,21 @@ int evt_ce_rows_fwd_bwd_ld(int32_t dtype, const void* logits, const int64_t* tar
 #define EVT_DEC_YCOUNT 2 /* tokens in the y buffer (prompt + generated) */
 #define EVT_DEC_YLEN 3   /* prompt length: the new token's position is YLEN + IDX (t2s_model.py:861) */
 #define EVT_DEC_SEED 4   /* per-call sampling seed, xor-ed with evt_sample_params.seed */
-/* y[b][n] = act(bias[n] + sum_k W[n][k] * x[b][k]); W [N][K] row-major in `wdtype`, vectors fp32, B <= 4, K % 512 == 0.
+/* y[b][n] = act(bias[n] + sum_k W[n][k] * x[b][k]); W [N][K] row-major in `wdtype`, vectors fp32, B <= 4 (sessions of up
+ * to four rows; evt_dec_gemm_rows below serves up to 32), K % 512 == 0.
  * r == NULL: x = a.  r != NULL: x = LayerNorm(a + r) * ln_g + ln_b (the post-LN residual of T2SBlock.decode_next_token,
  * t2s_model.py:208-221, recomputed per workgroup); x_out (may be NULL) receives it for the next residual and must not
  * alias a or r.  relu != 0 applies max(0, .) (T2SMLP.forward, t2s_model.py:74-77). */
 int evt_dec_gemv(int32_t wdtype, const void* W, const float* bias, const float* a, const float* r, const float* ln_g,
                  const float* ln_b, float ln_eps, float* x_out, float* y, int32_t B, int32_t N, int32_t K, int32_t relu,
                  void* stream);
+/* evt_dec_gemv for 1 <= B <= 32 rows (the wide decode sessions of 5..32 texts, t2s_model.py:563-730): same arguments and
+ * numerics (x fp32, 16-bit weights widened exactly, fp32 products and sums; only the order of the sum differs), but every
+ * weight byte is read from HBM once per launch for all rows (fp32-input MFMA over 16-row tiles of W).  K % 512 == 0,
+ * K <= 2048; W, a, r, ln_g, ln_b and x_out 16-byte aligned.  Deterministic: no atomics. */
+int evt_dec_gemm_rows(int32_t wdtype, const void* W, const float* bias, const float* a, const float* r,
+                      const float* ln_g, const float* ln_b, float ln_eps, float* x_out, float* y, int32_t B, int32_t N,
+                      int32_t K, int32_t relu, void* stream);
 /* qkv fp32 [B][3*H*D] of the new token: its key/value are stored at cache position ctr[POS] (kcache/vcache
  * [B][Lmax][H*D] in `cdtype`) and out[b][h*D+d] = softmax(q.K^T/sqrt(D)).V over positions 0..ctr[POS]
  * (t2s_model.py:187-204 without the torch.cat growth).  D == 32.
@@ -711,6 +719,12 @@ typedef struct evt_sample_params {
 } evt_sample_params;
 int evt_dec_sample(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr, const float* noise,
                    int32_t* stop_idx, float* probs_out, int32_t B, void* stream);
+/* evt_dec_sample with the built-in noise of row b keyed by the device table row_seed int32 [B][2] = (seed, lane) where
+ * evt_dec_sample uses (ctr[SEED], b): a wide session of up to 32 rows draws, row for row, the noise that groups of four
+ * rows seeded (seed + 4*g) draw in evt_dec_sample. */
+int evt_dec_sample_rows(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr,
+                        const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed, int32_t B,
+                        void* stream);
 /* evt_dec_sample + evt_dec_embed + evt_dec_advance(dpos) for ONE sequence in a single launch */
 int evt_dec_sample_embed(const evt_sample_params* p, const float* logits, int64_t* y, int32_t* ctr, const float* noise,
                          int32_t* stop_idx, const float* emb, const float* pe, const float* alpha, float x_scale, float* x,

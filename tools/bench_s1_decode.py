@@ -1,7 +1,10 @@
 """Decoding throughput of the s1 model: tokens/s of infer_panel_naive for one sequence, HIP-graph
 replay vs eager launches, with the algorithmic HBM bytes per token (every block matrix once + the key/value cache read).
+--rows R [R ...] (R <= 64) also times infer_panel_batch_infer on R texts of different lengths, two modes alternated in
+the same process: batch{R}_graph (one call: one session of up to 32 rows) and batch{R}_groups4_graph (the same texts in
+consecutive calls of <= 4 rows, one session each); algorithmic bytes per step = every matrix once + R caches.
 
-    python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16]
+    python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
 """
 import argparse
 import json
@@ -25,7 +28,10 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--rows", type=int, default=0, help="also time infer_panel_batch_infer with this many texts (<= 4)")
+    ap.add_argument("--rows", type=int, nargs="*", default=[],
+                    help="also time infer_panel_batch_infer with this many texts (each <= 64)")
+    ap.add_argument("--rows-only", action="store_true",
+                    help="time batch{R}_graph alone (no single-sequence lines, no groups of 4): for a kernel trace")
     args = ap.parse_args()
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
@@ -49,7 +55,7 @@ def main():
     E, nl = 512, 24
     w_bytes = (nl * (3 * E * E + E * E + 8 * E * E) + 1025 * E) * esz
     out = {}
-    for mode in ("1", "0"):
+    for mode in () if args.rows_only else ("1", "0"):
         os.environ["EVT_DECODE_GRAPH"] = mode
         times = []
         for rep in range(args.reps + 1):
@@ -63,26 +69,45 @@ def main():
         t = sorted(times[1:])[len(times[1:]) // 2]
         out["graph" if mode == "1" else "eager"] = dict(seconds=round(t, 4), tokens_per_s=round((args.tokens + 1) / t, 1),
                                                         us_per_token=round(1e6 * t / (args.tokens + 1), 1))
-    if args.rows:
-        os.environ["EVT_DECODE_GRAPH"] = "1"
-        R = args.rows
-        xs = [x[0][: args.x_len - 7 * r].contiguous() for r in range(R)]         # different text lengths: padded batch
-        berts = [bert[0][:, : args.x_len - 7 * r].contiguous() for r in range(R)]
-        times = []
-        for rep in range(args.reps + 1):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            ys, idxs = m.infer_panel_batch_infer(xs, None, prompts.expand(R, -1).contiguous(), berts, top_k=15, top_p=1,
-                                                 early_stop_num=args.tokens, noise=noise, repetition_penalty=1.35)
-            torch.cuda.synchronize()
-            times.append(time.perf_counter() - t0)
-            assert all(y.numel() == args.prompt + args.tokens for y in ys), [y.shape for y in ys]
-        t = sorted(times[1:])[len(times[1:]) // 2]
-        out[f"batch{R}_graph"] = dict(seconds=round(t, 4), tokens_per_s=round(R * (args.tokens + 1) / t, 1),
-                                      us_per_step=round(1e6 * t / (args.tokens + 1), 1))
     L_avg = args.x_len + args.prompt + args.tokens / 2
     cache_bytes = nl * 2 * L_avg * E * esz
+    for R in args.rows:
+        assert 1 <= R <= 64, R
+        os.environ["EVT_DECODE_GRAPH"] = "1"
+        # different text lengths (a padded batch), cycling past 12 rows so that every text stays non-empty
+        lens = [max(1, args.x_len - 7 * (r % 12)) for r in range(R)]
+        xs = [x[0][:n].contiguous() for n in lens]
+        berts = [bert[0][:, :n].contiguous() for n in lens]
+        pr = prompts.expand(R, -1).contiguous()
+
+        def call(rows):
+            return m.infer_panel_batch_infer([xs[r] for r in rows], None, pr[rows], [berts[r] for r in rows], top_k=15,
+                                             top_p=1, early_stop_num=args.tokens, noise=noise, repetition_penalty=1.35)
+
+        modes = {f"batch{R}_graph": [list(range(R))]}
+        if R > 4 and not args.rows_only:
+            modes[f"batch{R}_groups4_graph"] = [list(range(g, min(R, g + 4))) for g in range(0, R, 4)]
+        times = {k: [] for k in modes}
+        for rep in range(args.reps + 1):
+            for k, calls in modes.items():           # alternated: both modes see the same state of the device
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for rows in calls:
+                    ys, idxs = call(rows)
+                torch.cuda.synchronize()
+                times[k].append(time.perf_counter() - t0)
+                assert all(y.numel() == args.prompt + args.tokens for y in ys), [y.shape for y in ys]
+        bytes_step = w_bytes + R * cache_bytes
+        for k in modes:
+            t = sorted(times[k][1:])[len(times[k][1:]) // 2]
+            us = 1e6 * t / (args.tokens + 1)
+            out[k] = dict(seconds=round(t, 4), tokens_per_s=round(R * (args.tokens + 1) / t, 1), us_per_step=round(us, 1),
+                          algorithmic_bytes_per_step=int(bytes_step), GBps=round(bytes_step / (us * 1e-6) / 1e9, 1))
     per_tok = w_bytes + cache_bytes
+    if args.rows_only:
+        print(json.dumps(dict(workload=f"s1 decode, rows {args.rows}, x_len={args.x_len}, prompt={args.prompt}, "
+                                       f"{args.tokens} tokens, {args.dtype}, top_k=15 (prompt pass included)", **out)))
+        return
     gps = per_tok / (out["graph"]["us_per_token"] * 1e-6) / 1e9
     print(json.dumps(dict(workload=f"s1 decode, 1 sequence, x_len={args.x_len}, prompt={args.prompt}, {args.tokens} tokens, "
                                    f"{args.dtype}, top_k=15 (prompt pass included)",
