@@ -16,7 +16,6 @@
 // and flies under its 32 MFMAs per wave; one barrier per stage.
 #include "conv_p.h"
 #include "wgrad_epi.h"
-#include <cstdlib>
 
 namespace evt_conv {
 namespace {
@@ -841,10 +840,6 @@ __global__ __launch_bounds__(256, NS > 2 ? 1 : 2) void wgrad_gemm(WgP p, int sta
         for (int r = 0; r < 4; ++r) atomicAdd(p.dbias + a0 + wr * 64 + i * 16 + g8 * 4 + r, bacc[i][r]);
   }
 
-  if (p.parts < 0) {      // measurement variant (EVT_WGRAD_GEMM_NOEPI=1): the main loop without its atomics
-    if (acc[0][0][0] == 12345.678f) p.dw[0] = 1.f;
-    return;
-  }
   // lane holds dy-channels g8*4..+3 (rows) x x-channel j16 (column) of each tile; image [CA][nchunk][1][32]
 #pragma unroll
   for (int t = 0; t < GKT; ++t)
@@ -1174,16 +1169,9 @@ __global__ __launch_bounds__(256) void wgrad_ring(WgP p, int stages_per_split) {
   const int j16 = lane & 15, g8 = lane >> 4;
   const int wr = wave >> 1, wc = wave & 1;
 
-  // xcd_order (split count a multiple of 8): a split -- one range of positions -- lives on ONE XCD, its tiles dispatched back
-  // to back (consecutive workgroup ids go round-robin over the 8 XCDs): the rows of that range enter one L2 instead of
-  // all eight (PMC round 3: 34.8 MB per launch against 5 MB of operands for the 192 -> 384 k5 gradient)
-  int bx = blockIdx.x, split = blockIdx.y;
-  if (p.xcd_order) {
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int idx = lin >> 3;
-    bx = idx % (int)gridDim.x;
-    split = (lin & 7) + 8 * (idx / (int)gridDim.x);
-  }
+  // plain grid: an XCD-aware decode as in wgrad_deep cut the fetched bytes but made the launch slower (see launch_wgrad_ring)
+  int bx = blockIdx.x;
+  const int split = blockIdx.y;
   const int ch = bx % p.nchunk; bx /= p.nchunk;
   const int tgi = bx % p.ntapgrp;
   const int atile = bx / p.ntapgrp;
@@ -1303,10 +1291,9 @@ static int deep_kind(const ConvP& p, int dtype, int out_ch, int k_ch, int nphase
   if (p.nchunk * 32 != k_ch) return 0;                     // prepared image must be the ck = 32 layout
   if ((long)p.nseq * p.Q >= (1L << 31) - BN) return 0;
   const long units = (long)p.nseq * p.Q;
-  static const long min128 = getenv("EVT_DEEP_MIN_TILES") ? atol(getenv("EVT_DEEP_MIN_TILES")) : 192;   // tuning knob
+  constexpr long min128 = 192;                             // fewest 128 x 128 tiles that still beat the ring (tuned)
   if (out_ch % BM == 0 && ((units + BN - 1) / BN) * (out_ch / BM) * nphase >= min128) return 2;
-  static const bool no_ring = getenv("EVT_NO_RING") != nullptr;   // A/B switch for measurements
-  if (!no_ring && k_ch % BK == 0 && ((units + 63) / 64) * (out_ch / 64) * nphase >= 32) return 1;
+  if (k_ch % BK == 0 && ((units + 63) / 64) * (out_ch / 64) * nphase >= 32) return 1;
   return 0;
 }
 
@@ -1343,9 +1330,8 @@ int launch_conv_deep(const ConvP& p_in, int out_ch, int k_ch, int nphase, hipStr
   p.U = 0;
   // short reductions (<= 12 stages of 64) and K-side widths that are not multiples of 64: 32-channel stages, twice the
   // resident blocks (measured: 128->512 k5 s3 49 -> 37 us; the 40-80-stage 1024-wide layers are better with 64)
-  static const int deep32 = getenv("EVT_DEEP32") ? atoi(getenv("EVT_DEEP32")) : -1;   // A/B switch: 0 never, 1 always
   const bool short_k = (k_ch / 64) * p.KHp <= 12;
-  if (deep32 == 1 || k_ch % 64 || (deep32 != 0 && short_k)) {
+  if (k_ch % 64 || short_k) {
     static bool attr32 = false;
     const size_t lds32 = 2 * STAGE32 > 128 * 272 ? 2 * STAGE32 : 128 * 272;   // operand stages, then the staged output tile
     if (!attr32) {
@@ -1405,9 +1391,8 @@ int launch_wgrad_deep(const WgP& p_in, hipStream_t st) {
   p.nchunk = p.CB / 32;
   p.ntapgrp = (p.KHp + WKT - 1) / WKT;
   const long tiles = (long)(p.CA / 128) * p.nchunk * p.ntapgrp;
-  // XCD-aware tile order (EVT_WGRAD_DEEP_XCD=0: plain decode): needs an even number of dy tiles and chunks in fours
-  static const bool xcd_on = !(getenv("EVT_WGRAD_DEEP_XCD") && atoi(getenv("EVT_WGRAD_DEEP_XCD")) == 0);
-  p.xcd_order = (xcd_on && (p.CA / 128) % 2 == 0 && p.nchunk % 4 == 0) ? 1 : 0;
+  // XCD-aware tile order: needs an even number of dy tiles and chunks in fours (else the plain decode)
+  p.xcd_order = ((p.CA / 128) % 2 == 0 && p.nchunk % 4 == 0) ? 1 : 0;
   const int nstages = (int)(((long)p.nseq * p.Q + WPOS - 1) / WPOS);
   // ~2 blocks per CU in flight, >= 8 K stages per block so the pipeline amortises its fill and the atomics; slab mode:
   // one resident wave of blocks is enough once the tile leaves as plain stores
@@ -1430,8 +1415,7 @@ int launch_wgrad_deep(const WgP& p_in, hipStream_t st) {
 }
 
 bool wgrad_gemm_eligible(const WgP& p, int dtype) {
-  static const bool off = getenv("EVT_NO_WGRAD_GEMM") != nullptr;    // A/B switch for measurements
-  if (off || dtype != EVT_DT_HALF) return false;
+  if (dtype != EVT_DT_HALF) return false;
   if (p.KH != 1 || p.KHp != 1 || p.s != 1 || p.off != 0) return false;
   if (p.CA % 128 || p.CB % 128) return false;
   if (p.Aact || p.Bact || p.a_slope != 1.f || p.b_slope != 1.f) return false;
@@ -1448,26 +1432,22 @@ int launch_wgrad_gemm(const WgP& p_in, hipStream_t st) {
   if (!wgrad_gemm_eligible(p, EVT_DT_HALF)) return EVT_ENOTSUP;
   p.nchunk = p.CB / 32;
   p.ntapgrp = 1;
-  static const bool noepi = getenv("EVT_WGRAD_GEMM_NOEPI") != nullptr;
-  if (noepi) p.parts = -1;
   const long tiles = (long)(p.CA / 128) * (p.CB / 128);
   const int nstages = (int)(((long)p.nseq * p.Q + WPOS - 1) / WPOS);
   // Round 6: HALF a resident wave of blocks (one per CU).  The launch now runs on the s1 engine's side stream next to the
   // backward chain, which fills whatever slots it leaves; what it still pays alone are its fp32 atomics -- memory-side,
   // 1.31 TB/s whatever their scope (profiles/r06_atomics_vs_stores.txt), 15-24 us of a 48-100 us launch at 512 blocks --
   // and half the blocks are half the partial tiles: s1 micro-step 36.43 (512) / 35.91 (384) / 35.83 ms (256) on one box.
-  static const long target = getenv("EVT_WGRAD_GEMM_BLOCKS") ? atol(getenv("EVT_WGRAD_GEMM_BLOCKS")) : 256;
+  constexpr long target = 256;
   long split = (target + tiles - 1) / tiles;
   if (split > nstages / 8) split = nstages / 8;
   if (split < 1) split = 1;
   const int per = (int)((nstages + split - 1) / split);
   split = (nstages + per - 1) / per;
-  // XCD-aware order needs the split count to be a multiple of 8 (EVT_WGRAD_GEMM_XCD=0: the plain grid)
-  static const int xcd = getenv("EVT_WGRAD_GEMM_XCD") ? atoi(getenv("EVT_WGRAD_GEMM_XCD")) : 1;
+  // XCD-aware order needs the split count to be a multiple of 8 (rounded up), else the plain grid
   p.xcd_order = 0;
-  if (xcd && nstages >= 64) {
-    long s8 = xcd == 2 ? (split / 8 * 8) : (split + 7) / 8 * 8;       // 2: round down (measurement variant)
-    if (s8 < 8) s8 = 8;
+  if (nstages >= 64) {
+    const long s8 = (split + 7) / 8 * 8;
     const int per8 = (int)((nstages + s8 - 1) / s8);
     if ((long)per8 * (s8 - 1) < nstages) {       // every split non-empty (an empty one only returns, but keep the grid tight)
       split = s8;
@@ -1520,8 +1500,7 @@ static int launch_ring_inst(const WgP& p, int per, hipStream_t st) {
 }
 
 bool wgrad_ring_eligible(const WgP& p, int dtype) {
-  static const bool no_ring = getenv("EVT_NO_RING") != nullptr;
-  if (no_ring || dtype != EVT_DT_HALF) return false;
+  if (dtype != EVT_DT_HALF) return false;
   if (p.CA % 64 || p.CB % 32) return false;
   if (p.Aact || p.Bact || p.a_slope != 1.f || p.b_slope != 1.f) return false;
   if (p.LA != p.Q) return false;
@@ -1541,20 +1520,13 @@ int launch_wgrad_ring(const WgP& p_in, hipStream_t st) {
   const long tiles128 = p.CA % 128 == 0 ? (long)(p.CA / 128) * p.nchunk * p.ntapgrp : 0;
   const int MA = (tiles128 >= 128 || (tiles128 > 0 && tiles128 * (nstages / 4) >= 512)) ? 4 : 2;
   const long tiles = (long)(p.CA / (32 * MA)) * p.nchunk * p.ntapgrp;
-  static const long target = getenv("EVT_RING_BLOCKS") ? atol(getenv("EVT_RING_BLOCKS")) : 256;   // tuning knob (measured: 256 best)
+  constexpr long target = 256;                    // measured: 256 best
   int nsplit, per;                                // ~1 block per CU: more splits only add partial tiles; >= 3 K stages per block
   wgrad_pick_split(p, tiles, nstages, target, 3, &nsplit, &per);
-  // XCD-aware order, EVT_WGRAD_RING_XCD=1 (default: plain grid): the split count rounded DOWN to a multiple of 8 (it is
-  // bounded by the slabs the caller holds), every split non-empty.  Measured (round 4): FETCH_SIZE of the WN in-layer
-  // gradient (192 -> 384 k5, 3200 positions, 36 tiles x 8 splits) 12.1 -> 1.9 MB per launch, and the launch 15 -> 20 us:
-  // the 36 tiles of a split land on the 32 CUs of one XCD at once.  These operands fit every L2; time decides: off.
-  static const bool xcd_on = getenv("EVT_WGRAD_RING_XCD") && atoi(getenv("EVT_WGRAD_RING_XCD")) == 1;
-  p.xcd_order = 0;
-  if (xcd_on && nsplit >= 8) {
-    const int s8 = nsplit / 8 * 8;
-    const int per8 = (nstages + s8 - 1) / s8;
-    if ((long)per8 * (s8 - 1) < nstages) { nsplit = s8; per = per8; p.xcd_order = 1; }
-  }
+  // Plain grid.  An XCD-aware order (split count a multiple of 8, all tiles of a split on one XCD) was measured in round 4:
+  // FETCH_SIZE of the WN in-layer gradient (192 -> 384 k5, 3200 positions, 36 tiles x 8 splits) 12.1 -> 1.9 MB per launch,
+  // and the launch 15 -> 20 us: the 36 tiles of a split land on the 32 CUs of one XCD at once.  These operands fit every
+  // L2; time decided against it (profiles/r04_wgrad_ring_xcd.txt).
   p.nsplit = nsplit;
   p.now_used = p.prev_used > nsplit ? p.prev_used : nsplit;
   if (p.parts > 0 && p.used_host) *p.used_host = p.now_used;

@@ -142,8 +142,8 @@ int launch_inst(const ConvP& p, hipStream_t st) {
   const int ups = (p.Q + 63) / 64;
   const long total = (long)p.nseq * ups;
   long blocks = (total + 3) / 4;
-  static const long cap = getenv("EVT_NARROW_BLOCKS") ? atol(getenv("EVT_NARROW_BLOCKS")) : 1024;   // tuning knob
-  if (blocks > cap) blocks = cap;                                      // resident blocks, persistent waves
+  constexpr long cap = 1024;                                           // resident blocks, persistent waves
+  if (blocks > cap) blocks = cap;
   static bool attr = false;
   if (lds > 48 * 1024 && !attr) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_narrow<CI, MT, NK>),
@@ -159,8 +159,7 @@ int launch_inst(const ConvP& p, hipStream_t st) {
 }  // namespace
 
 bool narrow_eligible(const ConvP& p, int dtype, int out_ch, int k_ch, int nphase) {
-  static const bool off = getenv("EVT_NO_NARROW") != nullptr;   // A/B switch for measurements
-  if (off || dtype != EVT_DT_HALF || nphase != 1) return false;
+  if (dtype != EVT_DT_HALF || nphase != 1) return false;
   if (p.xact || p.in_slope != 1.f) return false;
   if (p.s_in != 1 || p.s_out != 1 || p.off_out != 0) return false;
   if (!((k_ch == 16 && out_ch == 16) || (k_ch == 32 && out_ch == 32))) return false;

@@ -7,7 +7,6 @@
 //     transposed FIR over an LDS tile of dy_eff; weight gradient = one thread per (channel, tap) over LDS tiles.
 // HBM-bound byte work: coalesced 16-byte reads, LDS only for the small weight vector / block reduction.
 #include "evt_common.h"
-#include <cstdlib>
 #include "../../include/evt.h"
 #include "conv_p.h"
 
@@ -512,7 +511,7 @@ extern "C" int evt_cout1_fwd(const evt_conv1d_params* c, const void* x, const vo
   p.G = G;
   const long total = (long)p.nseq * p.lout;
   long blocks = (total * G + 255) / 256;
-  static const long cap = getenv("EVT_COUT1_FWD_CAP") ? atol(getenv("EVT_COUT1_FWD_CAP")) : 4096;   // measurement knob
+  constexpr long cap = 4096;
   if (blocks > cap) blocks = cap;
   const size_t lds = (size_t)c->k * c->cin * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
@@ -533,8 +532,7 @@ extern "C" int evt_cout1_bwd_weight(const evt_conv1d_params* c, const void* x, c
   if (ws && img * 2 <= ws_floats) {
     // partial rows instead of atomics: the block count is no longer bounded by same-address atomics, and the loop is
     // latency-bound (a trip = 4 positions per lane) -- four times the blocks, a quarter of the trips
-    static const long tgt = getenv("EVT_COUT1_WG_BLOCKS") ? atol(getenv("EVT_COUT1_WG_BLOCKS")) : 1024;   // measurement knob
-    static const long minp = getenv("EVT_COUT1_WG_MINP") ? atol(getenv("EVT_COUT1_WG_MINP")) : 16;
+    constexpr long tgt = 1024, minp = 16;
     ppb = (total + tgt - 1) / tgt;
     if (ppb < minp) ppb = minp;
     const long maxb = ws_floats / img;
@@ -545,11 +543,10 @@ extern "C" int evt_cout1_bwd_weight(const evt_conv1d_params* c, const void* x, c
   int blocks = (int)((total + ppb - 1) / ppb);
   const int V = c->dtype == EVT_DT_HALF ? 8 : 4;
   hipStream_t st = (hipStream_t)stream;
-  static const bool xs_off = getenv("EVT_NO_COUT1_XS") != nullptr;          // A/B switch
   int ppr2 = 1;
   while (ppr2 < c->cin / V) ppr2 <<= 1;
   const size_t lds_xs = (size_t)(256 / ppr2) * c->k * c->cin * sizeof(float);
-  if (!xs_off && p.stride == 1 && p.dil == 1 && (c->k == 3 || c->k == 7) && ppr2 <= 256 && lds_xs <= (60u << 10)) {
+  if (p.stride == 1 && p.dil == 1 && (c->k == 3 || c->k == 7) && ppr2 <= 256 && lds_xs <= (60u << 10)) {
     // x-stationary form: blocks over INPUT rows (same bounds on the block count as below)
     const long rows = (long)p.nseq * p.lin;
     long rpb = (rows + blocks - 1) / blocks;

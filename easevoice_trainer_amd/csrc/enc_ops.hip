@@ -16,7 +16,6 @@
 // counter the engine bumps once per step (evt_counter_inc), so a replayed HIP graph draws fresh masks every step.
 #include "evt_common.h"
 #include <type_traits>
-#include <cstdlib>
 #include "../../include/evt.h"
 
 namespace {
@@ -537,8 +536,7 @@ int evt_res_dropout_ln_bwd(int32_t dtype, const void* x, const void* y, const fl
   if (p > 0.f && !dy) return EVT_EINVAL;
   if (C > 1024 || C % 8) return EVT_ENOTSUP;
   hipStream_t st = (hipStream_t)stream;
-  static const int wide_off = getenv("EVT_LN_BWD_WAVES4") != nullptr;      // A/B switch for measurements
-  const bool wide = rows >= 8192 && !wide_off;
+  const bool wide = rows >= 8192;
   const int maxb = wide ? 512 : 256;            // each block ends with one atomic per channel
   long rpb = (rows + maxb - 1) / maxb;
   if (rpb < 16) rpb = 16;

@@ -79,17 +79,6 @@ __device__ __forceinline__ void mma_quadrant(f32x4 (&acc)[8][4], const h16x8 (&a
             EVT_MFMA_16x16x32(af[i][ks], bfr[j][ks], acc[QA * 4 + i][QB * 2 + j], 0, 0, 0);
 }
 
-// ablation variants: the fragment registers stay live (and their ds_reads issued) without the matrix pipe
-__device__ __forceinline__ void keep_frags(const h16x8 (&af)[4][2], const h16x8 (&bfr)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { asm volatile("" ::"v"(af[i][0])); asm volatile("" ::"v"(af[i][1])); }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) { asm volatile("" ::"v"(bfr[j][0])); asm volatile("" ::"v"(bfr[j][1])); }
-}
-
-// VAR: measurement variants (tools/bench_gemm256.py; the product launches VAR = 0): bit 0 no MFMAs, bit 1 no DMA after the
-// prologue, bit 2 no fragment reads, bit 3 no epilogue stores
-template <int VAR>
 __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -139,14 +128,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
   // piece (kt, region): two DMA instructions per wave
   auto issue_a = [&](int kt, int region) {
     unsigned char* dst = my + (kt & 1) * KTB + region * PIECE;
-    if ((VAR & 2) && kt > 1) return;
 #pragma unroll
     for (int i = 0; i < 2; ++i) glds16(p.a + offs[region][i] + kt * 64, dst + i * 1024);
   };
   auto issue_b = [&](int kt, int region) {
     unsigned char* dst = my + (kt & 1) * KTB + region * PIECE;
     const int h = region == R_B1;
-    if ((VAR & 2) && kt > 0) return;
 #pragma unroll
     for (int i = 0; i < 2; ++i) glds16(bok[h][i] ? p.b + offs[region][i] + kt * 64 : zsrc, dst + i * 1024);
   };
@@ -164,14 +151,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
   const int b_row = (wc * 32 + n) * 128;                   // + (j & 1) * 16 * 128
 
   h16x8 af[4][2], bfr[2][2];
-  if (VAR & 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { af[i][0] = af[i][1] = h16x8{}; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { bfr[j][0] = bfr[j][1] = h16x8{}; }
-  }
   auto load_a = [&](const unsigned char* piece) {
-    if (VAR & 4) return;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       af[i][0] = *reinterpret_cast<const h16x8*>(piece + a_row + i * 2048 + so0);
@@ -179,7 +159,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
     }
   };
   auto load_b = [&](const unsigned char* piece) {
-    if (VAR & 4) return;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       bfr[j][0] = *reinterpret_cast<const h16x8*>(piece + b_row + j * 2048 + so0);
@@ -204,8 +183,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
     READS;                                              \
     ISSUE;                                              \
     __builtin_amdgcn_s_setprio(1);                      \
-    if (!(VAR & 1)) mma_quadrant<QA, QB>(acc, af, bfr); \
-    else keep_frags(af, bfr);                           \
+    mma_quadrant<QA, QB>(acc, af, bfr);                 \
     __builtin_amdgcn_s_setprio(0);                      \
     asm volatile("" ::: "memory");                      \
   }
@@ -232,12 +210,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
   }
 #undef PHASE
 
-  if ((VAR & 8) && p.M > 0) {
-    if (acc[0][0][0] == 12345.678f) p.out[0] = 1;    // data-dependent, never true: the accumulators stay live
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    continue;
-  }
   // ---- epilogue.  A lane holds channels g*4..g*4+3 of token n of each 16 x 16 tile: stored from there, every store
   //      instruction would write 16 rows x 32 bytes, and the 100 MB of a [32768, 1536] output took longer than the whole
   //      reduction (measured: 114 us with, 49 us without the stores).  So the wave's 64 x 128 tile goes through LDS once
@@ -280,8 +252,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt(G256 p) {
     const int trow = r * 4 + rrow;
     const int row = pb * 256 + wc * 64 + trow;
     if (row >= p.M) continue;
-    // VAR bit 4 (measurement): every token tile writes the rows of tile 0 -- the output stays L2-resident
-    const long off = (long)((VAR & 16) ? (row & 255) : row) * p.NO + yi * 256 + wr * 128 + c16 * 8;
+    const long off = (long)row * p.NO + yi * 256 + wr * 128 + c16 * 8;
     uint4 v = *reinterpret_cast<const uint4*>(ep + trow * EP_PITCH + c16 * 16);
     if (p.gate || p.add) {
       uint4 gv = make_uint4(0, 0, 0, 0), av = make_uint4(0, 0, 0, 0);
@@ -354,7 +325,7 @@ __device__ __forceinline__ void wait_vmcnt_dyn(int n) {
 }
 
 template <bool DROP>
-__global__ __launch_bounds__(512, 2) void gemm256_pipe(G256 p, int g_store_nt) {
+__global__ __launch_bounds__(512, 2) void gemm256_pipe(G256 p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -534,13 +505,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_pipe(G256 p, int g_store_nt) {
     u32x4* d0 = reinterpret_cast<u32x4*>(base + (size_t)st_lane);
     u32x4* d1 = reinterpret_cast<u32x4*>(base + (size_t)(16u * (unsigned)p.NO) + (size_t)st_lane);
     const bool ok0 = trow0 + 16 <= p.M || trow0 + rrow < p.M, ok1 = trow0 + 16 <= p.M || trow0 + rrow + 8 < p.M;
-    if (g_store_nt) {       // measurement switch (EVT_GEMM256_NT=1): streaming stores that do not allocate in the L2
-      if (ok0) __builtin_nontemporal_store(va, d0);
-      if (ok1) __builtin_nontemporal_store(vb, d1);
-    } else {
-      if (ok0) *d0 = va;
-      if (ok1) *d1 = vb;
-    }
+    if (ok0) *d0 = va;
+    if (ok1) *d1 = vb;
     return 2;
   };
   auto zero_quadrant = [&](auto qa_tag, auto qb_tag) {
@@ -651,8 +617,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_pipe(G256 p, int g_store_nt) {
   }
 }
 
-int g_variant = 0;     // measurement switch (evt_debug_gemm256_variant); 0 = the product kernel
-
 bool eligible(const evt_gemm_params* g, int kred, int nout) {
   if (g->dtype != EVT_DT_HALF) return false;
   if (nout % 256 || kred % 64 || kred < 128) return false;
@@ -689,13 +653,11 @@ int launch(const evt_gemm_params* g, const void* a, const void* b, int kred, int
     if (ncu <= 0) ncu = 8;
   }
   const dim3 grid(nvirt < ncu ? nvirt : ncu);
-  // the pipelined kernel takes every launch without a gate / residual operand (EVT_GEMM256_PIPE=0: the round-3 kernel)
-  static const bool pipe_on = !(getenv("EVT_GEMM256_PIPE") && atoi(getenv("EVT_GEMM256_PIPE")) == 0);
+  // the pipelined kernel takes every launch without a gate / residual operand
   // (one long-K tile per block -- [32768, 512, 2048]: 256 tiles, 32 K tiles each -- has no boundary to hide and runs 5 % faster
   //  on the round-3 loop: 68 against 72 us)
-  static const int pipe_force = getenv("EVT_GEMM256_PIPE") ? atoi(getenv("EVT_GEMM256_PIPE")) : 1;
-  const bool pipe_shape = nvirt > (int)grid.x || (p.K >> 6) <= 12 || pipe_force == 2;
-  if (pipe_on && pipe_shape && g_variant == 0 && !p.gate && !p.add && (long)p.M * p.NO < (1L << 32)) {
+  const bool pipe_shape = nvirt > (int)grid.x || (p.K >> 6) <= 12;
+  if (pipe_shape && !p.gate && !p.add && (long)p.M * p.NO < (1L << 32)) {
     evt_set_last_tag("gemm256_pipe<bf16, 256, 256, 64>");
     static bool attr_p[2] = {false, false};
     const int d = p.thr ? 1 : 0;
@@ -704,45 +666,25 @@ int launch(const evt_gemm_params* g, const void* a, const void* b, int kred, int
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_PIPE) != hipSuccess) return EVT_ELAUNCH;
       attr_p[d] = true;
     }
-    static const int nt_st = getenv("EVT_GEMM256_NT") ? atoi(getenv("EVT_GEMM256_NT")) : 0;
-    if (d) hipLaunchKernelGGL(gemm256_pipe<true>, grid, dim3(512), LDS_PIPE, st, p, nt_st);
-    else hipLaunchKernelGGL(gemm256_pipe<false>, grid, dim3(512), LDS_PIPE, st, p, nt_st);
+    if (d) hipLaunchKernelGGL(gemm256_pipe<true>, grid, dim3(512), LDS_PIPE, st, p);
+    else hipLaunchKernelGGL(gemm256_pipe<false>, grid, dim3(512), LDS_PIPE, st, p);
     return evt_check_launch();
   }
   evt_set_last_tag("gemm256_nt<bf16, 256, 256, 64>");
-#define G256_LAUNCH(V)                                                                                                  \
-  {                                                                                                                     \
-    static bool attr = false;                                                                                           \
-    if (!attr) {                                                                                                        \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_nt<V>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds) != hipSuccess)                                                                  \
-        return EVT_ELAUNCH;                                                                                             \
-      attr = true;                                                                                                      \
-    }                                                                                                                   \
-    hipLaunchKernelGGL(gemm256_nt<V>, grid, dim3(512), lds, st, p);                                                     \
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_nt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess)
+      return EVT_ELAUNCH;
+    attr = true;
   }
-  switch (g_variant) {
-    case 0: G256_LAUNCH(0) break;
-    case 1: G256_LAUNCH(1) break;
-    case 2: G256_LAUNCH(2) break;
-    case 4: G256_LAUNCH(4) break;
-    case 5: G256_LAUNCH(5) break;
-    case 6: G256_LAUNCH(6) break;
-    case 8: G256_LAUNCH(8) break;
-    case 9: G256_LAUNCH(9) break;
-    case 16: G256_LAUNCH(16) break;
-    case 17: G256_LAUNCH(17) break;
-    default: return EVT_EINVAL;
-  }
-#undef G256_LAUNCH
+  hipLaunchKernelGGL(gemm256_nt, grid, dim3(512), lds, st, p);
   return evt_check_launch();
 }
 
 }  // namespace
 
 extern "C" {
-
-void evt_debug_gemm256_variant(int32_t v) { g_variant = v; }
 
 int32_t evt_gemm_bf16_fused_supported(const evt_gemm_params* g, int32_t backward_data) {
   if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0) return 0;

@@ -19,7 +19,6 @@
 // size.  Three 20-30 us launches whose length is mostly fill and drain become one.
 #include "resunit_common.h"
 #include "../../include/evt.h"
-#include <cstdlib>
 
 namespace {
 
@@ -222,8 +221,7 @@ template <int CI, int NK>
 int launch(const RUP& p, size_t lds, hipStream_t st) {
   const int per_cu = (int)((160 * 1024) / lds) < 4 ? (int)((160 * 1024) / lds) : 4;
   long blocks = (p.total + 3) / 4;
-  static const long cap_env = getenv("EVT_RESUNIT_BLOCKS") ? atol(getenv("EVT_RESUNIT_BLOCKS")) : 0;   // tuning knob
-  const long cap = cap_env > 0 ? cap_env : 256L * per_cu;
+  const long cap = 256L * per_cu;
   if (blocks > cap) blocks = cap;
   static bool attr = false;
   if (set_lds_once(&resunit_fwd<CI, NK>, &attr)) return EVT_ELAUNCH;
@@ -245,8 +243,7 @@ bool job_ok(const evt_resunit_params* a) {
 extern "C" {
 
 int32_t evt_resunit_supported(const evt_resunit_params* a) {
-  static const bool off = getenv("EVT_NO_RESUNIT") != nullptr;   // A/B switch for measurements
-  return (!off && job_ok(a)) ? 1 : 0;
+  return job_ok(a) ? 1 : 0;
 }
 
 int evt_resunit_fwd(const evt_resunit_params* a, const void* x, const void* w1_reg, const void* w2_reg, const float* b1,
@@ -272,8 +269,6 @@ int evt_resunit_fwd(const evt_resunit_params* a, const void* x, const void* w1_r
 
 int evt_resunit_fwd_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, void* stream) {
   if (!jobs || njobs < 1 || njobs > 3) return EVT_EINVAL;
-  static const bool off = getenv("EVT_NO_RESUNIT_MULTI") != nullptr;   // A/B switch for measurements
-  if (off) return EVT_ENOTSUP;
   RUPM pm{};
   size_t lds = 0;
   double cost[3] = {0, 0, 0};
@@ -294,8 +289,7 @@ int evt_resunit_fwd_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, void* 
     cost[slot] = (double)p.total * (1.0 + 0.12 * jb.p.k);  // measured single launches: 20 / 21 / 21.5 us (C = 16), 21 / 25 / 29 (C = 32)
   }
   const int per_cu = (int)((160 * 1024) / lds) < 4 ? (int)((160 * 1024) / lds) : 4;
-  static const long cap_env = getenv("EVT_RESUNIT_BLOCKS") ? atol(getenv("EVT_RESUNIT_BLOCKS")) : 0;
-  const long cap = cap_env > 0 ? cap_env : 256L * per_cu;
+  const long cap = 256L * per_cu;
   const double tot = cost[0] + cost[1] + cost[2];
   int end = 0;
   for (int s = 0; s < 3; ++s) {

@@ -34,7 +34,6 @@
 // conflict-free for the 16-byte MFMA-operand reads (rows n + shift, any shift) and for the transpose reads.
 #include "resunit_common.h"
 #include "../../include/evt.h"
-#include <cstdlib>
 
 namespace {
 
@@ -476,8 +475,7 @@ int launch_multi_nt(const RBPM& pm, const int (&nt)[3], size_t lds, int njobs, h
 extern "C" {
 
 int32_t evt_resunit_bwd_supported(const evt_resunit_params* a, int32_t with_weight_grads) {
-  static const bool off = getenv("EVT_NO_RESUNIT_BWD") != nullptr;   // A/B switch for measurements
-  if (off || !evt_resunit_supported(a)) return 0;
+  if (!evt_resunit_supported(a)) return 0;
   Geo geo;
   return geometry(a->C, a->k, a->dil, with_weight_grads != 0, &geo) ? 1 : 0;
 }
@@ -493,8 +491,6 @@ int64_t evt_resunit_bwd_ws_floats(const evt_resunit_params* a) {
 // caller runs evt_conv1d_bwd_weight for it.
 int evt_resunit_bwd_multi(const evt_resunit_bwd_job* jobs, int32_t njobs, float* ws, int64_t ws_floats, void* stream) {
   if (!jobs || njobs < 1 || njobs > 3) return EVT_EINVAL;
-  static const bool multi_off = getenv("EVT_NO_RESUNIT_MULTI") != nullptr;   // A/B switch for measurements
-  if (multi_off && njobs > 1) return EVT_ENOTSUP;
   RBPM pm{};
   const int C = jobs[0].p.C;
   size_t lds = 0;
@@ -550,8 +546,7 @@ int evt_resunit_bwd_multi(const evt_resunit_bwd_job* jobs, int32_t njobs, float*
   }
   if (lds > 160 * 1024) return EVT_ENOTSUP;
   const int per_cu = (int)((160 * 1024) / lds) < 2 ? (int)((160 * 1024) / lds) : 2;
-  static const long cap_env = getenv("EVT_RESUNIT_BWD_BLOCKS") ? atol(getenv("EVT_RESUNIT_BWD_BLOCKS")) : 0;
-  long cap = cap_env > 0 ? cap_env : 256L * per_cu;
+  long cap = 256L * per_cu;
   const double tot = cost[0] + cost[1] + cost[2];
   // the partial rows must fit the scratch
   for (;;) {

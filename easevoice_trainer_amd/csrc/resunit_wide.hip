@@ -22,7 +22,6 @@
 //     K step are requested before the MFMAs of this one (software pipelining by hand, see resunit_common.h).
 #include "resunit_common.h"
 #include "../../include/evt.h"
-#include <cstdlib>
 
 namespace {
 
@@ -319,8 +318,7 @@ bool wide_ok(const evt_resunit_params* a) {
 extern "C" {
 
 int32_t evt_resunit_wide_supported(const evt_resunit_params* a) {
-  static const bool off = getenv("EVT_NO_RESUNIT_WIDE") != nullptr;   // A/B switch for measurements
-  return (!off && wide_ok(a)) ? 1 : 0;
+  return wide_ok(a) ? 1 : 0;
 }
 
 int evt_resunit_wide_fwd(const evt_resunit_params* a, const void* x, const void* w1_reg, const void* w2_reg, const float* b1,

@@ -6,7 +6,6 @@
 // through LDS; each lane streams its own 16-byte pieces of the weight row straight from global memory.
 // Forward takes the REG image (for k = 1: W row-major [N][K]), backward-data the ALT image (W^T row-major [K][N]).
 #include "conv_p.h"
-#include <cstdlib>
 
 namespace {
 
@@ -54,8 +53,7 @@ namespace evt_conv {
 
 // k = 1, dense, un-fused, at most 16 rows in total: true when rows16 takes the launch
 bool rows16_eligible(const evt_conv1d_params* c, int rows, int n_out, int k_red, bool fused) {
-  static const bool off = getenv("EVT_NO_ROWS16") != nullptr;
-  return !off && !fused && c->dtype == EVT_DT_HALF && c->impl == EVT_IMPL_AUTO && c->k == 1 && c->stride == 1 &&
+  return !fused && c->dtype == EVT_DT_HALF && c->impl == EVT_IMPL_AUTO && c->k == 1 && c->stride == 1 &&
          c->groups == 1 && !c->transposed && c->pad == 0 && rows <= 16 && n_out % 16 == 0 && k_red % 32 == 0;
 }
 

@@ -248,8 +248,7 @@ int launch_inst(const WgP& p, int spq, int per, hipStream_t st) {
 }  // namespace
 
 bool wgrad_halo_eligible(const WgP& p, int dtype) {
-  static const bool off = getenv("EVT_NO_HALO") != nullptr;           // A/B switch for measurements
-  if (off || dtype != EVT_DT_HALF) return false;
+  if (dtype != EVT_DT_HALF) return false;
   if (p.s != 1 || p.KHp != p.KH) return false;
   if (p.KH != 3 && p.KH != 5 && p.KH != 7 && p.KH != 11) return false;
   if ((p.CA % 64 && p.CA != 32) || p.CB % 32) return false;
@@ -263,8 +262,7 @@ bool wgrad_halo_eligible(const WgP& p, int dtype) {
   // 64-channel tile here is bound by its LDS reads (52 transpose reads per 44 MFMAs).  So: 64 dy channels only
   // (EVT_HALO_ALL=1 lifts that for measurements).
   static const bool all = getenv("EVT_HALO_ALL") != nullptr;
-  static const bool no32 = getenv("EVT_HALO_NO32") != nullptr;
-  if (!all && p.CA != 64 && !(p.CA == 32 && !no32)) return false;
+  if (!all && p.CA != 64 && p.CA != 32) return false;
   if (p.CA % 128 == 0 && (long)(p.CA / 128) * (p.CB / 32) >= 128) return false;
   // sequence-local stages: the tail stage of a sequence is partly zero rows; DiscriminatorP's 23..127-long sequences
   // stay on the flat-position kernels
@@ -283,12 +281,10 @@ int launch_wgrad_halo(const WgP& p_in, hipStream_t st) {
   const int nstages = p.nseq * spq;
   // 128-channel tiles when that still yields enough blocks, else 64
   const long tiles128 = p.CA % 128 == 0 ? (long)(p.CA / 128) * p.nchunk : 0;
-  static const int force_ma = getenv("EVT_HALO_MA") ? atoi(getenv("EVT_HALO_MA")) : 0;
   int MA = tiles128 >= 64 ? 4 : 2;
-  if (force_ma == 2 || (force_ma == 4 && tiles128 > 0)) MA = force_ma;
   if (p.CA == 32) MA = 1;                        // the 32-channel vocoder stage: one tile, all the parallelism from the split
   const long tiles = (long)(p.CA / (32 * MA)) * p.nchunk;
-  static const long target = getenv("EVT_HALO_BLOCKS") ? atol(getenv("EVT_HALO_BLOCKS")) : 256;
+  constexpr long target = 256;
   int nsplit, per;
   wgrad_pick_split(p, tiles, nstages, target, 3, &nsplit, &per);
   p.nsplit = nsplit;

@@ -28,7 +28,6 @@
 // The tensors the backward needs (x_in, acts) are written as before; backward is unchanged (hip/wn.py).
 #include "resunit_common.h"
 #include "../../include/evt.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -540,6 +539,13 @@ __global__ __launch_bounds__(256) void frag_pack_kernel(const evt_frag_item* ite
   }
 }
 
+// The product is launch<1, 8, LAST>.  Positions per block (16 NT) and ring depth were measured on the B = 16 x 200 shape as a
+// replayed graph of 16 layers with every layer's weights a first touch (tools/bench_wn.py --flush;
+// profiles/r05_wn_layer.txt), us per layer:
+//   NT = 1 (208 blocks): 18.0   NT = 2 (112 blocks): 20.0   NT = 3 (80 blocks): 35 (before the epilogue loads were hoisted)
+//   ring 4 and 8 alike; the four launches this replaces: 25.5.  In the s2 step: 22.96-22.98 ms (NT = 1), 23.10-23.18
+//   (NT = 2), 23.29-23.33 with the four launches.  More positions per block do not pay: a block is bound by its own
+//   serial chain (stage rows, 884 KB of weights at the CU's 64 B/clk, two epilogues), and the chip has CUs to spare.
 template <int NT, int R, bool LAST>
 int launch(WNP p, hipStream_t st) {
   constexpr int H = 192, K = 5, P = 16 * NT;
@@ -550,26 +556,8 @@ int launch(WNP p, hipStream_t st) {
   return evt_check_launch();
 }
 
-template <bool LAST>
-int launch_nt(WNP p, hipStream_t st) {
-  // positions per block (16 NT) and ring depth, measured on the B = 16 x 200 shape as a replayed graph of 16 layers with
-  // every layer's weights a first touch (tools/bench_wn.py --flush; profiles/r05_wn_layer.txt), us per layer:
-  //   NT = 1 (208 blocks): 18.0   NT = 2 (112 blocks): 20.0   NT = 3 (80 blocks): 35 (before the epilogue loads were hoisted)
-  //   ring 4 and 8 alike; the four launches this replaces: 25.5.  In the s2 step: 22.96-22.98 ms (NT = 1), 23.10-23.18
-  //   (NT = 2), 23.29-23.33 with the four launches.  More positions per block do not pay: a block is bound by its own
-  //   serial chain (stage rows, 884 KB of weights at the CU's 64 B/clk, two epilogues), and the chip has CUs to spare.
-  static const int nt = getenv("EVT_WN_NT") ? atoi(getenv("EVT_WN_NT")) : 1;
-  static const int ring = getenv("EVT_WN_RING") ? atoi(getenv("EVT_WN_RING")) : 8;
-  if (ring <= 4) {
-    if (nt == 1) return launch<1, 4, LAST>(p, st);
-    if (nt == 3) return launch<3, 4, LAST>(p, st);
-    return launch<2, 4, LAST>(p, st);
-  }
-  if (nt == 1) return launch<1, 8, LAST>(p, st);
-  if (nt == 3) return launch<3, 8, LAST>(p, st);
-  return launch<2, 8, LAST>(p, st);
-}
-
+// The product is launch_b<1, 8, LAST>.  16 or 32 own positions per block: 22.38 / 22.44 vs 22.44 / 22.37 ms per s2 step --
+// alike; 16 keeps the LDS under 64 KB
 template <int NT, int R, bool LAST>
 int launch_b(WNB p, hipStream_t st) {
   constexpr int H = 192, K = 5, P = 16 * NT;
@@ -587,21 +575,12 @@ int launch_b(WNB p, hipStream_t st) {
   return evt_check_launch();
 }
 
-template <bool LAST>
-int launch_b_nt(WNB p, hipStream_t st) {
-  // 16 or 32 own positions per block: 22.38 / 22.44 vs 22.44 / 22.37 ms per s2 step -- alike; 16 keeps the LDS under 64 KB
-  static const int nt = getenv("EVT_WN_BWD_NT") ? atoi(getenv("EVT_WN_BWD_NT")) : 1;
-  if (nt == 2) return launch_b<2, 8, LAST>(p, st);
-  return launch_b<1, 8, LAST>(p, st);
-}
-
 }  // namespace
 
 extern "C" {
 
 int32_t evt_wn_layer_supported(int32_t dtype, int32_t H, int32_t k, int32_t dil) {
-  static const bool off = getenv("EVT_NO_WN_LAYER") != nullptr;      // A/B switch for measurements
-  return (!off && dtype == EVT_DT_HALF && H == 192 && k == 5 && dil == 1) ? 1 : 0;
+  return (dtype == EVT_DT_HALF && H == 192 && k == 5 && dil == 1) ? 1 : 0;
 }
 
 int evt_frag_pack(const evt_frag_item* items, int32_t nitems, void* stream) {
@@ -622,7 +601,7 @@ int evt_wn_layer_fwd(int32_t dtype, const void* x, const void* w_in_frag, const 
   p.x_in = (h16_t*)x_in; p.acts = (h16_t*)acts; p.x_out = (h16_t*)x_out; p.acc_out = (h16_t*)acc_out;
   p.nseq = nseq; p.L = L;
   hipStream_t st = (hipStream_t)stream;
-  return last ? launch_nt<true>(p, st) : launch_nt<false>(p, st);
+  return last ? launch<1, 8, true>(p, st) : launch<1, 8, false>(p, st);
 }
 
 int evt_wn_layer_bwd_data(int32_t dtype, const void* dx_next, const void* dacc, const void* x_in, const void* g,
@@ -637,7 +616,7 @@ int evt_wn_layer_bwd_data(int32_t dtype, const void* dx_next, const void* dacc, 
   p.drs = (h16_t*)drs; p.dx_in = (h16_t*)dx_in; p.dx = (h16_t*)dx; p.dg = dg;
   p.nseq = nseq; p.L = L;
   hipStream_t st = (hipStream_t)stream;
-  return last ? launch_b_nt<true>(p, st) : launch_b_nt<false>(p, st);
+  return last ? launch_b<1, 8, true>(p, st) : launch_b<1, 8, false>(p, st);
 }
 
 }  // extern "C"

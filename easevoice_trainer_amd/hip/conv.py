@@ -160,16 +160,13 @@ class WeightBank:
         self.dt = L.dt_code(dtype)
         self.dtype, self.device, self.impl = dtype, torch.device(device), impl
         self.weight_grads = True
-        # EVT_ASYNC_WGRAD=1: weight gradients on a side HIP stream next to the backward-data chain; grads() joins and
-        # the operands are held until then.  Measured on MI355X: -1.6 ms/step with eager launches, +7 ms/step under
-        # HIP-graph replay (fork/join edges per conv), so it is off by default.
-        self.async_wgrad = self.device.type == "cuda" and os.environ.get("EVT_ASYNC_WGRAD", "0") == "1"
-        # EVT_WGRAD_DEFER=N (default 64; 0 = off): weight-gradient launches are queued and handed to a side HIP stream N at
+        # EVT_WGRAD_DEFER=N (default 48; 0 = off): weight-gradient launches are queued and handed to a side HIP stream N at
         # a time -- ONE fork per batch instead of one per convolution -- so the backward-data chain (the critical path:
         # every launch waits for the one before it) shares the chip with the weight gradients, which depend on nothing
         # but their two operands.  grads() joins.  The operands are held until the join.  Measured on MI355X, s2 step
         # under HIP-graph replay, three interleaved rounds: 27.85-27.95 ms without, 27.14-27.18 ms with N = 64; small N
-        # (a fork every few convolutions) is what made EVT_ASYNC_WGRAD slower under replay.
+        # is slower under replay: one fork per convolution was measured at -1.6 ms/step with eager launches and
+        # +7 ms/step under HIP-graph replay (fork/join edges per conv).
         # Round 6, under the branch streams (profiles/r06_streams.txt): the generator's ~150 launches flushed every 48 instead
         # of every 64 is 0.3 ms ahead (40-56 level except 52; 32 and 80-96 behind -- it matters which stretch of the backward a
         # flush lands beside); the discriminators' 42 stay one flush at the end either way (in pieces: +0.2 ms).
@@ -227,9 +224,9 @@ class WeightBank:
         # fold at the end of the backward (wn_grad).  32 until the launches moved off the critical path (side stream, branch
         # streams); since then the fold's bytes weigh more: 16-24 measured level and 0.2 ms ahead of 32, 8 and 4 behind
         # (profiles/r06_streams.txt)
-        cap = int(os.environ.get("EVT_WGRAD_PARTS_CAP", "20"))
+        cap = 20
         # operands held for the deferred weight-gradient launches: flushed on a byte budget as well as on a count
-        self.defer_bytes = int(os.environ.get("EVT_WGRAD_DEFER_MB", str(max(256, int(4096 * mem_scale))))) << 20
+        self.defer_bytes = max(256, int(4096 * mem_scale)) << 20
         self._deferred_bytes = 0
         ex_n = db_n = 0
         ex_offs = []
@@ -652,13 +649,6 @@ def _bwd_weight(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope):
         bank._deferred_bytes += x.numel() * x.element_size() + dy.numel() * dy.element_size()
         if len(bank._deferred) >= bank.defer_n or bank._deferred_bytes >= bank.defer_bytes:
             bank.flush_deferred()
-        return
-    if bank.async_wgrad and TRACE is None:
-        side = bank.side_stream()
-        side.wait_stream(torch.cuda.current_stream(bank.device))
-        with torch.cuda.stream(side):
-            _bwd_weight_now(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope)
-        bank._held.append((x, dy, y))
         return
     _bwd_weight_now(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope)
 
@@ -1104,8 +1094,6 @@ class ResStageFn(torch.autograd.Function):
 def res_stage(x, blocks, slope: float, scale: float):
     """mean over `blocks` (ResBlock1 modules) of block(x), through the grouped kernels; None when the stage is not covered
     (the caller then runs the blocks one by one)"""
-    if os.environ.get("EVT_NO_RESSTAGE") == "1":
-        return None
     plan = _stage_plan(x, blocks, slope)
     if plan is None:
         return None

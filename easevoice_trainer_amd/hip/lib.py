@@ -266,8 +266,6 @@ def role_stream(device, role: str, ring: int = 4):
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    if os.environ.get("EVT_POOL_STREAMS", "0") == "1":               # A/B switch: torch's pooled streams, as before
-        return torch.cuda.Stream(device=device)
     pool = _role_pools.setdefault((device.index, role), [[], 0])
     if len(pool[0]) < ring:
         pool[0].append(own_stream(device))

@@ -9,7 +9,6 @@ W and of W^T per layer, rebuilt by ONE multi-tensor launch whenever the optimise
 the per-call `weight.to(bf16)` casts of a torch-level implementation.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -96,8 +95,7 @@ class LinearBank:
         self._side_used = False       # through the modules directly gets its weight gradients in stream order
         # ... and WHEN on the side stream: queued, and handed over in one go right before a layer's attention backward
         # (auto_reg/blocks.py) -- four dW GEMMs (MFMA-bound) beside the three attention kernels (VALU-bound, the matrix pipe
-        # ~85 % idle) share the CUs better than dW GEMMs beside backward-data GEMMs do.  EVT_S1_WGRAD_PAIR=0: hand over at once.
-        self.pair = os.environ.get("EVT_S1_WGRAD_PAIR", "1") != "0"
+        # ~85 % idle) share the CUs better than dW GEMMs beside backward-data GEMMs do.
         self._pending = []
 
     def enable_side_stream(self):
@@ -256,19 +254,10 @@ def gemm_bwd_weight(slot, x, dy, want_bias=True):
     if sunk and bank.side_on and bank.side is not None and x.is_cuda and not torch.cuda.is_current_stream_capturing():
         # straight into the arena, on the side stream: ordered behind what the current stream has enqueued (x, dy exist),
         # the operands kept alive for the allocator until the launch has run; S1Engine joins before it reads the arena
-        if bank.pair:
-            bank._pending.append((p, x, dy, dw_buf, db_buf))
-            bank._side_used = True
-            if len(bank._pending) >= 8:          # no attention backward in sight (a stack of plain linears)
-                bank.flush_pending()
-            return None, None
-        bank.side.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.cuda.stream(bank.side):
-            L.check(L.lib().evt_gemm_bf16_bwd_weight(C.byref(p), L.ptr(x), L.ptr(dy), L.ptr(dw_buf), L.ptr(db_buf),
-                                                     L.stream_ptr()), "evt_gemm_bf16_bwd_weight")
-        x.record_stream(bank.side)
-        dy.record_stream(bank.side)
+        bank._pending.append((p, x, dy, dw_buf, db_buf))
         bank._side_used = True
+        if len(bank._pending) >= 8:          # no attention backward in sight (a stack of plain linears)
+            bank.flush_pending()
         return None, None
     L.check(L.lib().evt_gemm_bf16_bwd_weight(C.byref(p), L.ptr(x), L.ptr(dy), L.ptr(dw_buf), L.ptr(db_buf),
                                              L.stream_ptr()), "evt_gemm_bf16_bwd_weight")

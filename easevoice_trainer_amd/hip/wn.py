@@ -5,7 +5,7 @@ Per layer the arithmetic is the reference's: in_layer conv (k = 5) -> tanh * sig
 res_skip conv (1x1) -> x <- (x + rs[:H]) * mask, out <- out + rs[H:] (last layer: out <- (out + rs) * mask).  The launches
 are the library's: forward ONE per layer in the 16-bit types at the model's shape (evt_wn_layer_fwd, csrc/wn_layer.hip: H =
 192, k = 5; the gate output stays in LDS between the two convolutions), otherwise four (evt_conv1d_fwd, evt_gated_act_fwd,
-evt_conv1d_fwd, evt_wn_residual_fwd: fp32, other shapes, EVT_NO_WN_LAYER=1); backward likewise ONE launch for the data half
+evt_conv1d_fwd, evt_wn_residual_fwd: fp32, other shapes); backward likewise ONE launch for the data half
 (evt_wn_layer_bwd_data) plus the two weight gradients, otherwise four + two; what the
 single node removes is everything between them that torch issued: the element-wise sum of the two gradient branches of
 every layer input (now the add-epilogue of the in_layer backward-data launch), a zero fill and a cast per layer for the

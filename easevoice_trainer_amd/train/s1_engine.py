@@ -36,8 +36,7 @@ class S1Engine:
         pad_rows = (w.size(0) + N_ALIGN - 1) // N_ALIGN * N_ALIGN
         self.arena = ParamArena(self.model, self.device, reserve={"ar_predict_layer.weight": pad_rows * w.size(1)})
         self.bank = self.model.attach_bank(dtype, self.device)
-        if os.environ.get("EVT_S1_WGRAD_SIDE", "1") != "0":       # the dense layers' dW launches next to the backward chain
-            self.bank.enable_side_stream()
+        self.bank.enable_side_stream()       # the dense layers' dW launches next to the backward chain
         o = config["optimizer"]
         self.optimizer = ScaledAdam(self.arena, lr=0.01, betas=(0.9, 0.95), clipping_scale=2.0,
                                     clipping_update_period=1000)

@@ -50,14 +50,11 @@ int32_t evt_half_dtype(void);
 /* Profiling aid, OUTSIDE the contract above and off by default: after evt_debug_kernel_tags(1) every dispatcher
  * records the name of the kernel instantiation it launched in a per-thread buffer that evt_last_kernel_tag() returns
  * (bench.py's roofline leg groups its timings by these names, the same names rocprofv3 prints).  With tags off (the
- * product path) nothing is recorded.  evt_debug_* are the library's ONLY process-global mutable state (two flags and a
- * thread-local name buffer): measurement switches, never read by a computation's arithmetic.  DEBUG ONLY, NOT REENTRANT:
- * switching them while another thread is inside the library is undefined; the product path never calls them. */
+ * product path) nothing is recorded.  evt_debug_kernel_tags is the library's ONLY process-global mutable state (one flag and
+ * a thread-local name buffer): a measurement switch, never read by a computation's arithmetic.  DEBUG ONLY, NOT REENTRANT:
+ * switching it while another thread is inside the library is undefined; the product path never calls it. */
 void evt_debug_kernel_tags(int32_t enable);
 const char* evt_last_kernel_tag(void);
-/* measurement switch of the bf16 attention kernels: 1 = both query/key tiles of a wave in one instruction stream
- * , 0 = one tile at a time (fewer registers, more waves per SIMD; default).  Same results either way. */
-void evt_debug_attn_variant(int32_t joint);
 
 /* Scratch memory the caller must provide, in bytes, for the ops that take a workspace pointer; -1 for an unknown op or
  * a wrong dims count.  The library never allocates.
@@ -500,10 +497,6 @@ typedef struct evt_gemm_epilogue {
   const void* add;          /* [M][out columns] in the GEMM's dtype, or NULL; added last */
 } evt_gemm_epilogue;
 int32_t evt_gemm_bf16_fused_supported(const evt_gemm_params* g, int32_t backward_data);
-/* measurement switch of csrc/gemm256.hip (tools/bench_gemm256.py): ablation variants of the kernel, bit 0 no MFMAs, bit 1
- * no DMA after the prologue, bit 2 no fragment reads, bit 3 no stores; 0 = the product kernel.  Results are only
- * meaningful for 0. */
-void evt_debug_gemm256_variant(int32_t variant);
 int evt_gemm_bf16_fwd_ex(const evt_gemm_params* g, const void* x, const void* w_reg, const void* w_alt, const float* bias,
                          const evt_gemm_epilogue* epi, void* y, void* stream);
 int evt_gemm_bf16_bwd_data_ex(const evt_gemm_params* g, const void* dy, const void* w_reg, const void* w_alt,

@@ -282,7 +282,7 @@ HALO_CASES = [
     (192, 384, 5, 1, 2, 1, 1, False, True, 200, 16),       # WN in_layer: tail of 8 (second half of the stage skipped)
     (192, 768, 3, 1, 1, 1, 1, False, False, 200, 16),      # FFN
     (768, 192, 3, 1, 1, 1, 1, False, False, 200, 16),
-    (512, 256, 7, 1, 3, 1, 1, False, True, 128, 12),       # 128-channel tiles (EVT_HALO_MA=4 forces them elsewhere)
+    (512, 256, 7, 1, 3, 1, 1, False, True, 128, 12),       # 128-channel tiles
     (32, 32, 11, 1, 25, 5, 1, False, True, 1536, 6),       # 32 dy channels: the A tile has the window's geometry
     (64, 32, 7, 1, 3, 1, 1, False, True, 1000, 4),
 ]

@@ -654,3 +654,32 @@ def test_reducer_plan_and_description():
     assert not one.active and GradReducer(1, force=True).active
     with pytest.raises(ValueError):
         GradReducer(2, rsag="sometimes")
+
+
+def test_readme_switch_table_matches_the_code():
+    """every EVT_* variable that the package, cmd/ or the kernels' dispatchers read from the environment has exactly one row in
+    README's switch table, and the table names nothing that is not read"""
+    import glob
+    import re
+
+    name = r"(EVT_[A-Z0-9_]+)"
+    py_reads = [re.compile(p) for p in (r"""os\.environ\.get\(\s*["']""" + name, r"""os\.getenv\(\s*["']""" + name,
+                                        r"""os\.environ\[\s*["']""" + name + r"""["']\s*\](?!\s*=[^=])""",
+                                        r"""["']""" + name + r"""["']\s+(?:not\s+)?in\s+os\.environ""")]
+    c_reads = [re.compile(r"""getenv\(\s*\"""" + name)]
+    files = [(f, py_reads) for f in glob.glob(os.path.join(ROOT, "easevoice_trainer_amd", "**", "*.py"), recursive=True)]
+    files += [(f, py_reads) for f in glob.glob(os.path.join(ROOT, "cmd", "*.py"))]
+    files += [(f, c_reads) for f in glob.glob(os.path.join(ROOT, "easevoice_trainer_amd", "csrc", "*"))
+              if f.endswith((".hip", ".h"))]
+    assert len(files) > 40
+    read = set()
+    for path, pats in files:
+        with open(path, encoding="utf-8") as f:
+            text = f.read()
+        for pat in pats:
+            read.update(pat.findall(text))
+    with open(os.path.join(ROOT, "README.md"), encoding="utf-8") as f:
+        rows = [ln for ln in f if ln.startswith("| `EVT_")]
+    table = [n for ln in rows for n in re.findall(name, ln.split("|")[1])]
+    assert len(table) == len(set(table)) == len(rows), "one row per switch, no switch twice"
+    assert read == set(table), (sorted(read - set(table)), sorted(set(table) - read))

@@ -88,7 +88,6 @@ def main():
     mods = mods.to(dev)
     bank = HC.WeightBank(mods, dtype, dev, impl=a.impl)
     bank.build_tables()
-    bank.async_wgrad = False      # per-call timings below are taken on the current stream
     bank.defer_n = 0
     bank.fold()
     torch.cuda.synchronize()

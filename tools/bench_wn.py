@@ -1,7 +1,6 @@
 """GPU development tool: forward of one WN stack (posterior encoder shape: 16 layers, H = 192, k = 5, B x T = 16 x 200) with the
 one-launch layer (csrc/wn_layer.hip) and with the four launches per layer, alternating in one process, each as a replayed HIP graph; us per layer.
 --flush: a 512 MB fill between the stacks, so every layer's weights are a first touch as in the training step.
-Tile / ring variants: EVT_WN_NT=1|2|3, EVT_WN_RING=4|8 (read once per process).
 
     python tools/bench_wn.py [--dtype bf16|f16] [--flush] [--iters 30]
 """
@@ -93,8 +92,8 @@ def main():
     for fused in (True, False):
         v = sorted(times[fused])
         print(f"{'one launch ' if fused else 'four launches'} per layer: median {v[len(v) // 2]:7.2f} us  min {v[0]:7.2f} us   "
-              f"[{args.dtype}, {B} x {T}, {NL} layers, flush={args.flush}, EVT_WN_NT={os.environ.get('EVT_WN_NT', '1')}, "
-              f"EVT_WN_RING={os.environ.get('EVT_WN_RING', '8')}; graph replay{', forward + backward' if args.backward else ''}]")
+              f"[{args.dtype}, {B} x {T}, {NL} layers, flush={args.flush}; "
+              f"graph replay{', forward + backward' if args.backward else ''}]")
 
 
 if __name__ == "__main__":
