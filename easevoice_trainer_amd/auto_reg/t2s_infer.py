@@ -11,9 +11,13 @@ Same token sequence as the reference for the same sampling noise; a different ex
   * batches: a session of up to four rows runs the kernels above; 5..32 rows share ONE wide session (one prompt pass,
     one step loop) whose linear layers read every weight once per step for all rows (csrc/s1_decode_rows.hip) and whose
     sampler keys each row's noise by a row-seed table, so a row draws what it drew in a group of four.
+  * continuous batching (StreamSession, decode_stream): the counters live per row (csrc/s1_decode_stream.hip), so rows of
+    one session have their own prompt length, step index and limit; a finished row's slot is refilled with the next
+    waiting text between two graph replays and results are handed out as they finish.
 The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
 import ctypes as C
 import os
+import time
 
 import torch
 from torch.nn import functional as F
@@ -134,6 +138,81 @@ class DecodeSession:
         self._sample_embed_advance(W, sp, noise, pe, 1)
 
 
+ROW_WORDS = 8             # include/evt.h EVT_ROW_*
+ROW_POS, ROW_IDX, ROW_YCOUNT, ROW_YLEN, ROW_LIMIT, ROW_STATUS, ROW_NOISE = range(7)
+ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
+
+
+class StreamSession:
+    """static buffers + the captured step graph of a continuously batched session: B slots, each with its own counters
+    rstate[b] (csrc/s1_decode_stream.hip).  Cache slab of a slot: [0, Xmax) the text, padded and masked by x_lens[b];
+    [Xmax, Xmax + ylen[b] + steps) the audio.  All per-row state is device memory, so admitting a text into a free slot
+    changes no launch argument and the graph is captured once per (sampling parameters, noise table)."""
+
+    def __init__(self, model, B, Xmax, Lmax, ymax, dtype, device):
+        self.model, self.B, self.Xmax, self.Lmax, self.ymax = model, B, Xmax, Lmax, ymax
+        self.dtype, self.device = dtype, device
+        E, nl, V = model.model_dim, model.num_layers, model.vocab_size
+        self.E, self.H, self.nl, self.V = E, model.num_head, nl, V
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
+        self.kc = z(nl, B, Lmax, E, dt=dtype)
+        self.vc = z(nl, B, Lmax, E, dt=dtype)
+        self.xa, self.xb = z(B, E), z(B, E)
+        self.qkv, self.att, self.t, self.u = z(B, 3 * E), z(B, E), z(B, E), z(B, E)
+        self.hid = z(B, 4 * E)
+        self.logits = z(B, V)
+        self.y = z(B, ymax, dt=torch.int64)
+        self.state = z(B * (ROW_WORDS + 1), dt=torch.int32)      # rstate [B][8], then stop [B]: one read per poll
+        self.rstate = self.state[:B * ROW_WORDS].view(B, ROW_WORDS)
+        self.stop = self.state[B * ROW_WORDS:]
+        self.x_lens = z(B, dt=torch.int32)
+        self.row_seed = z(B, 2, dt=torch.int32)
+        self.mask = z(B, dt=torch.int32)                          # rows of an admission's step 0
+        self.graph, self.graph_key = None, None
+
+    def reset(self):
+        self.state.zero_()                 # every slot idle
+        self.stop.fill_(-1)
+
+    # ---- launches ----
+    def _gemv(self, w, bias, a, r, g, b, eps, x_out, y, relu=0):
+        N, K = w.shape
+        L.check(L.lib().evt_dec_gemm_rows(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
+                                          C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu),
+                                          L.stream_ptr()), "evt_dec_gemm_rows")
+
+    def _attn(self, i):
+        L.check(L.lib().evt_dec_attn_rows(L.dt_of(self.kc), L.ptr(self.qkv), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
+                                          L.ptr(self.rstate), L.ptr(self.att), self.B, self.H, self.E // self.H,
+                                          self.Lmax, L.ptr(self.x_lens), self.Xmax, L.stream_ptr()), "evt_dec_attn_rows")
+
+    def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
+        """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
+        (each row's workgroup owns its counters); `mask` restricts it to the rows of an admission"""
+        L.check(L.lib().evt_dec_sample_embed_rows(
+            C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise), L.ptr(self.stop), None,
+            L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
+            C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), self.B, self.E, pe.size(0), dpos,
+            L.stream_ptr()), "evt_dec_sample_embed_rows")
+
+    def step_launches(self, W, sp, noise, pe):
+        """one token for every running row: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + one
+        launch for sampling / embedding / counters = 122 launches (a wide DecodeSession: 124).  Idle and stopped rows
+        ride along in the linear layers on stale inputs; the attention and the sampler skip them."""
+        prev = None
+        for i, w in enumerate(W.layers):
+            ln = (None, None, None, 0.0, None) if prev is None else (self.u, prev["g2"], prev["be2"], prev["eps2"], self.xa)
+            src = self.xa if prev is None else self.xb
+            self._gemv(w["wqkv"], w["bqkv"], src, *ln, self.qkv)
+            self._attn(i)
+            self._gemv(w["wo"], w["bo"], self.att, None, None, None, 0.0, None, self.t)
+            self._gemv(w["w1"], w["b1"], self.xa, self.t, w["g1"], w["be1"], w["eps1"], self.xb, self.hid, relu=1)
+            self._gemv(w["w2"], w["b2"], self.hid, None, None, None, 0.0, None, self.u)
+            prev = w
+        self._gemv(W.wpred, None, self.xb, self.u, prev["g2"], prev["be2"], prev["eps2"], None, self.logits)
+        self._sample_embed(W, sp, noise, pe, 1)
+
+
 class T2SInfer:
     """decoder front end bound to one Text2SemanticDecoder; `infer_panel_naive` has the reference's signature"""
 
@@ -193,6 +272,20 @@ class T2SInfer:
             self._wide.append(key)
         if key not in self._sessions:
             self._sessions[key] = DecodeSession(self.model, B, Lmax, ymax, dtype, device)
+        return self._sessions[key]
+
+    def stream_session(self, B, Xmax, Lneed, yneed, dtype, device):
+        """the session cache of session(): capacities rounded to 512, stream sessions share the wide-session LRU"""
+        Lmax, ymax = -(-Lneed // 512) * 512, -(-yneed // 512) * 512
+        key = (B, Lmax, ymax, dtype, str(device), "stream", Xmax)
+        if key in self._wide:
+            self._wide.remove(key)
+        else:
+            while len(self._wide) >= self.WIDE_SESSIONS:
+                del self._sessions[self._wide.pop(0)]
+        self._wide.append(key)
+        if key not in self._sessions:
+            self._sessions[key] = StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device)
         return self._sessions[key]
 
     MAX_ROWS = 4        # rows of a session on the kernels of csrc/s1_decode.hip (kMaxB); also the seed group of a row
@@ -352,4 +445,247 @@ class T2SInfer:
             for k in range(len(rows)):
                 ys.append(ybuf[k, :y_len + last[k]].clone())
                 idxs.append(last[k] - 1 if eos[k] else last[k])
+        return ys, idxs
+
+    # ---- continuous batching: finished rows are refilled from a queue (csrc/s1_decode_stream.hip) ----
+    @staticmethod
+    def _limit(early_stop_num):
+        return MAX_STEPS if early_stop_num == -1 else max(1, min(MAX_STEPS, int(early_stop_num) + 1))
+
+    def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
+                      early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None):
+        """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
+        (x, bert, prompt, early_stop_num) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may
+        differ in content and length.  Returns a generator of (request_index, y, idx) in COMPLETION order, y and idx as
+        infer_panel_batch_infer returns them per text.  Up to `slots` (1..32) texts decode at once in one graph-replayed
+        session; every `poll` steps the rows' status is read, finished rows are handed out and their slots refilled
+        with the next waiting requests (one prompt pass for all of them).  A list has the capacity (longest text,
+        longest prompt, largest limit) computed from itself; a lazy iterable needs max_text_len / max_prompt_len and
+        is bounded by `early_stop_num`.  A request that does not fit raises EvtError before anything is launched for
+        it.  Request r draws the built-in noise of (seed + 4 * (r // 4), r % 4), the convention of
+        infer_panel_batch_infer; an injected table [steps][R][V] is read at column r ([steps][V]: by every request).
+        One stream at a time per model and capacity: the session's buffers are shared."""
+        if self.model.training:
+            raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
+        if not 1 <= int(slots) <= self.WIDE_ROWS:
+            raise L.EvtError(f"slots must be 1..{self.WIDE_ROWS}, got {slots}")
+        nsteps = None if noise is None else int(noise.size(0))
+        ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
+
+        def norm(r, req):
+            if len(req) not in (3, 4):
+                raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num])")
+            x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
+            lim = self._limit(early_stop_num if len(req) == 3 else req[3])
+            if nsteps is not None:
+                lim = min(lim, nsteps)      # an injected noise table also bounds the number of steps
+            if x.numel() < 1 or prompt.numel() < 1:
+                raise L.EvtError(f"request {r}: empty text or prompt")
+            if ncols is not None and r >= ncols:
+                raise L.EvtError(f"request {r}: the noise table has {ncols} columns")
+            return r, x, bert, prompt, lim
+
+        if isinstance(requests, (list, tuple)):
+            reqs = [norm(r, q) for r, q in enumerate(requests)]
+            if not reqs:
+                return iter(())
+            Xmax = int(max_text_len) if max_text_len is not None else max(q[1].numel() for q in reqs)
+            Pmax = int(max_prompt_len) if max_prompt_len is not None else max(q[3].numel() for q in reqs)
+            n_max = max(q[4] for q in reqs)
+            cap = (Xmax, Pmax, n_max)
+            for q in reqs:
+                self._fits(q, cap)
+            it = iter(reqs)
+        else:
+            if max_text_len is None or max_prompt_len is None:
+                raise L.EvtError("a lazy iterable of requests needs max_text_len and max_prompt_len (the session's "
+                                 "capacity is fixed when it is made)")
+            n_max = self._limit(early_stop_num)
+            if nsteps is not None:
+                n_max = min(n_max, nsteps)
+            cap = (int(max_text_len), int(max_prompt_len), n_max)
+            it = (norm(r, q) for r, q in enumerate(requests))
+        return self._stream(it, cap, int(slots), top_k, top_p, temperature, repetition_penalty, noise, seed,
+                            max(1, int(poll)))
+
+    @staticmethod
+    def _fits(q, cap):
+        r, x, _bert, prompt, lim = q
+        if x.numel() > cap[0] or prompt.numel() > cap[1] or lim > cap[2]:
+            raise L.EvtError(f"request {r} (text {x.numel()}, prompt {prompt.numel()}, {lim} steps) does not fit the "
+                             f"session's capacity (text {cap[0]}, prompt {cap[1]}, {cap[2]} steps)")
+
+    @torch.no_grad()
+    def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise):
+        """session, weights, sampling parameters and the captured step graph; every slot idle"""
+        m = self.model
+        cd = m.cd
+        L.set_half(cd)
+        W = self.weights(cd)
+        Xmax, Pmax, n_max = cap
+        noise_rows = 1
+        if noise is not None:
+            noise = noise.to(dev, torch.float32).contiguous()
+            noise_rows = 1 if noise.dim() == 2 else noise.size(1)
+            assert noise.size(-1) == m.vocab_size
+        S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev)
+        S.reset()
+        sp = L.SampleParams(S.V, m.EOS, int(top_k) if top_k is not None else 0, 1, S.ymax, float(top_p),
+                            float(temperature), float(repetition_penalty), 0x5EED5EED, noise_rows)
+        pe = m.ar_audio_position.pe(max(4000, Pmax + n_max + 1), dev, torch.float32).contiguous()
+        from .. import hip_graphs_safe
+
+        use_graph = os.environ.get("EVT_DECODE_GRAPH", "1") != "0" and hip_graphs_safe()
+        gkey = (bytes(sp), None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W))
+        if use_graph and S.graph_key != gkey:
+            # every slot is idle here: the warm-up and the capture move no counter and write no cache line, so there is
+            # no state to restore (the activations they leave are overwritten by each admission)
+            side = L.role_stream(dev, "decode_warm", ring=1)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                S.step_launches(W, sp, noise, pe)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="relaxed"):
+                S.step_launches(W, sp, noise, pe)
+            S.graph, S.graph_key, S._keep = g, gkey, (sp, noise, pe, W)
+        return S, W, sp, pe, noise, use_graph
+
+    @torch.no_grad()
+    def _admit(self, S, W, sp, pe, noise, batch, seeds):
+        """batch: [(slot, (r, x, bert, prompt, limit))].  The prompt pass of _decode for these requests only (texts padded
+        to Xmax, prompts to the longest of them), their keys/values into their slots' cache slabs, their row state, then
+        step 0 for those rows: logits of the last prompt position and a masked sample."""
+        m = self.model
+        dev, cd = S.device, S.dtype
+        dense = self.dense(cd, dev)
+        Xmax, k = S.Xmax, len(batch)
+        y_lens = [int(q[3].numel()) for _s, q in batch]
+        x_lens = [int(q[1].numel()) for _s, q in batch]
+        Pk = max(y_lens)
+        rows, prs = [], []
+        for _slot, (_r, x, bert, prompt, _lim) in batch:
+            x, bert = x.to(dev), bert.to(dev)
+            xe = m.ar_text_embedding(x.unsqueeze(0))
+            xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
+            xe = m.ar_text_position(xe).squeeze(0)
+            rows.append(F.pad(xe, (0, 0, 0, Xmax - xe.size(0))))
+            prs.append(F.pad(prompt.to(dev).long(), (0, Pk - prompt.numel())))
+        pr = torch.stack(prs, dim=0)
+        xy = torch.cat([torch.stack(rows, dim=0), m.ar_audio_position(m.ar_audio_embedding(pr))], dim=1).to(cd).contiguous()
+        src_len = Xmax + Pk
+        xl = torch.tensor(x_lens, dtype=torch.int32, device=dev)
+        yl = torch.tensor(y_lens, dtype=torch.int32, device=dev)
+        slots_t = torch.tensor([s for s, _q in batch], dtype=torch.long, device=dev)
+        for i, lyr in enumerate(m.h.layers):
+            w = W.layers[i]
+            qkv = dense(xy, lyr.self_attn.in_proj_weight)
+            S.kc[i, slots_t, :src_len] = qkv[..., S.E:2 * S.E]
+            S.vc[i, slots_t, :src_len] = qkv[..., 2 * S.E:]
+            o = PrefixLMAttentionFn.apply(qkv, xl, yl, Xmax, S.H, 0.0, 0)
+            sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
+            xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
+            ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
+            xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
+        # ---- row state ----
+        ncol = 0 if noise is None or noise.dim() == 2 else None
+        rs = [[Xmax + yn, 0, yn, yn, q[4], ROW_RUNNING, q[0] if ncol is None else 0, 0] for yn, (_s, q) in zip(y_lens, batch)]
+        S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
+        S.stop[slots_t] = -1
+        S.row_seed[slots_t] = torch.tensor([list(seeds(q[0])) for _s, q in batch], dtype=torch.int32).to(dev)
+        S.x_lens[slots_t] = xl
+        S.y[slots_t] = 0
+        S.y[slots_t, :Pk] = pr
+        S.mask.zero_()
+        S.mask[slots_t] = 1
+        # ---- step 0 of the admitted rows (the other rows' xb / logits are dead between two steps) ----
+        S.xb[slots_t] = xy[torch.arange(k, device=dev), Xmax + yl.long() - 1].float()
+        S._gemv(W.wpred, None, S.xb, None, None, None, 0.0, None, S.logits)
+        S._sample_embed(W, sp, noise, pe, 0, S.mask)
+
+    def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll):
+        G, draws = self.MAX_ROWS, []
+
+        def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
+            g = r // G
+            while len(draws) <= g:
+                draws.append(int(seed + G * len(draws) if seed is not None
+                                 else torch.randint(0, 2 ** 31 - 1, (1,)).item()) & 0x7FFFFFFF)
+            return draws[g], r % G
+
+        stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_s=[], events=[])
+        free, running, S, exhausted = list(range(slots)), {}, None, False
+        while True:
+            batch = []
+            while free and not exhausted:
+                try:
+                    q = next(it)
+                except StopIteration:
+                    exhausted = True
+                    break
+                self._fits(q, cap)
+                batch.append((free.pop(0), q))
+            if batch:
+                dev = batch[0][1][1].device
+                if S is None:
+                    S, W, sp, pe, noise, use_graph = self._stream_open(cap, slots, dev, top_k, top_p, temperature,
+                                                                      repetition_penalty, noise)
+                cuda = torch.device(dev).type == "cuda"
+                if cuda:
+                    torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                self._admit(S, W, sp, pe, noise, batch, seeds)
+                if cuda:
+                    torch.cuda.synchronize(dev)
+                stats["prefill_s"].append(time.perf_counter() - t0)
+                stats["admissions"] += 1
+                stats["admitted"].append(len(batch))
+                for slot, q in batch:
+                    running[slot] = [q[0], int(q[3].numel()), q[4] - 1]     # request, prompt length, replays left at most
+                    stats["events"].append(("admit", stats["steps"], q[0], slot))
+            if not running:
+                return
+            n = min(poll, max(v[2] for v in running.values()))
+            for _ in range(n):
+                if use_graph:
+                    S.graph.replay()
+                else:
+                    with torch.no_grad():
+                        S.step_launches(W, sp, noise, pe)
+            stats["steps"] += n
+            st = S.state.tolist()                    # the only device->host read of the loop: status and stop of all rows
+            done = []
+            for slot in sorted(running):
+                r, ylen, left = running[slot]
+                running[slot][2] = max(0, left - n)
+                status = st[slot * ROW_WORDS + ROW_STATUS]
+                if status in (ROW_STOP_EOS, ROW_STOP_LIMIT):
+                    last = st[S.B * ROW_WORDS + slot]
+                    done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last))
+            if n == 0 and not done:
+                raise L.EvtError("stream session: a row is past its step limit but not stopped")
+            for slot, r, y, idx in done:
+                del running[slot]
+                free.append(slot)
+                stats["events"].append(("finish", stats["steps"], r, slot))
+            free.sort()
+            for slot, r, y, idx in done:
+                yield r, y, idx
+
+    def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
+                                       early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,
+                                       poll=8, **kwargs):
+        """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
+        the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
+        of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths."""
+        if prompts is None:
+            return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
+                                                  early_stop_num=early_stop_num, temperature=temperature, noise=noise,
+                                                  seed=seed, poll=poll)
+        reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(len(x))]
+        ys, idxs = [None] * len(reqs), [None] * len(reqs)
+        for r, y, idx in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), top_k=top_k, top_p=top_p,
+                                            temperature=temperature, repetition_penalty=repetition_penalty,
+                                            early_stop_num=early_stop_num, noise=noise, seed=seed, poll=poll):
+            ys[r], idxs[r] = y, idx
         return ys, idxs

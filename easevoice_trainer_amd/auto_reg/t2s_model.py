@@ -267,3 +267,9 @@ class Text2SemanticDecoder(nn.Module):
 
     def infer_panel_naive_batched(self, x, x_lens, prompts, bert_feature, **kwargs):
         return self._infer().infer_panel_naive_batched(x, x_lens, prompts, bert_feature, **kwargs)
+
+    def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, **kwargs):
+        return self._infer().infer_panel_batch_infer_refill(x, x_lens, prompts, bert_feature, **kwargs)
+
+    def decode_stream(self, requests, **kwargs):
+        return self._infer().decode_stream(requests, **kwargs)

@@ -16,55 +16,11 @@
 //   dec_attn   one block per (batch, head): appends the new key/value to the cache, softmax(q.K/sqrt(d)).V over it.
 //   dec_sample one block per batch row, 1024 threads, whole vocabulary (1025) in LDS, bitonic sort for the nucleus /
 //              top-k pivots.
-#include "evt_common.h"
-#include "../../include/evt.h"
+#include "s1_decode_common.h"
 
 namespace {
 
 constexpr int kMaxB = 4;
-
-__device__ __forceinline__ float block_sum(float v, float* red, int nwaves) {
-  v = wave_reduce_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int i = 0; i < nwaves; ++i) s += red[i];
-  return s;
-}
-
-__device__ __forceinline__ float block_max(float v, float* red, int nwaves) {
-  v = wave_reduce_max(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float s = -INFINITY;
-  for (int i = 0; i < nwaves; ++i) s = fmaxf(s, red[i]);
-  return s;
-}
-
-// (value, index) argmax with the FIRST index among equal values (torch.argmax on CPU); all threads get the result
-__device__ __forceinline__ int block_argmax(float v, int i, float* redv, int* redi, int nwaves) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { redv[w] = v; redi[w] = i; }
-  __syncthreads();
-  float bv = redv[0];
-  int bi = redi[0];
-  for (int k = 1; k < nwaves; ++k)
-    if (redv[k] > bv || (redv[k] == bv && redi[k] < bi)) { bv = redv[k]; bi = redi[k]; }
-  return bi;
-}
-
-template <typename T> struct WVec { static constexpr int V = 16 / sizeof(T); };
 
 // ---- y[b][n] = act(bias[n] + sum_k W[n][k] * x[b][k]),  x = a  or  LayerNorm(a + r) --------------------------------
 // A launch is a dependent chain of memory latencies, not a bandwidth problem (a workgroup touches 8-16 KB of weights), so
@@ -165,123 +121,6 @@ __global__ __launch_bounds__(256) void dec_gemv(const T* __restrict__ W, const f
         y[(long)b * N + n] = o;
       }
     }
-}
-
-// ---- append (k, v) of the new token to the cache, attend over all cached positions -------------------------------
-// Scores: one key per thread (D elements = D/V 16-byte loads, all in flight).  P.V: a thread owns one 16-byte chunk of
-// the value rows of every G-th key (G = 256 / chunks-per-row), so the cache is read with 16-byte loads only; the G
-// partial rows are summed through LDS.  The first key row and the first PF value chunks of a thread depend on nothing
-// computed in the launch and are requested before anything else (Prefetch), the rest follows the softmax.
-template <typename T, int D> struct AttnShape {
-  static constexpr int V = WVec<T>::V;
-  static constexpr int C = D / V;        // 16-byte chunks per row
-  static constexpr int G = 256 / C;      // key groups in the P.V phase
-  static constexpr int PF = 8;
-};
-
-template <typename T, int D> struct Prefetch {
-  uint4 u0[AttnShape<T, D>::C], vpre[AttnShape<T, D>::PF];
-  __device__ __forceinline__ void issue(const T* kc, const T* vc, int b, int h, int E, int Lmax, int L, int pos) {
-    using S = AttnShape<T, D>;
-    const int tid = threadIdx.x, g = tid / S::C, c = tid % S::C;
-    if (tid < L && tid != pos) {
-      const T* row = kc + ((long)b * Lmax + tid) * E + h * D;
-#pragma unroll
-      for (int cc = 0; cc < S::C; ++cc) u0[cc] = *reinterpret_cast<const uint4*>(row + cc * S::V);
-    }
-#pragma unroll
-    for (int i = 0; i < S::PF; ++i) {
-      const int j = g + i * S::G;
-      if (j < L && j != pos) vpre[i] = *reinterpret_cast<const uint4*>(vc + ((long)b * Lmax + j) * E + h * D + c * S::V);
-    }
-  }
-};
-
-// qs (scaled query), kn / vn (new key / value, already rounded to the cache dtype) are in LDS and published
-template <typename T, int D>
-__device__ __forceinline__ void attn_tail(const Prefetch<T, D>& pf, const float* qs, const float* kn, const float* vn,
-                                          float* sc, float* red, float (*part)[D + 1], const T* kc, const T* vc,
-                                          float* __restrict__ out, int b, int h, int E, int Lmax, int L, int pos,
-                                          int mlo, int mhi) {
-  // keys mlo <= j < mhi are padding of a shorter text in a batch (infer_panel_batch_infer's padding mask): skipped
-  using S = AttnShape<T, D>;
-  constexpr int V = S::V, C = S::C, G = S::G, PF = S::PF;
-  const int tid = threadIdx.x, g = tid / C, c = tid % C;
-  float mx = -INFINITY;
-  for (int j = tid; j < L; j += 256) {
-    float s = 0.f;
-    if (j >= mlo && j < mhi) {
-      s = -INFINITY;
-    } else if (j == pos) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) s += qs[d] * kn[d];
-    } else {
-      uint4 u[C];
-      if (j == tid) {
-#pragma unroll
-        for (int cc = 0; cc < C; ++cc) u[cc] = pf.u0[cc];
-      } else {
-        const T* row = kc + ((long)b * Lmax + j) * E + h * D;
-#pragma unroll
-        for (int cc = 0; cc < C; ++cc) u[cc] = *reinterpret_cast<const uint4*>(row + cc * V);
-      }
-#pragma unroll
-      for (int cc = 0; cc < C; ++cc) {
-        const T* pu = reinterpret_cast<const T*>(&u[cc]);
-#pragma unroll
-        for (int e = 0; e < V; ++e) s += qs[cc * V + e] * to_f<T>(pu[e]);
-      }
-    }
-    sc[j] = s;
-    mx = fmaxf(mx, s);
-  }
-  mx = block_max(mx, red, 4);
-  float sum = 0.f;
-  for (int j = tid; j < L; j += 256) {
-    const float e = sc[j] == -INFINITY ? 0.f : expf(sc[j] - mx);
-    sc[j] = e;
-    sum += e;
-  }
-  sum = block_sum(sum, red, 4);      // its barriers also publish sc[]
-  float acc[V];
-#pragma unroll
-  for (int e = 0; e < V; ++e) acc[e] = 0.f;
-#pragma unroll
-  for (int i = 0; i < PF; ++i) {
-    const int j = g + i * G;
-    if (j < L) {
-      const float pj = sc[j];
-      if (j == pos) {
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += pj * vn[c * V + e];
-      } else {
-        const T* pu = reinterpret_cast<const T*>(&pf.vpre[i]);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += pj * to_f<T>(pu[e]);
-      }
-    }
-  }
-  for (int j = g + PF * G; j < L; j += G) {
-    const float pj = sc[j];
-    if (j == pos) {
-#pragma unroll
-      for (int e = 0; e < V; ++e) acc[e] += pj * vn[c * V + e];
-    } else {
-      const uint4 u = *reinterpret_cast<const uint4*>(vc + ((long)b * Lmax + j) * E + h * D + c * V);
-      const T* pu = reinterpret_cast<const T*>(&u);
-#pragma unroll
-      for (int e = 0; e < V; ++e) acc[e] += pj * to_f<T>(pu[e]);
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < V; ++e) part[g][c * V + e] = acc[e];
-  __syncthreads();
-  if (tid < D) {
-    float o = 0.f;
-#pragma unroll 8
-    for (int i = 0; i < G; ++i) o += part[i][tid];
-    out[(long)b * E + h * D + tid] = o / sum;
-  }
 }
 
 template <typename T, int D>
@@ -413,17 +252,6 @@ __global__ __launch_bounds__(256) void dec_qkv_attn(const T* __restrict__ W, con
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned mix32s(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-
-__device__ __forceinline__ bool before(float av, int ai, float bv, int bi) {   // descending value, ascending index
-  return av > bv || (av == bv && ai < bi);
-}
-
-constexpr int kSortN = 2048;
-
 struct EmbedArgs {          // optional tail of dec_sample: x_next and the counter update of the step (B == 1 only)
   const float* emb; const float* pe; const float* alpha; float* x; float x_scale; int E, npos, dpos;
 };
@@ -431,128 +259,16 @@ struct EmbedArgs {          // optional tail of dec_sample: x_next and the count
 __global__ __launch_bounds__(1024) void dec_sample(evt_sample_params p, const float* __restrict__ logits, long* y,
                                                    int* ctr, const float* __restrict__ noise, int* stop_idx,
                                                    float* probs_out, EmbedArgs ea, const int* __restrict__ row_seed) {
-  __shared__ float sv[kSortN];
-  __shared__ int si[kSortN];
-  __shared__ float cur[kSortN];
-  __shared__ unsigned char flag[kSortN];
-  __shared__ float redv[16];
-  __shared__ int redi[16];
-  __shared__ float wsum[16];
   const int tid = threadIdx.x, b = blockIdx.x, V = p.V;
   const int idx = ctr[EVT_DEC_IDX], ycount = ctr[EVT_DEC_YCOUNT];
   // built-in noise of this row: (seed, lane) from the row-seed table, else (ctr[SEED], b)
   const unsigned nseed = row_seed ? (unsigned)row_seed[2 * b] : (unsigned)ctr[EVT_DEC_SEED];
   const unsigned nlane = row_seed ? (unsigned)row_seed[2 * b + 1] : (unsigned)b;
-  const int Ve = idx < p.no_eos_steps ? V - 1 : V;     // "at least 10 tokens otherwise not stop", t2s_model.py:833
-  const float* lg = logits + (long)b * V;
   long* yb = y + (long)b * p.ymax;
-  for (int v = tid; v < kSortN; v += 1024) flag[v] = 0;
-  __syncthreads();
-  if (p.repetition_penalty != 1.0f)
-    for (int j = tid; j < ycount; j += 1024) {
-      const long t = yb[j];
-      if (t >= 0 && t < Ve) flag[t] = 1;
-    }
-  __syncthreads();
-  float bvv = -INFINITY;
-  int bii = 0x7fffffff;
-  for (int v = tid; v < kSortN; v += 1024) {
-    float x = -INFINITY;
-    if (v < Ve) {
-      x = lg[v];
-      if (flag[v]) x = x < 0.f ? x * p.repetition_penalty : x / p.repetition_penalty;
-      if (x > bvv || (x == bvv && v < bii)) { bvv = x; bii = v; }
-    }
-    cur[v] = x;
-    sv[v] = x;
-    si[v] = v;
-  }
-  // argmax of the (penalised, in place in the reference) logits: the EOS test of t2s_model.py:846
-  const int amax = block_argmax(bvv, bii, redv, redi, 16);
-  // bitonic sort, descending
-  for (int k = 2; k <= kSortN; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      const int i = 2 * j * (tid / j) + (tid % j), l = i + j;
-      const bool up = (i & k) == 0;
-      const float av = sv[i], bv = sv[l];
-      const int ai = si[i], bi = si[l];
-      const bool in_order = before(av, ai, bv, bi);
-      if (in_order != up) { sv[i] = bv; sv[l] = av; si[i] = bi; si[l] = ai; }
-    }
-  __syncthreads();
-  if (p.top_p < 1.0f) {
-    // cumulative softmax over the sorted logits; entries past the nucleus are removed, the first is always kept
-    const float m = sv[0];
-    const float e0 = expf(sv[2 * tid] - m), e1 = expf(sv[2 * tid + 1] - m);
-    float run = e0 + e1;
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float t = __shfl_up(run, o, 64);
-      if (lane >= o) run += t;
-    }
-    if (lane == 63) wsum[w] = run;
-    __syncthreads();
-    float offs = 0.f, total = 0.f;
-    for (int i = 0; i < 16; ++i) {
-      if (i < w) offs += wsum[i];
-      total += wsum[i];
-    }
-    const float c1 = (offs + run) / total, c0 = (offs + run - e1) / total;
-    if (2 * tid > 0 && c0 > p.top_p && si[2 * tid] < Ve) cur[si[2 * tid]] = -INFINITY;
-    if (c1 > p.top_p && si[2 * tid + 1] < Ve) cur[si[2 * tid + 1]] = -INFINITY;
-    __syncthreads();
-  }
-  const float tdiv = fmaxf(p.temperature, 1e-5f);
-  float pivot = -INFINITY;
-  if (p.top_k > 0) {
-    const int kk = p.top_k < Ve ? p.top_k : Ve;
-    pivot = cur[si[kk - 1]] / tdiv;
-  }
-  float x0[2], mx = -INFINITY;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int v = tid + u * 1024;
-    float x = -INFINITY;
-    if (v < Ve) {
-      x = cur[v] / tdiv;
-      if (x < pivot) x = -INFINITY;
-    }
-    x0[u] = x;
-    mx = fmaxf(mx, x);
-  }
-  mx = block_max(mx, redv, 16);
-  float e[2], sum = 0.f;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    e[u] = x0[u] == -INFINITY ? 0.f : expf(x0[u] - mx);
-    sum += e[u];
-  }
-  sum = block_sum(sum, redv, 16);
-  float best = -INFINITY;
-  int besti = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int v = tid + u * 1024;
-    if (v < Ve) {
-      const float pr = e[u] / sum;
-      if (probs_out) probs_out[(long)b * V + v] = pr;
-      float q;
-      if (noise) {
-        q = noise[((long)idx * p.noise_rows + (p.noise_rows > 1 ? b : 0)) * V + v];
-      } else {
-        const unsigned hsh =
-            mix32s(mix32s((p.seed ^ nseed) + (unsigned)idx * 0x9E3779B9u) ^ (nlane << 16) ^ (unsigned)v);
-        q = -logf(((float)(hsh >> 8) + 0.5f) * (1.0f / 16777216.0f));
-      }
-      const float s = pr / q;
-      if (s > best || (s == best && v < besti)) { best = s; besti = v; }
-    } else if (probs_out && v < V) {
-      probs_out[(long)b * V + v] = 0.f;
-    }
-  }
-  const int tok = block_argmax(best, besti, redv, redi, 16);
+  int amax;
+  const int tok = sample_row(p, logits + (long)b * V, yb, idx, ycount, nseed, nlane,
+                             noise ? noise + ((long)idx * p.noise_rows + (p.noise_rows > 1 ? b : 0)) * V : nullptr,
+                             probs_out ? probs_out + (long)b * V : nullptr, &amax);
   if (tid == 0) {
     if (ycount < p.ymax) yb[ycount] = tok;
     if ((amax == p.eos || tok == p.eos) && stop_idx[b] < 0) stop_idx[b] = idx;

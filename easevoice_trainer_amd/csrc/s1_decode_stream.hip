@@ -1,0 +1,130 @@
+// s1 decoding with PER-ROW counters: the step of a continuously batched session (auto_reg/t2s_infer.py StreamSession), in
+// which a finished row's slot is refilled with the next waiting text while the other rows keep decoding, for gfx950.
+//
+// The sessions of s1_decode.hip keep one set of counters ctr[POS|IDX|YCOUNT|YLEN] for all rows, so every row has the
+// same prompt length and the same step index, and the counters may only move in a launch of their own after every row's
+// workgroup has read them.  Here every row b owns rstate[b][8] (EVT_ROW_*): cache position, step index, token count,
+// prompt length, step limit, status and the column of an injected noise table.  A row is touched only by its own
+// workgroups, so
+//   dec_attn_rows          is dec_attn with pos = rstate[b][POS]; a row that is not running returns at once;
+//   dec_sample_embed_rows  samples, appends, tests EOS / the step limit, embeds the next input and moves the row's
+//                          counters in ONE launch for all rows (three launches in a session with shared counters).
+// A row that stops (EOS, or its limit) is marked in the same launch and is skipped from then on: however late the host
+// reads the status, a stopped row never advances its position or writes past its buffers.
+// The counters are written with ordinary stores by thread 0 of the row's workgroup after a barrier.
+#include "s1_decode_common.h"
+
+namespace {
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void dec_attn_rows(const float* __restrict__ qkv, T* kc, T* vc,
+                                                     const int* __restrict__ rstate, float* __restrict__ out, int H,
+                                                     int Lmax, const int* __restrict__ x_lens, int x_len) {
+  extern __shared__ float sc[];   // [Lmax] scores -> probabilities
+  __shared__ float qs[D], kn[D], vn[D], red[4], part[AttnShape<T, D>::G][D + 1];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / H, h = blockIdx.x % H, E = H * D;
+  const int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;   // idle / stopped: no cache write, out untouched
+  const int pos = rs[EVT_ROW_POS];
+  if (pos < 0 || pos >= Lmax) return;   // cache full: the host bounds the number of steps, this only guards memory
+  const int L = pos + 1;
+  Prefetch<T, D> pf;
+  pf.issue(kc, vc, b, h, E, Lmax, L, pos);
+  if (tid < D) {
+    const float* base = qkv + (long)b * 3 * E + h * D + tid;
+    qs[tid] = base[0] * rsqrtf((float)D);
+    const T kq = from_f<T>(base[E]), vq = from_f<T>(base[2 * E]);
+    kn[tid] = to_f<T>(kq);
+    vn[tid] = to_f<T>(vq);
+    kc[((long)b * Lmax + pos) * E + h * D + tid] = kq;
+    vc[((long)b * Lmax + pos) * E + h * D + tid] = vq;
+  }
+  __syncthreads();
+  attn_tail<T, D>(pf, qs, kn, vn, sc, red, part, kc, vc, out, b, h, E, Lmax, L, pos, x_lens ? x_lens[b] : 0,
+                  x_lens ? x_len : 0);
+}
+
+struct RowEmbed { const float* emb; const float* pe; const float* alpha; float* x; float x_scale; int E, npos, dpos; };
+
+__global__ __launch_bounds__(1024) void dec_sample_embed_rows(evt_sample_params p, const float* __restrict__ logits,
+                                                              long* y, int* rstate, const float* __restrict__ noise,
+                                                              int* stop_idx, float* probs_out,
+                                                              const int* __restrict__ row_seed,
+                                                              const int* __restrict__ row_mask, RowEmbed ea) {
+  const int tid = threadIdx.x, b = blockIdx.x, V = p.V;
+  if (row_mask && !row_mask[b]) return;
+  int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
+  const int idx = rs[EVT_ROW_IDX], ycount = rs[EVT_ROW_YCOUNT], ylen = rs[EVT_ROW_YLEN], limit = rs[EVT_ROW_LIMIT];
+  int col = rs[EVT_ROW_NOISE];
+  if (col < 0 || col >= p.noise_rows) col = 0;
+  long* yb = y + (long)b * p.ymax;
+  int amax;
+  const int tok = sample_row(p, logits + (long)b * V, yb, idx, ycount, (unsigned)row_seed[2 * b],
+                             (unsigned)row_seed[2 * b + 1],
+                             noise ? noise + ((long)idx * p.noise_rows + col) * V : nullptr,
+                             probs_out ? probs_out + (long)b * V : nullptr, &amax);
+  // x_next = emb[token] * x_scale + alpha * pe[y_len + idx]  (t2s_model.py:860-861)
+  int ppos = ylen + idx;
+  if (ppos >= ea.npos) ppos = ea.npos - 1;
+  const float al = ea.alpha[0];
+  // the rounding is spelled out (one product rounded, then one fused multiply-add) instead of left to the compiler's
+  // contraction, which picks different forms for different loop shapes: this is what dec_embed computes at E = 512
+  for (int c = tid; c < ea.E; c += 1024)
+    ea.x[(long)b * ea.E + c] =
+        __fmaf_rn(ea.emb[(long)tok * ea.E + c], ea.x_scale, __fmul_rn(al, ea.pe[(long)ppos * ea.E + c]));
+  __syncthreads();       // every read of the row's state above is done; only this workgroup touches it
+  if (tid == 0) {
+    if (ycount < p.ymax) yb[ycount] = tok;
+    if (amax == p.eos || tok == p.eos) {
+      stop_idx[b] = idx;
+      rs[EVT_ROW_STATUS] = EVT_ROW_STOP_EOS;
+    } else if (idx + 1 >= limit || ycount + 1 >= p.ymax) {
+      stop_idx[b] = idx;
+      rs[EVT_ROW_STATUS] = EVT_ROW_STOP_LIMIT;
+    } else {
+      rs[EVT_ROW_POS] += ea.dpos;
+      rs[EVT_ROW_IDX] = idx + 1;
+      rs[EVT_ROW_YCOUNT] = ycount + 1;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int evt_dec_attn_rows(int32_t cdtype, const float* qkv, void* kcache, void* vcache, const int32_t* rstate, float* out,
+                      int32_t B, int32_t H, int32_t D, int32_t Lmax, const int32_t* x_lens, int32_t x_len, void* stream) {
+  if (!qkv || !kcache || !vcache || !rstate || !out || B <= 0 || H <= 0 || Lmax <= 0) return EVT_EINVAL;
+  if (D != 32 || (size_t)Lmax * 4 > 60 * 1024) return EVT_ENOTSUP;
+  const size_t shm = (size_t)Lmax * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (cdtype == EVT_DT_HALF)
+    hipLaunchKernelGGL((dec_attn_rows<h16_t, 32>), dim3(B * H), dim3(256), shm, st, qkv, (h16_t*)kcache, (h16_t*)vcache,
+                       (const int*)rstate, out, H, Lmax, (const int*)x_lens, x_len);
+  else if (cdtype == EVT_DT_F32)
+    hipLaunchKernelGGL((dec_attn_rows<float, 32>), dim3(B * H), dim3(256), shm, st, qkv, (float*)kcache, (float*)vcache,
+                       (const int*)rstate, out, H, Lmax, (const int*)x_lens, x_len);
+  else return EVT_EINVAL;
+  return evt_check_launch();
+}
+
+int evt_dec_sample_embed_rows(const evt_sample_params* p, const float* logits, int64_t* y, int32_t* rstate,
+                              const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed,
+                              const int32_t* row_mask, const float* emb, const float* pe, const float* alpha,
+                              float x_scale, float* x, int32_t B, int32_t E, int32_t npos, int32_t dpos, void* stream) {
+  if (!p || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 || E <= 0 ||
+      npos <= 0 || dpos < 0)
+    return EVT_EINVAL;
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
+  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  hipLaunchKernelGGL(dec_sample_embed_rows, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y,
+                     (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed, (const int*)row_mask, ea);
+  return evt_check_launch();
+}
+
+}  // extern "C"

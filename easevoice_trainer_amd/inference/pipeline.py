@@ -40,3 +40,31 @@ def synthesize_fragments(t2s, voice, batch_phones, all_phoneme_ids, all_bert_fea
         sem = p[-i:].unsqueeze(0).unsqueeze(0)
         out.append(voice.model.decode(sem, ph.to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :])
     return out
+
+
+def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
+                      top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
+                      decode_kwargs=None, sample_kwargs=None):
+    """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
+    mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
+    fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
+    free row); each is turned into audio on its own by the s2 decoder as soon as its tokens are there, at any
+    speed_factor, while the other rows' tokens wait in the session.  prompt_semantic: [1, P] for all fragments, or a
+    list with one token vector per fragment (fragments of several reference voices in one session)."""
+    model, dev = t2s.model, t2s.device
+    n = len(all_phoneme_ids)
+    if prompt_semantic is None:
+        raise ValueError("synthesize_stream needs the prompt's semantic tokens")
+    prompts = ([p.reshape(-1).to(dev) for p in prompt_semantic] if isinstance(prompt_semantic, (list, tuple))
+               else [prompt_semantic.reshape(-1).to(dev)] * n)
+    reqs = [(p.to(dev), b.to(dev), pr) for p, b, pr in zip(all_phoneme_ids, all_bert_features, prompts)]
+    refer = [r.to(dev) for r in refer_specs]
+    kw = decode_kwargs or {}
+    stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
+                                 early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
+                                 **(sample_kwargs or {}))
+    for r, y, idx in stream:
+        with torch.no_grad():
+            sem = y[-idx:].unsqueeze(0).unsqueeze(0)
+            wav = voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]
+        yield r, wav

@@ -729,6 +729,41 @@ int evt_dec_embed(const float* emb, const float* pe, const float* alpha, float x
 /* end of a step: ctr[IDX] += 1, ctr[YCOUNT] += 1, ctr[POS] += dpos (1 after a decode step, 0 after the prompt pass) */
 int evt_dec_advance(int32_t* ctr, int32_t dpos, void* stream);
 
+/* Per-row decode state of a continuously batched session (csrc/s1_decode_stream.hip): rstate is a device int32
+ * [B][EVT_ROW_WORDS].  With the counters per row, rows of one session may have different prompt lengths, start at
+ * different times and stop on their own, and a finished row's slot can be refilled between two steps. */
+#define EVT_ROW_WORDS 8
+#define EVT_ROW_POS 0      /* key/value positions of this row already in its cache slab */
+#define EVT_ROW_IDX 1      /* the row's own decode step index */
+#define EVT_ROW_YCOUNT 2   /* tokens in the row's y buffer (prompt + generated) */
+#define EVT_ROW_YLEN 3     /* the row's prompt length */
+#define EVT_ROW_LIMIT 4    /* the row stops after the step IDX == LIMIT - 1 at the latest */
+#define EVT_ROW_STATUS 5   /* EVT_ROW_IDLE | RUNNING | STOP_EOS | STOP_LIMIT */
+#define EVT_ROW_NOISE 6    /* column of an injected noise table [steps][noise_rows][V] this row reads */
+#define EVT_ROW_SPARE 7
+#define EVT_ROW_IDLE 0
+#define EVT_ROW_RUNNING 1
+#define EVT_ROW_STOP_EOS 2
+#define EVT_ROW_STOP_LIMIT 3
+/* evt_dec_attn with the cache length of row b taken from rstate[b][POS]: appends the new key/value at that position of
+ * the row's slab and attends over positions 0..POS except the padding x_lens[b] <= j < x_len.  A row whose status is not
+ * RUNNING is skipped: nothing is appended and out[b] is left as it is.  Arithmetic and summation order are those of
+ * evt_dec_attn, so a row equals a one-row evt_dec_attn call at its position bit for bit. */
+int evt_dec_attn_rows(int32_t cdtype, const float* qkv, void* kcache, void* vcache, const int32_t* rstate, float* out,
+                      int32_t B, int32_t H, int32_t D, int32_t Lmax, const int32_t* x_lens, int32_t x_len, void* stream);
+/* One launch for the end of a step of all B rows: the sampling of evt_dec_sample_rows with IDX / YCOUNT / YLEN of the
+ * row (no_eos_steps against the row's own IDX; built-in noise keyed by row_seed[b] and the row's IDX; an injected table
+ * read at [IDX][rstate[b][NOISE]]), the append to y[b], x[b] = emb[token] * x_scale + alpha[0] * pe[YLEN + IDX], and
+ * the row's counter update.  On EOS (arg-max of the penalised logits or the token), or when IDX + 1 reaches LIMIT, the
+ * row's status becomes STOP_EOS / STOP_LIMIT and stop_idx[b] receives IDX; the counters then stay.  Otherwise
+ * POS += dpos (1 in a decode step, 0 after the prompt pass), IDX += 1, YCOUNT += 1.  Rows that are not RUNNING are
+ * skipped, and so are rows with row_mask[b] == 0 when row_mask (int32 [B], may be NULL) is given: step 0 of freshly
+ * admitted rows.  probs_out may be NULL. */
+int evt_dec_sample_embed_rows(const evt_sample_params* p, const float* logits, int64_t* y, int32_t* rstate,
+                              const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed,
+                              const int32_t* row_mask, const float* emb, const float* pe, const float* alpha,
+                              float x_scale, float* x, int32_t B, int32_t E, int32_t npos, int32_t dpos, void* stream);
+
 /* ScaledAdam (src/easevoice/soundstorm/auto_reg/modules/optim.py:206-251,300-390,448-622) over a flat fp32 arena.
  * The reference stacks same-shaped tensors only to batch its torch ops; the arithmetic is per tensor, which is what
  * these two launches implement for ALL tensors at once:

@@ -4,7 +4,15 @@ replay vs eager launches, with the algorithmic HBM bytes per token (every block 
 the same process: batch{R}_graph (one call: one session of up to 32 rows) and batch{R}_groups4_graph (the same texts in
 consecutive calls of <= 4 rows, one session each); algorithmic bytes per step = every matrix once + R caches.
 
+--stream times continuous batching: N texts (--stream-n, default 96) whose lives are spread over 64..512 steps in seeded
+random order (EOS forced at each text's step through the noise table, so both paths stop every text at the same step) go
+through infer_panel_batch_infer (groups of 32, each waiting for its slowest row) and then through the refilled session
+(infer_panel_batch_infer_refill / decode_stream, 32 slots) in the same process; one JSON line with steps, useful tokens,
+tokens/s and us per step of both, the stream's admissions and prefill time, median and last completion time, the step
+time of both sessions with 32 rows alive for --tokens steps, and the prefill time of 1, 8 and 32 admitted rows.
+
     python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
+    python tools/bench_s1_decode.py --stream [--stream-n 96]
 """
 import argparse
 import json
@@ -21,6 +29,120 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def run_stream(args, m, dev, x, bert, prompts):
+    """grouped against refilled decoding of the same requests (see the module docstring)"""
+    import random
+
+    N, lo, hi, poll = args.stream_n, 64, 512, 8
+    rnd = random.Random(7)
+    lives = [lo + (hi - lo) * r // max(1, N - 1) for r in range(N)]       # step at which text r meets EOS
+    rnd.shuffle(lives)
+    lens = [max(1, args.x_len - 7 * (r % 12)) for r in range(N)]
+    xs = [x[0][:n].contiguous() for n in lens]
+    berts = [bert[0][:, :n].contiguous() for n in lens]
+    pr = prompts.expand(N, -1).contiguous()
+    g = torch.Generator().manual_seed(5)
+    noise = torch.empty(hi + 2, N, 1025).exponential_(1, generator=g)
+    noise[:, :, 1024] = 1e30                  # EOS never wins ...
+    for r, s in enumerate(lives):
+        noise[s, r, 1024] = 1e-30             # ... except at the text's own step (top_k covers the whole vocabulary)
+    noise = noise.to(dev)
+    kw = dict(top_k=1100, top_p=1, early_stop_num=hi + 8, repetition_penalty=1.35, poll=poll)
+    infer = m._infer()
+
+    def grouped():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys, idxs, done = [], [], []
+        for g0 in range(0, N, 32):            # infer_panel_batch_infer's own grouping, timed per group
+            rows = list(range(g0, min(N, g0 + 32)))
+            y, i = m.infer_panel_batch_infer([xs[r] for r in rows], None, pr[rows], [berts[r] for r in rows],
+                                             noise=noise[:, rows].contiguous(), **kw)
+            torch.cuda.synchronize()
+            ys += y
+            idxs += i
+            done += [time.perf_counter() - t0] * len(rows)
+        return ys, idxs, done, time.perf_counter() - t0
+
+    def refilled():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys, done = [None] * N, [None] * N
+        reqs = [(xs[r], berts[r], pr[r]) for r in range(N)]
+        for r, y, _i in m.decode_stream(reqs, slots=32, noise=noise, **kw):
+            ys[r], done[r] = y, time.perf_counter() - t0
+        torch.cuda.synchronize()
+        return ys, done, time.perf_counter() - t0, dict(infer.stream_stats)
+
+    out = {}
+    gt, st = [], []
+    for rep in range(args.reps + 1):
+        ys_g, idx_g, done_g, t_g = grouped()
+        ys_s, done_s, t_s, stats = refilled()
+        assert [y.numel() for y in ys_g] == [y.numel() for y in ys_s] == [args.prompt + s for s in lives]
+        gt.append((t_g, done_g))
+        st.append((t_s, done_s, stats))
+    useful = sum(lives)
+    # replays of the grouped path: each group steps until the poll after its slowest row's stop
+    steps_g = sum(-(-(max(lives[g0:g0 + 32]) + 1) // poll) * poll for g0 in range(0, N, 32))
+    t_g, done_g = _median(gt[1:])
+    t_s, done_s, stats = sorted(st[1:], key=lambda v: v[0])[len(st[1:]) // 2]
+    pre = sum(stats["prefill_s"])
+    out["grouped"] = dict(seconds=round(t_g, 4), steps=steps_g, useful_tokens=useful, tokens_per_s=round(useful / t_g, 1),
+                          us_per_step=round(1e6 * t_g / steps_g, 1), median_completion_s=round(_median(done_g), 4),
+                          last_completion_s=round(max(done_g), 4))
+    out["stream"] = dict(seconds=round(t_s, 4), steps=stats["steps"], useful_tokens=useful,
+                         tokens_per_s=round(useful / t_s, 1), us_per_step=round(1e6 * (t_s - pre) / stats["steps"], 1),
+                         admissions=stats["admissions"], admitted=stats["admitted"], prefill_ms=round(1e3 * pre, 2),
+                         median_completion_s=round(_median(done_s), 4), last_completion_s=round(max(done_s), 4))
+    out["stream_over_grouped"] = round(t_g / t_s, 3)
+    out["grouped_seconds_all_runs"] = [round(v[0], 4) for v in gt[1:]]
+    out["stream_seconds_all_runs"] = [round(v[0], 4) for v in st[1:]]
+    # ---- step time with 32 rows alive for --tokens steps (the workload of --rows 32) ----
+    T = args.tokens
+    nz = torch.empty(T + 2, 1025).exponential_(1, generator=g)
+    nz[:, 1024] = 1e30
+    nz = nz.to(dev)
+    kw32 = dict(top_k=15, top_p=1, early_stop_num=T, repetition_penalty=1.35, noise=nz)
+    rows = list(range(32))
+    tg, ts = [], []
+    for rep in range(args.reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.infer_panel_batch_infer([xs[r] for r in rows], None, pr[rows], [berts[r] for r in rows], **kw32)
+        torch.cuda.synchronize()
+        tg.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        ys = m.infer_panel_batch_infer_refill([xs[r] for r in rows], None, pr[rows], [berts[r] for r in rows], slots=32,
+                                              **kw32)[0]
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0, sum(infer.stream_stats["prefill_s"]), infer.stream_stats["steps"]))
+        assert all(y.numel() == args.prompt + T for y in ys)
+    out["rows32"] = dict(
+        tokens=T,
+        grouped_us_per_step_all_runs=[round(1e6 * t / (T + 1), 1) for t in tg[1:]],
+        stream_us_per_step_all_runs=[round(1e6 * t / (T + 1), 1) for t, _p, _n in ts[1:]],
+        stream_us_per_replay_all_runs=[round(1e6 * (t - p) / n, 1) for t, p, n in ts[1:]],
+        note="per step: whole call / (tokens + 1), prompt pass included, as batch32_graph; per replay: prefill excluded")
+    # ---- cost of an admission: prompt pass + cache copy + step 0 for k rows ----
+    adm = {}
+    for k in (1, 8, 32):
+        reqs = [(xs[r], berts[r], pr[r], 1) for r in range(k)]
+        ms = []
+        for rep in range(3):
+            list(m.decode_stream(reqs, slots=k, noise=nz, top_k=15, top_p=1, early_stop_num=T))
+            ms.append(1e3 * infer.stream_stats["prefill_s"][0])
+        adm[str(k)] = round(min(ms[1:]), 2)
+    out["admission_prefill_ms"] = adm
+    print(json.dumps(dict(workload=f"s1 decode stream, {N} texts living {lo}..{hi} steps, x_len<={args.x_len}, "
+                                   f"prompt={args.prompt}, {args.dtype}, 32 slots, poll {poll}", **out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=512)
@@ -32,6 +154,9 @@ def main():
                     help="also time infer_panel_batch_infer with this many texts (each <= 64)")
     ap.add_argument("--rows-only", action="store_true",
                     help="time batch{R}_graph alone (no single-sequence lines, no groups of 4): for a kernel trace")
+    ap.add_argument("--stream", action="store_true",
+                    help="time the refilled session against infer_panel_batch_infer on --stream-n texts (nothing else)")
+    ap.add_argument("--stream-n", type=int, default=96)
     args = ap.parse_args()
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
@@ -51,6 +176,10 @@ def main():
     noise = torch.empty(args.tokens + 2, 1025).exponential_(1, generator=g)
     noise[:, 1024] = 1e30
     noise = noise.to(dev)
+    if args.stream:
+        os.environ["EVT_DECODE_GRAPH"] = "1"
+        run_stream(args, m, dev, x, bert, prompts)
+        return
     esz = 2 if dtype == torch.bfloat16 else 4
     E, nl = 512, 24
     w_bytes = (nl * (3 * E * E + E * E + 8 * E * E) + 1025 * E) * esz
