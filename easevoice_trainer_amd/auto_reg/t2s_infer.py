@@ -13,9 +13,12 @@ Same token sequence as the reference for the same sampling noise; a different ex
     sampler keys each row's noise by a row-seed table, so a row draws what it drew in a group of four.
   * continuous batching (StreamSession, decode_stream): the counters live per row (csrc/s1_decode_stream.hip), so rows of
     one session have their own prompt length, step index and limit; a finished row's slot is refilled with the next
-    waiting text between two graph replays and results are handed out as they finish.
+    waiting text between two graph replays and results are handed out as they finish.  The sampling parameters are per
+    row as well (a device table next to the counters), so requests of one session may differ in them, one captured graph
+    serves every parameter set, and a request can be cancelled between two polls (StreamControl).
 The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
 import ctypes as C
+import math
 import os
 import time
 
@@ -143,11 +146,26 @@ ROW_POS, ROW_IDX, ROW_YCOUNT, ROW_YLEN, ROW_LIMIT, ROW_STATUS, ROW_NOISE = range
 ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 
 
+SAMPLE_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty")
+
+
+class StreamControl:
+    """handle of a running decode_stream for the caller that consumes it: cancel(r) withdraws request r.  It only
+    records the index; the stream acts at its next poll, so the caller cancels between two next() calls (one thread)."""
+
+    def __init__(self):
+        self.cancelled = set()
+
+    def cancel(self, r):
+        self.cancelled.add(int(r))
+
+
 class StreamSession:
     """static buffers + the captured step graph of a continuously batched session: B slots, each with its own counters
     rstate[b] (csrc/s1_decode_stream.hip).  Cache slab of a slot: [0, Xmax) the text, padded and masked by x_lens[b];
     [Xmax, Xmax + ylen[b] + steps) the audio.  All per-row state is device memory, so admitting a text into a free slot
-    changes no launch argument and the graph is captured once per (sampling parameters, noise table)."""
+    changes no launch argument; that includes the row's top_k / top_p / temperature / repetition_penalty (row_sample[b]),
+    so the graph is captured once per (vocabulary-level parameters, noise table) and serves every parameter set."""
 
     def __init__(self, model, B, Xmax, Lmax, ymax, dtype, device):
         self.model, self.B, self.Xmax, self.Lmax, self.ymax = model, B, Xmax, Lmax, ymax
@@ -167,6 +185,7 @@ class StreamSession:
         self.stop = self.state[B * ROW_WORDS:]
         self.x_lens = z(B, dt=torch.int32)
         self.row_seed = z(B, 2, dt=torch.int32)
+        self.row_sample = z(B, 4, dt=torch.int32)                 # evt_row_sample [B]: top_k, then the bits of 3 floats
         self.mask = z(B, dt=torch.int32)                          # rows of an admission's step 0
         self.graph, self.graph_key = None, None
 
@@ -188,12 +207,14 @@ class StreamSession:
 
     def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
-        (each row's workgroup owns its counters); `mask` restricts it to the rows of an admission"""
-        L.check(L.lib().evt_dec_sample_embed_rows(
-            C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise), L.ptr(self.stop), None,
+        (each row's workgroup owns its counters); `mask` restricts it to the rows of an admission.  top_k, top_p,
+        temperature and repetition_penalty of a row come from row_sample[b]; `sp` carries the session-wide rest"""
+        L.check(L.lib().evt_dec_sample_embed_rows_p(
+            C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
+            L.ptr(self.stop), None,
             L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
             C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), self.B, self.E, pe.size(0), dpos,
-            L.stream_ptr()), "evt_dec_sample_embed_rows")
+            L.stream_ptr()), "evt_dec_sample_embed_rows_p")
 
     def step_launches(self, W, sp, noise, pe):
         """one token for every running row: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + one
@@ -452,11 +473,33 @@ class T2SInfer:
     def _limit(early_stop_num):
         return MAX_STEPS if early_stop_num == -1 else max(1, min(MAX_STEPS, int(early_stop_num) + 1))
 
+    @staticmethod
+    def _sampling(top_k, top_p, temperature, repetition_penalty, who):
+        """the four sampling values as the table holds them: int(top_k) (None: 0, off), three floats; non-finite values
+        and repetition_penalty <= 0 are refused here, the kernel's launcher cannot see the device table"""
+        try:
+            v = (int(top_k) if top_k is not None else 0, float(top_p), float(temperature), float(repetition_penalty))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise L.EvtError(f"{who}: bad sampling parameter ({e})") from None
+        for name, f in zip(SAMPLE_KEYS[1:], v[1:]):
+            if not math.isfinite(f):
+                raise L.EvtError(f"{who}: {name} = {f} is not finite")
+        if v[3] <= 0.0:
+            raise L.EvtError(f"{who}: repetition_penalty = {v[3]} must be > 0")
+        return v
+
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
-                      early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None):
+                      early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
+                      control=None):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
-        (x, bert, prompt, early_stop_num) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may
-        differ in content and length.  Returns a generator of (request_index, y, idx) in COMPLETION order, y and idx as
+        (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
+        content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
+        repetition_penalty, early_stop_num that replace the session-wide values for this request alone (an unknown key,
+        a non-finite value or repetition_penalty <= 0 raises EvtError naming the request, before anything is launched
+        for it).  control: a StreamControl; control.cancel(r) between two next() calls withdraws request r at the next
+        poll -- a running row is set idle and its slot freed for the admission that follows, a waiting request is
+        skipped without a prompt pass, either is yielded as (r, None, None); a request that finished at that poll is
+        delivered.  Returns a generator of (request_index, y, idx) in COMPLETION order, y and idx as
         infer_panel_batch_infer returns them per text.  Up to `slots` (1..32) texts decode at once in one graph-replayed
         session; every `poll` steps the rows' status is read, finished rows are handed out and their slots refilled
         with the next waiting requests (one prompt pass for all of them).  A list has the capacity (longest text,
@@ -472,18 +515,30 @@ class T2SInfer:
         nsteps = None if noise is None else int(noise.size(0))
         ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
 
+        base = dict(zip(SAMPLE_KEYS, (top_k, top_p, temperature, repetition_penalty)))
+        base_v = self._sampling(top_k, top_p, temperature, repetition_penalty, "decode_stream")
+
         def norm(r, req):
             if len(req) not in (3, 4):
-                raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num])")
+                raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num or dict])")
             x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
-            lim = self._limit(early_stop_num if len(req) == 3 else req[3])
+            opt, samp = req[3] if len(req) == 4 else None, base_v
+            if isinstance(opt, dict):
+                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num"})
+                if unknown:
+                    raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)} and "
+                                     "early_stop_num)")
+                samp = self._sampling(*({**base, **{k: v for k, v in opt.items() if k in SAMPLE_KEYS}}[k]
+                                        for k in SAMPLE_KEYS), f"request {r}")
+                opt = opt.get("early_stop_num")
+            lim = self._limit(early_stop_num if opt is None else opt)
             if nsteps is not None:
                 lim = min(lim, nsteps)      # an injected noise table also bounds the number of steps
             if x.numel() < 1 or prompt.numel() < 1:
                 raise L.EvtError(f"request {r}: empty text or prompt")
             if ncols is not None and r >= ncols:
                 raise L.EvtError(f"request {r}: the noise table has {ncols} columns")
-            return r, x, bert, prompt, lim
+            return r, x, bert, prompt, lim, samp
 
         if isinstance(requests, (list, tuple)):
             reqs = [norm(r, q) for r, q in enumerate(requests)]
@@ -506,11 +561,11 @@ class T2SInfer:
             cap = (int(max_text_len), int(max_prompt_len), n_max)
             it = (norm(r, q) for r, q in enumerate(requests))
         return self._stream(it, cap, int(slots), top_k, top_p, temperature, repetition_penalty, noise, seed,
-                            max(1, int(poll)))
+                            max(1, int(poll)), control)
 
     @staticmethod
     def _fits(q, cap):
-        r, x, _bert, prompt, lim = q
+        r, x, _bert, prompt, lim = q[:5]
         if x.numel() > cap[0] or prompt.numel() > cap[1] or lim > cap[2]:
             raise L.EvtError(f"request {r} (text {x.numel()}, prompt {prompt.numel()}, {lim} steps) does not fit the "
                              f"session's capacity (text {cap[0]}, prompt {cap[1]}, {cap[2]} steps)")
@@ -536,7 +591,11 @@ class T2SInfer:
         from .. import hip_graphs_safe
 
         use_graph = os.environ.get("EVT_DECODE_GRAPH", "1") != "0" and hip_graphs_safe()
-        gkey = (bytes(sp), None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W))
+        # the four per-request values reach the sampler through S.row_sample, not through sp: the graph does not depend
+        # on them
+        gkey = (sp.V, sp.eos, sp.no_eos_steps, sp.ymax, sp.seed, sp.noise_rows,
+                None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W))
+        captured = False
         if use_graph and S.graph_key != gkey:
             # every slot is idle here: the warm-up and the capture move no counter and write no cache line, so there is
             # no state to restore (the activations they leave are overwritten by each admission)
@@ -549,7 +608,8 @@ class T2SInfer:
             with torch.cuda.graph(g, capture_error_mode="relaxed"):
                 S.step_launches(W, sp, noise, pe)
             S.graph, S.graph_key, S._keep = g, gkey, (sp, noise, pe, W)
-        return S, W, sp, pe, noise, use_graph
+            captured = True
+        return S, W, sp, pe, noise, use_graph, captured
 
     @torch.no_grad()
     def _admit(self, S, W, sp, pe, noise, batch, seeds):
@@ -564,7 +624,7 @@ class T2SInfer:
         x_lens = [int(q[1].numel()) for _s, q in batch]
         Pk = max(y_lens)
         rows, prs = [], []
-        for _slot, (_r, x, bert, prompt, _lim) in batch:
+        for _slot, (_r, x, bert, prompt, _lim, _samp) in batch:
             x, bert = x.to(dev), bert.to(dev)
             xe = m.ar_text_embedding(x.unsqueeze(0))
             xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
@@ -593,6 +653,9 @@ class T2SInfer:
         S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
         S.stop[slots_t] = -1
         S.row_seed[slots_t] = torch.tensor([list(seeds(q[0])) for _s, q in batch], dtype=torch.int32).to(dev)
+        tab = torch.tensor([[0.0, *q[5][1:]] for _s, q in batch], dtype=torch.float32)
+        tab.view(torch.int32)[:, 0] = torch.tensor([q[5][0] for _s, q in batch], dtype=torch.int32)
+        S.row_sample[slots_t] = tab.view(torch.int32).to(dev)      # moved as integers: every bit pattern survives
         S.x_lens[slots_t] = xl
         S.y[slots_t] = 0
         S.y[slots_t, :Pk] = pr
@@ -603,7 +666,7 @@ class T2SInfer:
         S._gemv(W.wpred, None, S.xb, None, None, None, 0.0, None, S.logits)
         S._sample_embed(W, sp, noise, pe, 0, S.mask)
 
-    def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll):
+    def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None):
         G, draws = self.MAX_ROWS, []
 
         def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
@@ -613,8 +676,9 @@ class T2SInfer:
                                  else torch.randint(0, 2 ** 31 - 1, (1,)).item()) & 0x7FFFFFFF)
             return draws[g], r % G
 
-        stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_s=[], events=[])
+        stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_s=[], events=[], graph_captured=False)
         free, running, S, exhausted = list(range(slots)), {}, None, False
+        cancelled = control.cancelled if control is not None else ()
         while True:
             batch = []
             while free and not exhausted:
@@ -624,12 +688,16 @@ class T2SInfer:
                     exhausted = True
                     break
                 self._fits(q, cap)
+                if q[0] in cancelled:            # withdrawn while it waited: no prompt pass, no slot
+                    stats["events"].append(("cancel", stats["steps"], q[0], None))
+                    yield q[0], None, None
+                    continue
                 batch.append((free.pop(0), q))
             if batch:
                 dev = batch[0][1][1].device
                 if S is None:
-                    S, W, sp, pe, noise, use_graph = self._stream_open(cap, slots, dev, top_k, top_p, temperature,
-                                                                      repetition_penalty, noise)
+                    S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
+                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise)
                 cuda = torch.device(dev).type == "cuda"
                 if cuda:
                     torch.cuda.synchronize(dev)
@@ -662,12 +730,17 @@ class T2SInfer:
                 if status in (ROW_STOP_EOS, ROW_STOP_LIMIT):
                     last = st[S.B * ROW_WORDS + slot]
                     done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last))
+                elif r in cancelled:
+                    # an ordinary write on the stream of the replays: the row's workgroups see IDLE from the next
+                    # replay on and return at once, whatever an admission later makes of the slot
+                    S.rstate[slot, ROW_STATUS] = ROW_IDLE
+                    done.append((slot, r, None, None))
             if n == 0 and not done:
                 raise L.EvtError("stream session: a row is past its step limit but not stopped")
             for slot, r, y, idx in done:
                 del running[slot]
                 free.append(slot)
-                stats["events"].append(("finish", stats["steps"], r, slot))
+                stats["events"].append(("finish" if y is not None else "cancel", stats["steps"], r, slot))
             free.sort()
             for slot, r, y, idx in done:
                 yield r, y, idx
@@ -677,15 +750,29 @@ class T2SInfer:
                                        poll=8, **kwargs):
         """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
         the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
-        of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths."""
+        of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths.
+        top_k, top_p, temperature, repetition_penalty and early_stop_num: a scalar for all texts, or a sequence with
+        one value per text."""
         if prompts is None:
             return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
                                                   early_stop_num=early_stop_num, temperature=temperature, noise=noise,
                                                   seed=seed, poll=poll)
-        reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(len(x))]
+        R = len(x)
+        given = dict(top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty,
+                     early_stop_num=early_stop_num)
+        per = {k: list(v) for k, v in given.items()
+               if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0)}
+        for k, v in per.items():
+            if len(v) != R:
+                raise L.EvtError(f"{k}: {len(v)} values for {R} texts")
+            v[:] = [e.item() if torch.is_tensor(e) else e for e in v]
+        wide = {k: (per[k][0] if k in per and R else v) for k, v in given.items()}     # per-text values replace these
+        if per:
+            reqs = [(x[r], bert_feature[r], prompts[r], {k: v[r] for k, v in per.items()}) for r in range(R)]
+        else:
+            reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(R)]
         ys, idxs = [None] * len(reqs), [None] * len(reqs)
-        for r, y, idx in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), top_k=top_k, top_p=top_p,
-                                            temperature=temperature, repetition_penalty=repetition_penalty,
-                                            early_stop_num=early_stop_num, noise=noise, seed=seed, poll=poll):
+        for r, y, idx in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed,
+                                            poll=poll, **wide):
             ys[r], idxs[r] = y, idx
         return ys, idxs

@@ -8,7 +8,10 @@
 // workgroups, so
 //   dec_attn_rows          is dec_attn with pos = rstate[b][POS]; a row that is not running returns at once;
 //   dec_sample_embed_rows  samples, appends, tests EOS / the step limit, embeds the next input and moves the row's
-//                          counters in ONE launch for all rows (three launches in a session with shared counters).
+//                          counters in ONE launch for all rows (three launches in a session with shared counters);
+//   dec_sample_embed_rows_p  is the same launch with top_k / top_p / temperature / repetition_penalty of row b read from
+//                          a device table row_sample[b], so requests of one session sample with their own values and
+//                          the captured step graph does not depend on them.
 // A row that stops (EOS, or its limit) is marked in the same launch and is skipped from then on: however late the host
 // reads the status, a stopped row never advances its position or writes past its buffers.
 // The counters are written with ordinary stores by thread 0 of the row's workgroup after a barrier.
@@ -47,15 +50,12 @@ __global__ __launch_bounds__(256) void dec_attn_rows(const float* __restrict__ q
 
 struct RowEmbed { const float* emb; const float* pe; const float* alpha; float* x; float x_scale; int E, npos, dpos; };
 
-__global__ __launch_bounds__(1024) void dec_sample_embed_rows(evt_sample_params p, const float* __restrict__ logits,
-                                                              long* y, int* rstate, const float* __restrict__ noise,
-                                                              int* stop_idx, float* probs_out,
-                                                              const int* __restrict__ row_seed,
-                                                              const int* __restrict__ row_mask, RowEmbed ea) {
+// The end of a step for row b = blockIdx.x, shared by the two kernels below.  `p` is this workgroup's own copy of the
+// sampling parameters: the session-wide one, or that copy with the row's four values written over it.
+__device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, const float* __restrict__ logits, long* y,
+                                                 int* rs, const float* __restrict__ noise, int* stop_idx,
+                                                 float* probs_out, const int* __restrict__ row_seed, const RowEmbed& ea) {
   const int tid = threadIdx.x, b = blockIdx.x, V = p.V;
-  if (row_mask && !row_mask[b]) return;
-  int* rs = rstate + b * EVT_ROW_WORDS;
-  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
   const int idx = rs[EVT_ROW_IDX], ycount = rs[EVT_ROW_YCOUNT], ylen = rs[EVT_ROW_YLEN], limit = rs[EVT_ROW_LIMIT];
   int col = rs[EVT_ROW_NOISE];
   if (col < 0 || col >= p.noise_rows) col = 0;
@@ -71,9 +71,12 @@ __global__ __launch_bounds__(1024) void dec_sample_embed_rows(evt_sample_params 
   const float al = ea.alpha[0];
   // the rounding is spelled out (one product rounded, then one fused multiply-add) instead of left to the compiler's
   // contraction, which picks different forms for different loop shapes: this is what dec_embed computes at E = 512
+  // sample_row's arg-max leaves its start value 0x7fffffff when every probability is NaN (NaN logits, or a NaN among
+  // the sampling parameters): the token is stored as it is for the host to see, the embedding row is kept in range
+  const int trow = (unsigned)tok < (unsigned)V ? tok : 0;
   for (int c = tid; c < ea.E; c += 1024)
     ea.x[(long)b * ea.E + c] =
-        __fmaf_rn(ea.emb[(long)tok * ea.E + c], ea.x_scale, __fmul_rn(al, ea.pe[(long)ppos * ea.E + c]));
+        __fmaf_rn(ea.emb[(long)trow * ea.E + c], ea.x_scale, __fmul_rn(al, ea.pe[(long)ppos * ea.E + c]));
   __syncthreads();       // every read of the row's state above is done; only this workgroup touches it
   if (tid == 0) {
     if (ycount < p.ymax) yb[ycount] = tok;
@@ -89,6 +92,46 @@ __global__ __launch_bounds__(1024) void dec_sample_embed_rows(evt_sample_params 
       rs[EVT_ROW_YCOUNT] = ycount + 1;
     }
   }
+}
+
+__global__ __launch_bounds__(1024) void dec_sample_embed_rows(evt_sample_params p, const float* __restrict__ logits,
+                                                              long* y, int* rstate, const float* __restrict__ noise,
+                                                              int* stop_idx, float* probs_out,
+                                                              const int* __restrict__ row_seed,
+                                                              const int* __restrict__ row_mask, RowEmbed ea) {
+  const int b = blockIdx.x;
+  if (row_mask && !row_mask[b]) return;
+  int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
+  sample_embed_row(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea);
+}
+
+// dec_sample_embed_rows with top_k / top_p / temperature / repetition_penalty of row b taken from row_sample[b]
+__global__ __launch_bounds__(1024) void dec_sample_embed_rows_p(evt_sample_params p,
+                                                                const evt_row_sample* __restrict__ row_sample,
+                                                                const float* __restrict__ logits, long* y, int* rstate,
+                                                                const float* __restrict__ noise, int* stop_idx,
+                                                                float* probs_out, const int* __restrict__ row_seed,
+                                                                const int* __restrict__ row_mask, RowEmbed ea) {
+  const int b = blockIdx.x;
+  if (row_mask && !row_mask[b]) return;
+  int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
+  // One 16-byte entry per row, addressed by blockIdx.x alone: every thread of the workgroup loads the same four values,
+  // so the branches of sample_row on them (repetition_penalty != 1, top_p < 1, top_k > 0) are taken by all 1024 threads
+  // or by none, and the barriers inside `if (p.top_p < 1.0f)` stay non-divergent, as with the by-value parameters.
+  // No table value can move an address out of bounds.  top_k only selects si[kk - 1] after the clamp 1 <= kk <= Ve
+  // (top_k <= 0 skips the pivot), and si[] holds the sort's own indices 0..kSortN-1 into cur[kSortN].  top_p,
+  // temperature and repetition_penalty feed comparisons, multiplications and divisions of values, never an index.  The
+  // one index derived from those values is the token: with NaN probabilities the arg-max returns 0x7fffffff, which
+  // sample_embed_row keeps away from the embedding table and which only lands in the row's own y slot.  The host still
+  // refuses non-finite values and repetition_penalty <= 0 before they reach the table.
+  const evt_row_sample r = row_sample[b];
+  p.top_k = r.top_k;
+  p.top_p = r.top_p;
+  p.temperature = r.temperature;
+  p.repetition_penalty = r.repetition_penalty;
+  sample_embed_row(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea);
 }
 
 }  // namespace
@@ -124,6 +167,25 @@ int evt_dec_sample_embed_rows(const evt_sample_params* p, const float* logits, i
   if (sp.noise_rows < 1) sp.noise_rows = 1;
   hipLaunchKernelGGL(dec_sample_embed_rows, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y,
                      (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed, (const int*)row_mask, ea);
+  return evt_check_launch();
+}
+
+int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                const float* alpha, float x_scale, float* x, int32_t B, int32_t E, int32_t npos,
+                                int32_t dpos, void* stream) {
+  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 ||
+      E <= 0 || npos <= 0 || dpos < 0)
+    return EVT_EINVAL;
+  // the four per-row values live in device memory: the host that fills the table validates them (t2s_infer.py)
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
+  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  hipLaunchKernelGGL(dec_sample_embed_rows_p, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
+                     (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
+                     (const int*)row_mask, ea);
   return evt_check_launch();
 }
 

@@ -108,6 +108,12 @@ class SampleParams(C.Structure):
                 ("repetition_penalty", C.c_float), ("seed", C.c_uint32), ("noise_rows", C.c_int32)]
 
 
+class RowSample(C.Structure):
+    """evt_row_sample: one row of a stream session's device table (16 bytes)"""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float),
+                ("repetition_penalty", C.c_float)]
+
+
 DEC_POS, DEC_IDX, DEC_YCOUNT, DEC_YLEN, DEC_SEED = 0, 1, 2, 3, 4
 
 

@@ -44,26 +44,36 @@ def synthesize_fragments(t2s, voice, batch_phones, all_phoneme_ids, all_bert_fea
 
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
-                      decode_kwargs=None, sample_kwargs=None):
+                      decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
     free row); each is turned into audio on its own by the s2 decoder as soon as its tokens are there, at any
     speed_factor, while the other rows' tokens wait in the session.  prompt_semantic: [1, P] for all fragments, or a
-    list with one token vector per fragment (fragments of several reference voices in one session)."""
+    list with one token vector per fragment (fragments of several reference voices in one session).
+    fragment_sampling: a list with one dict (keys out of top_k, top_p, temperature, repetition_penalty, early_stop_num)
+    or None per fragment, replacing the values above for that fragment alone.  control: a StreamControl of
+    auto_reg/t2s_infer.py; a fragment cancelled through it is yielded as (index, None) and never reaches the s2 decoder."""
     model, dev = t2s.model, t2s.device
     n = len(all_phoneme_ids)
     if prompt_semantic is None:
         raise ValueError("synthesize_stream needs the prompt's semantic tokens")
     prompts = ([p.reshape(-1).to(dev) for p in prompt_semantic] if isinstance(prompt_semantic, (list, tuple))
                else [prompt_semantic.reshape(-1).to(dev)] * n)
+    if fragment_sampling is not None and len(fragment_sampling) != n:
+        raise ValueError(f"fragment_sampling has {len(fragment_sampling)} entries for {n} fragments")
     reqs = [(p.to(dev), b.to(dev), pr) for p, b, pr in zip(all_phoneme_ids, all_bert_features, prompts)]
+    if fragment_sampling is not None:
+        reqs = [q if fs is None else (*q, dict(fs)) for q, fs in zip(reqs, fragment_sampling)]
     refer = [r.to(dev) for r in refer_specs]
     kw = decode_kwargs or {}
     stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
                                  early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
-                                 **(sample_kwargs or {}))
+                                 control=control, **(sample_kwargs or {}))
     for r, y, idx in stream:
+        if y is None:                      # cancelled: no tokens, no s2 decode
+            yield r, None
+            continue
         with torch.no_grad():
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             wav = voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]

@@ -763,6 +763,16 @@ int evt_dec_sample_embed_rows(const evt_sample_params* p, const float* logits, i
                               const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed,
                               const int32_t* row_mask, const float* emb, const float* pe, const float* alpha,
                               float x_scale, float* x, int32_t B, int32_t E, int32_t npos, int32_t dpos, void* stream);
+/* evt_dec_sample_embed_rows with top_k, top_p, temperature and repetition_penalty of row b read from row_sample[b]
+ * (device memory, [B]) instead of p; V, eos, no_eos_steps, ymax, seed and noise_rows stay in p.  A table whose entries
+ * all equal p's values gives evt_dec_sample_embed_rows bit for bit.  The launcher cannot see the table: the caller keeps
+ * repetition_penalty > 0 and every float finite (no table value can move a memory access, see the kernel). */
+typedef struct evt_row_sample { int32_t top_k; float top_p, temperature, repetition_penalty; } evt_row_sample;  /* 16 bytes */
+int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                const float* alpha, float x_scale, float* x, int32_t B, int32_t E, int32_t npos,
+                                int32_t dpos, void* stream);
 
 /* ScaledAdam (src/easevoice/soundstorm/auto_reg/modules/optim.py:206-251,300-390,448-622) over a flat fp32 arena.
  * The reference stacks same-shaped tensors only to batch its torch ops; the arithmetic is per tensor, which is what

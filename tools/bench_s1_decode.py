@@ -13,6 +13,7 @@ time of both sessions with 32 rows alive for --tokens steps, and the prefill tim
 
     python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
     python tools/bench_s1_decode.py --stream [--stream-n 96]
+    python tools/bench_s1_decode.py --stream --mixed 4      (per-request sampling parameters, see run_mixed)
 """
 import argparse
 import json
@@ -34,8 +35,8 @@ def _median(v):
     return v[len(v) // 2]
 
 
-def run_stream(args, m, dev, x, bert, prompts):
-    """grouped against refilled decoding of the same requests (see the module docstring)"""
+def _stream_workload(args, dev, x, bert, prompts):
+    """the texts of --stream: (lives, xs, berts, prompts, noise table, decode arguments, the noise generator)"""
     import random
 
     N, lo, hi, poll = args.stream_n, 64, 512, 8
@@ -53,6 +54,73 @@ def run_stream(args, m, dev, x, bert, prompts):
         noise[s, r, 1024] = 1e-30             # ... except at the text's own step (top_k covers the whole vocabulary)
     noise = noise.to(dev)
     kw = dict(top_k=1100, top_p=1, early_stop_num=hi + 8, repetition_penalty=1.35, poll=poll)
+    return lives, xs, berts, pr, noise, kw, g
+
+
+def run_mixed(args, m, dev, x, bert, prompts):
+    """--mixed N: request r samples with parameter set r % N.  One refilled session that holds all sets (per-request
+    values) against what a caller without them has to do: N uniform streams, one per set, one after the other.  The sets
+    differ in temperature and repetition penalty only, so the forced EOS steps and with them the useful tokens are the
+    same in both."""
+    lives, xs, berts, pr, noise, kw, _g = _stream_workload(args, dev, x, bert, prompts)
+    N, M = args.stream_n, args.mixed
+    sets = [dict(temperature=1.0 + 0.05 * k, repetition_penalty=1.35 - 0.05 * k) for k in range(M)]
+    kw = {k: v for k, v in kw.items() if k != "repetition_penalty"}
+    cap = dict(max_text_len=args.x_len, max_prompt_len=args.prompt)      # one capacity: every stream may share a session
+    infer = m._infer()
+    groups = [list(range(k, N, M)) for k in range(M)]
+    tables = [noise[:, members].contiguous() for members in groups]      # stream k reads its members' columns
+
+    def mixed():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reqs = [(xs[r], berts[r], pr[r], sets[r % M]) for r in range(N)]
+        ys = [None] * N
+        for r, y, _i in m.decode_stream(reqs, slots=32, noise=noise, **cap, **kw):
+            ys[r] = y
+        torch.cuda.synchronize()
+        st = infer.stream_stats
+        return ys, time.perf_counter() - t0, st["steps"], [bool(st["graph_captured"])]
+
+    def uniform():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys, steps, captured = [None] * N, 0, []
+        for k in range(M):
+            members = groups[k]
+            reqs = [(xs[r], berts[r], pr[r]) for r in members]
+            for i, y, _i in m.decode_stream(reqs, slots=32, noise=tables[k], **cap, **kw, **sets[k]):
+                ys[members[i]] = y
+            steps += infer.stream_stats["steps"]
+            captured.append(bool(infer.stream_stats["graph_captured"]))
+        torch.cuda.synchronize()
+        return ys, time.perf_counter() - t0, steps, captured
+
+    runs = dict(uniform=[], mixed=[])
+    for rep in range(args.reps + 1):
+        for name, fn in (("uniform", uniform), ("mixed", mixed)):      # alternated: both see the same state of the device
+            ys, t, steps, captured = fn()
+            assert [y.numel() for y in ys] == [args.prompt + s for s in lives], name
+            runs[name].append((t, steps, captured))
+    useful, out = sum(lives), {}
+    for name, v in runs.items():
+        t, steps, _c = sorted(v[1:], key=lambda e: e[0])[len(v[1:]) // 2]
+        out[name] = dict(seconds=round(t, 4), steps=steps, useful_tokens=useful, tokens_per_s=round(useful / t, 1),
+                         seconds_all_runs=[round(e[0], 4) for e in v[1:]],
+                         graph_captures_first_pass=sum(v[0][2]), graph_captures_timed_passes=sum(sum(e[2]) for e in v[1:]))
+    out["mixed_over_uniform"] = round(out["uniform"]["seconds"] / out["mixed"]["seconds"], 3)
+    print(json.dumps(dict(workload=f"s1 decode stream, {N} texts living 64..512 steps, {M} parameter sets (request r: "
+                                   f"set r % {M}), x_len<={args.x_len}, prompt={args.prompt}, {args.dtype}, 32 slots; "
+                                   f"uniform = {M} streams of {N // M} texts one after the other, mixed = one session; "
+                                   "all streams share one capacity and one session; the step graph is keyed by the "
+                                   "noise table, so each uniform stream (own table) captures again, as a stream per "
+                                   "parameter set did when the parameters were part of the key", **out)))
+
+
+def run_stream(args, m, dev, x, bert, prompts):
+    """grouped against refilled decoding of the same requests (see the module docstring)"""
+    lives, xs, berts, pr, noise, kw, g = _stream_workload(args, dev, x, bert, prompts)
+    N, lo, hi, poll = args.stream_n, 64, 512, 8
     infer = m._infer()
 
     def grouped():
@@ -157,6 +225,9 @@ def main():
     ap.add_argument("--stream", action="store_true",
                     help="time the refilled session against infer_panel_batch_infer on --stream-n texts (nothing else)")
     ap.add_argument("--stream-n", type=int, default=96)
+    ap.add_argument("--mixed", type=int, default=0, metavar="N",
+                    help="with --stream: request r samples with parameter set r %% N; one session holding all sets "
+                         "against N uniform streams run one after the other (nothing else)")
     args = ap.parse_args()
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
@@ -178,6 +249,10 @@ def main():
     noise = noise.to(dev)
     if args.stream:
         os.environ["EVT_DECODE_GRAPH"] = "1"
+        if args.mixed:
+            assert 1 <= args.mixed <= 8, args.mixed
+            run_mixed(args, m, dev, x, bert, prompts)
+            return
         run_stream(args, m, dev, x, bert, prompts)
         return
     esz = 2 if dtype == torch.bfloat16 else 4
