@@ -15,10 +15,14 @@ Same token sequence as the reference for the same sampling noise; a different ex
     one session have their own prompt length, step index and limit; a finished row's slot is refilled with the next
     waiting text between two graph replays and results are handed out as they finish.  The sampling parameters are per
     row as well (a device table next to the counters), so requests of one session may differ in them, one captured graph
-    serves every parameter set, and a request can be cancelled between two polls (StreamControl).
+    serves every parameter set, and a request can be cancelled between two polls (StreamControl).  A request may ask
+    for n candidates: one prompt pass, n slots, n noise lanes; with logprobs=True the sampler also writes the model's and
+    the sampler's log-probability of every drawn token (evt_dec_sample_embed_rows_lp).
 The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
+import collections
 import ctypes as C
 import math
+import operator
 import os
 import time
 
@@ -149,6 +153,11 @@ ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 SAMPLE_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty")
 
 
+# what decode_stream yields when log-probabilities or several candidates per request were asked for: candidate c of
+# `request`; y, idx as in the 3-tuple form; logprobs None or fp32 [steps taken][2] (model, sampler), see decode_stream
+StreamOutput = collections.namedtuple("StreamOutput", "request y idx candidate logprobs")
+
+
 class StreamControl:
     """handle of a running decode_stream for the caller that consumes it: cancel(r) withdraws request r.  It only
     records the index; the stream acts at its next poll, so the caller cancels between two next() calls (one thread)."""
@@ -187,6 +196,8 @@ class StreamSession:
         self.row_seed = z(B, 2, dt=torch.int32)
         self.row_sample = z(B, 4, dt=torch.int32)                 # evt_row_sample [B]: top_k, then the bits of 3 floats
         self.mask = z(B, dt=torch.int32)                          # rows of an admission's step 0
+        self.logp, self.lp_on = None, False                       # [B][ymax][2] of a logprobs=True stream, made on demand
+        self.noise_cands = 1                                      # C of an injected [steps][R][C][V] noise table
         self.graph, self.graph_key = None, None
 
     def reset(self):
@@ -208,7 +219,16 @@ class StreamSession:
     def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
         (each row's workgroup owns its counters); `mask` restricts it to the rows of an admission.  top_k, top_p,
-        temperature and repetition_penalty of a row come from row_sample[b]; `sp` carries the session-wide rest"""
+        temperature and repetition_penalty of a row come from row_sample[b]; `sp` carries the session-wide rest.  A
+        stream with logprobs=True launches the variant that also fills logp[b][YCOUNT]"""
+        if self.lp_on:
+            L.check(L.lib().evt_dec_sample_embed_rows_lp(
+                C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
+                L.ptr(self.stop), None,
+                L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
+                C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), L.ptr(self.logp), self.B, self.E,
+                pe.size(0), dpos, L.stream_ptr()), "evt_dec_sample_embed_rows_lp")
+            return
         L.check(L.lib().evt_dec_sample_embed_rows_p(
             C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
             L.ptr(self.stop), None,
@@ -490,7 +510,7 @@ class T2SInfer:
 
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
                       early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
-                      control=None):
+                      control=None, n=1, logprobs=False):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
         (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
         content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
@@ -507,13 +527,42 @@ class T2SInfer:
         is bounded by `early_stop_num`.  A request that does not fit raises EvtError before anything is launched for
         it.  Request r draws the built-in noise of (seed + 4 * (r // 4), r % 4), the convention of
         infer_panel_batch_infer; an injected table [steps][R][V] is read at column r ([steps][V]: by every request).
-        One stream at a time per model and capacity: the session's buffers are shared."""
+        One stream at a time per model and capacity: the session's buffers are shared.
+
+        n: candidates per request (1..slots; a request's dict may carry "n" for itself).  The n candidates of a request
+        are admitted together after ONE prompt pass, whose keys/values are copied into n slots; the queue stays FIFO, so
+        a head request waits until n slots are free and nothing overtakes it.  Candidate c of request r draws lane
+        r % 4 + 4c of the group seed of r: candidate 0 is what n = 1 gives.  An injected table may be
+        [steps][R][C][V], candidate c of request r reading [.., r, c, :]; a table without that dimension serves n = 1
+        only.  logprobs=True: the sampler also records, per drawn token, the log-softmax of the raw logits at the token
+        and the log of the probability it was drawn from (after penalty, nucleus, top-k, temperature).  With
+        logprobs=True or any n > 1 the generator yields StreamOutput(request, y, idx, candidate, logprobs) instead of
+        3-tuples, exactly n per request (y = idx = logprobs = None for a cancelled candidate); logprobs is None when
+        not asked for, else fp32 [last + 1, 2]: rows 0 .. len(y) - prompt_len - 1 belong to y[prompt_len:], the last
+        row to the step that stopped the candidate.  A lazy iterable fixes the form when it is opened: there a
+        request's own "n" > 1 needs logprobs=True or a session-wide n > 1."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
         if not 1 <= int(slots) <= self.WIDE_ROWS:
             raise L.EvtError(f"slots must be 1..{self.WIDE_ROWS}, got {slots}")
+        slots, logprobs = int(slots), bool(logprobs)
         nsteps = None if noise is None else int(noise.size(0))
         ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
+        ncand = int(noise.size(2)) if noise is not None and noise.dim() == 4 else None
+
+        def candidates(v, who):
+            try:
+                if isinstance(v, bool):
+                    raise TypeError("a bool")
+                v = operator.index(v)
+            except TypeError:
+                raise L.EvtError(f"{who}: n = {v!r} is not an integer") from None
+            if not 1 <= v <= slots:
+                raise L.EvtError(f"{who}: n = {v} must be 1..slots = {slots}")
+            return v
+
+        base_n = candidates(n, "decode_stream")
+        lazy = not isinstance(requests, (list, tuple))
 
         base = dict(zip(SAMPLE_KEYS, (top_k, top_p, temperature, repetition_penalty)))
         base_v = self._sampling(top_k, top_p, temperature, repetition_penalty, "decode_stream")
@@ -522,12 +571,14 @@ class T2SInfer:
             if len(req) not in (3, 4):
                 raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num or dict])")
             x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
-            opt, samp = req[3] if len(req) == 4 else None, base_v
+            opt, samp, nr = req[3] if len(req) == 4 else None, base_v, base_n
             if isinstance(opt, dict):
-                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num"})
+                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num", "n"})
                 if unknown:
-                    raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)} and "
-                                     "early_stop_num)")
+                    raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)}, "
+                                     "early_stop_num and n)")
+                if "n" in opt:
+                    nr = candidates(opt["n"], f"request {r}")
                 samp = self._sampling(*({**base, **{k: v for k, v in opt.items() if k in SAMPLE_KEYS}}[k]
                                         for k in SAMPLE_KEYS), f"request {r}")
                 opt = opt.get("early_stop_num")
@@ -538,12 +589,22 @@ class T2SInfer:
                 raise L.EvtError(f"request {r}: empty text or prompt")
             if ncols is not None and r >= ncols:
                 raise L.EvtError(f"request {r}: the noise table has {ncols} columns")
-            return r, x, bert, prompt, lim, samp
+            if nr > 1 and noise is not None and ncand is None:
+                raise L.EvtError(f"request {r}: n = {nr}, but the noise table has no candidate dimension "
+                                 "([steps][R][C][V])")
+            if ncand is not None and nr > ncand:
+                raise L.EvtError(f"request {r}: n = {nr}, but the noise table has {ncand} candidates per request")
+            if lazy and nr > 1 and not (logprobs or base_n > 1):
+                raise L.EvtError(f"request {r}: n = {nr} in a lazy stream needs logprobs=True or a session-wide n > 1 "
+                                 "(the form of the outputs is fixed when the stream is opened)")
+            return r, x, bert, prompt, lim, samp, nr
 
-        if isinstance(requests, (list, tuple)):
+        rich = logprobs or base_n > 1
+        if not lazy:
             reqs = [norm(r, q) for r, q in enumerate(requests)]
             if not reqs:
                 return iter(())
+            rich = rich or any(q[6] > 1 for q in reqs)
             Xmax = int(max_text_len) if max_text_len is not None else max(q[1].numel() for q in reqs)
             Pmax = int(max_prompt_len) if max_prompt_len is not None else max(q[3].numel() for q in reqs)
             n_max = max(q[4] for q in reqs)
@@ -560,8 +621,8 @@ class T2SInfer:
                 n_max = min(n_max, nsteps)
             cap = (int(max_text_len), int(max_prompt_len), n_max)
             it = (norm(r, q) for r, q in enumerate(requests))
-        return self._stream(it, cap, int(slots), top_k, top_p, temperature, repetition_penalty, noise, seed,
-                            max(1, int(poll)), control)
+        return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
+                            max(1, int(poll)), control, logprobs, rich)
 
     @staticmethod
     def _fits(q, cap):
@@ -571,20 +632,25 @@ class T2SInfer:
                              f"session's capacity (text {cap[0]}, prompt {cap[1]}, {cap[2]} steps)")
 
     @torch.no_grad()
-    def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise):
+    def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs=False):
         """session, weights, sampling parameters and the captured step graph; every slot idle"""
         m = self.model
         cd = m.cd
         L.set_half(cd)
         W = self.weights(cd)
         Xmax, Pmax, n_max = cap
-        noise_rows = 1
+        noise_rows, cands = 1, 1
         if noise is not None:
             noise = noise.to(dev, torch.float32).contiguous()
+            if noise.dim() == 4:      # [steps][R][C][V]: candidate c of request r reads the flattened column r * C + c
+                cands, noise = noise.size(2), noise.flatten(1, 2)
             noise_rows = 1 if noise.dim() == 2 else noise.size(1)
             assert noise.size(-1) == m.vocab_size
         S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev)
         S.reset()
+        S.lp_on, S.noise_cands = bool(logprobs), cands
+        if S.lp_on and S.logp is None:
+            S.logp = torch.zeros(S.B, S.ymax, 2, dtype=torch.float32, device=dev)
         sp = L.SampleParams(S.V, m.EOS, int(top_k) if top_k is not None else 0, 1, S.ymax, float(top_p),
                             float(temperature), float(repetition_penalty), 0x5EED5EED, noise_rows)
         pe = m.ar_audio_position.pe(max(4000, Pmax + n_max + 1), dev, torch.float32).contiguous()
@@ -595,6 +661,8 @@ class T2SInfer:
         # on them
         gkey = (sp.V, sp.eos, sp.no_eos_steps, sp.ymax, sp.seed, sp.noise_rows,
                 None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W))
+        if S.lp_on:      # another sampler kernel in the graph; a session without it keeps the key it always had
+            gkey = gkey + ("logprobs",)
         captured = False
         if use_graph and S.graph_key != gkey:
             # every slot is idle here: the warm-up and the capture move no counter and write no cache line, so there is
@@ -613,9 +681,10 @@ class T2SInfer:
 
     @torch.no_grad()
     def _admit(self, S, W, sp, pe, noise, batch, seeds):
-        """batch: [(slot, (r, x, bert, prompt, limit))].  The prompt pass of _decode for these requests only (texts padded
-        to Xmax, prompts to the longest of them), their keys/values into their slots' cache slabs, their row state, then
-        step 0 for those rows: logits of the last prompt position and a masked sample."""
+        """batch: [(slots, (r, x, bert, prompt, limit, sampling, n))], `slots` the n slots of the request's candidates in
+        candidate order.  The prompt pass of _decode for these requests only, ONE row per request (texts padded to Xmax,
+        prompts to the longest of them); each row's keys/values go into the cache slabs of all its slots, then the row
+        state of every slot and step 0 for those slots: logits of the last prompt position and a masked sample."""
         m = self.model
         dev, cd = S.device, S.dtype
         dense = self.dense(cd, dev)
@@ -624,7 +693,7 @@ class T2SInfer:
         x_lens = [int(q[1].numel()) for _s, q in batch]
         Pk = max(y_lens)
         rows, prs = [], []
-        for _slot, (_r, x, bert, prompt, _lim, _samp) in batch:
+        for _slots, (_r, x, bert, prompt, _lim, _samp, _n) in batch:
             x, bert = x.to(dev), bert.to(dev)
             xe = m.ar_text_embedding(x.unsqueeze(0))
             xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
@@ -636,37 +705,50 @@ class T2SInfer:
         src_len = Xmax + Pk
         xl = torch.tensor(x_lens, dtype=torch.int32, device=dev)
         yl = torch.tensor(y_lens, dtype=torch.int32, device=dev)
-        slots_t = torch.tensor([s for s, _q in batch], dtype=torch.long, device=dev)
+        # per slot: (prompt row it copies from, candidate number, its request); one entry per request when every n is 1
+        per = [(i, c, q) for i, (sl, q) in enumerate(batch) for c in range(len(sl))]
+        slots_t = torch.tensor([s for sl, _q in batch for s in sl], dtype=torch.long, device=dev)
+        if len(per) == k:
+            spread = lambda t: t
+        else:
+            src_t = torch.tensor([i for i, _c, _q in per], dtype=torch.long, device=dev)
+            spread = lambda t: t[src_t]
         for i, lyr in enumerate(m.h.layers):
             w = W.layers[i]
             qkv = dense(xy, lyr.self_attn.in_proj_weight)
-            S.kc[i, slots_t, :src_len] = qkv[..., S.E:2 * S.E]
-            S.vc[i, slots_t, :src_len] = qkv[..., 2 * S.E:]
+            S.kc[i, slots_t, :src_len] = spread(qkv[..., S.E:2 * S.E])
+            S.vc[i, slots_t, :src_len] = spread(qkv[..., 2 * S.E:])
             o = PrefixLMAttentionFn.apply(qkv, xl, yl, Xmax, S.H, 0.0, 0)
             sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
             xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
             ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
             xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
         # ---- row state ----
-        ncol = 0 if noise is None or noise.dim() == 2 else None
-        rs = [[Xmax + yn, 0, yn, yn, q[4], ROW_RUNNING, q[0] if ncol is None else 0, 0] for yn, (_s, q) in zip(y_lens, batch)]
+        # noise column: none for a [steps][V] table, the request's for [steps][R][V]; `noise` arrives with a candidate
+        # dimension flattened ([steps][R * C][V], _stream_open), C = S.noise_cands: column r * C + c
+        C_ = S.noise_cands
+        ncol = (lambda r, c: 0) if noise is None or noise.dim() == 2 else (lambda r, c: r * C_ + c)
+        rs = [[Xmax + y_lens[i], 0, y_lens[i], y_lens[i], q[4], ROW_RUNNING, ncol(q[0], c), 0] for i, c, q in per]
         S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
         S.stop[slots_t] = -1
-        S.row_seed[slots_t] = torch.tensor([list(seeds(q[0])) for _s, q in batch], dtype=torch.int32).to(dev)
-        tab = torch.tensor([[0.0, *q[5][1:]] for _s, q in batch], dtype=torch.float32)
-        tab.view(torch.int32)[:, 0] = torch.tensor([q[5][0] for _s, q in batch], dtype=torch.int32)
+        # candidate c draws lane r % 4 + 4c of the request's group seed (the hash folds the lane in as lane << 16)
+        S.row_seed[slots_t] = torch.tensor([[seeds(q[0])[0], seeds(q[0])[1] + self.MAX_ROWS * c] for _i, c, q in per],
+                                           dtype=torch.int32).to(dev)
+        tab = torch.tensor([[0.0, *q[5][1:]] for _i, _c, q in per], dtype=torch.float32)
+        tab.view(torch.int32)[:, 0] = torch.tensor([q[5][0] for _i, _c, q in per], dtype=torch.int32)
         S.row_sample[slots_t] = tab.view(torch.int32).to(dev)      # moved as integers: every bit pattern survives
-        S.x_lens[slots_t] = xl
+        S.x_lens[slots_t] = spread(xl)
         S.y[slots_t] = 0
-        S.y[slots_t, :Pk] = pr
+        S.y[slots_t, :Pk] = spread(pr)
         S.mask.zero_()
         S.mask[slots_t] = 1
         # ---- step 0 of the admitted rows (the other rows' xb / logits are dead between two steps) ----
-        S.xb[slots_t] = xy[torch.arange(k, device=dev), Xmax + yl.long() - 1].float()
+        S.xb[slots_t] = spread(xy[torch.arange(k, device=dev), Xmax + yl.long() - 1].float())
         S._gemv(W.wpred, None, S.xb, None, None, None, 0.0, None, S.logits)
         S._sample_embed(W, sp, noise, pe, 0, S.mask)
 
-    def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None):
+    def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None,
+                logprobs=False, rich=False):
         G, draws = self.MAX_ROWS, []
 
         def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
@@ -676,28 +758,38 @@ class T2SInfer:
                                  else torch.randint(0, 2 ** 31 - 1, (1,)).item()) & 0x7FFFFFFF)
             return draws[g], r % G
 
-        stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_s=[], events=[], graph_captured=False)
+        stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_rows=[], prefill_s=[], events=[],
+                                         graph_captured=False)
         free, running, S, exhausted = list(range(slots)), {}, None, False
         cancelled = control.cancelled if control is not None else ()
+        out = (lambda r, y, idx, c, lp: StreamOutput(r, y, idx, c, lp)) if rich else (lambda r, y, idx, c, lp: (r, y, idx))
+        head = None            # the request at the head of the queue, drawn but still waiting for its n slots
         while True:
             batch = []
-            while free and not exhausted:
-                try:
-                    q = next(it)
-                except StopIteration:
-                    exhausted = True
-                    break
-                self._fits(q, cap)
+            while free and (head is not None or not exhausted):
+                if head is None:
+                    try:
+                        head = next(it)
+                    except StopIteration:
+                        exhausted = True
+                        break
+                    self._fits(head, cap)
+                q = head
                 if q[0] in cancelled:            # withdrawn while it waited: no prompt pass, no slot
+                    head = None
                     stats["events"].append(("cancel", stats["steps"], q[0], None))
-                    yield q[0], None, None
+                    for c in range(q[6]):
+                        yield out(q[0], None, None, c, None)
                     continue
-                batch.append((free.pop(0), q))
+                if q[6] > len(free):             # FIFO: it waits for its n slots and nothing overtakes it
+                    break
+                head = None
+                batch.append(([free.pop(0) for _ in range(q[6])], q))
             if batch:
                 dev = batch[0][1][1].device
                 if S is None:
                     S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
-                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise)
+                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs)
                 cuda = torch.device(dev).type == "cuda"
                 if cuda:
                     torch.cuda.synchronize(dev)
@@ -707,10 +799,13 @@ class T2SInfer:
                     torch.cuda.synchronize(dev)
                 stats["prefill_s"].append(time.perf_counter() - t0)
                 stats["admissions"] += 1
-                stats["admitted"].append(len(batch))
-                for slot, q in batch:
-                    running[slot] = [q[0], int(q[3].numel()), q[4] - 1]     # request, prompt length, replays left at most
-                    stats["events"].append(("admit", stats["steps"], q[0], slot))
+                stats["admitted"].append(sum(len(sl) for sl, _q in batch))
+                stats["prefill_rows"].append(len(batch))
+                for sl, q in batch:
+                    for c, slot in enumerate(sl):
+                        # request, prompt length, replays left at most, candidate
+                        running[slot] = [q[0], int(q[3].numel()), q[4] - 1, c]
+                        stats["events"].append(("admit", stats["steps"], q[0], slot))
             if not running:
                 return
             n = min(poll, max(v[2] for v in running.values()))
@@ -724,36 +819,42 @@ class T2SInfer:
             st = S.state.tolist()                    # the only device->host read of the loop: status and stop of all rows
             done = []
             for slot in sorted(running):
-                r, ylen, left = running[slot]
+                r, ylen, left, c = running[slot]
                 running[slot][2] = max(0, left - n)
                 status = st[slot * ROW_WORDS + ROW_STATUS]
                 if status in (ROW_STOP_EOS, ROW_STOP_LIMIT):
                     last = st[S.B * ROW_WORDS + slot]
-                    done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last))
+                    # one pair per step 0..last, written at the index the step's token went to: y[ylen + step]
+                    lp = S.logp[slot, ylen:ylen + last + 1].clone() if logprobs else None
+                    done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last,
+                                 c, lp))
                 elif r in cancelled:
                     # an ordinary write on the stream of the replays: the row's workgroups see IDLE from the next
                     # replay on and return at once, whatever an admission later makes of the slot
                     S.rstate[slot, ROW_STATUS] = ROW_IDLE
-                    done.append((slot, r, None, None))
+                    done.append((slot, r, None, None, c, None))
             if n == 0 and not done:
                 raise L.EvtError("stream session: a row is past its step limit but not stopped")
-            for slot, r, y, idx in done:
+            for slot, r, y, idx, c, lp in done:
                 del running[slot]
                 free.append(slot)
                 stats["events"].append(("finish" if y is not None else "cancel", stats["steps"], r, slot))
             free.sort()
-            for slot, r, y, idx in done:
-                yield r, y, idx
+            for slot, r, y, idx, c, lp in done:
+                yield out(r, y, idx, c, lp)
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
                                        early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,
-                                       poll=8, **kwargs):
+                                       poll=8, logprobs=False, **kwargs):
         """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
         the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
         of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths.
         top_k, top_p, temperature, repetition_penalty and early_stop_num: a scalar for all texts, or a sequence with
-        one value per text."""
+        one value per text.  logprobs=True returns (ys, idxs, lps), lps[r] the fp32 [steps, 2] log-probabilities of text
+        r as decode_stream hands them out."""
         if prompts is None:
+            if logprobs:
+                raise L.EvtError("logprobs needs prompts (the refilled session)")
             return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
                                                   early_stop_num=early_stop_num, temperature=temperature, noise=noise,
                                                   seed=seed, poll=poll)
@@ -771,8 +872,10 @@ class T2SInfer:
             reqs = [(x[r], bert_feature[r], prompts[r], {k: v[r] for k, v in per.items()}) for r in range(R)]
         else:
             reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(R)]
-        ys, idxs = [None] * len(reqs), [None] * len(reqs)
-        for r, y, idx in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed,
-                                            poll=poll, **wide):
-            ys[r], idxs[r] = y, idx
-        return ys, idxs
+        ys, idxs, lps = [None] * len(reqs), [None] * len(reqs), [None] * len(reqs)
+        for o in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed, poll=poll,
+                                    logprobs=logprobs, **wide):
+            ys[o[0]], idxs[o[0]] = o[1], o[2]
+            if logprobs:
+                lps[o[0]] = o.logprobs
+        return (ys, idxs, lps) if logprobs else (ys, idxs)

@@ -182,9 +182,14 @@ constexpr int kSortN = 2048;
 // Called by all 1024 threads of a workgroup.  lg: the row's logits; yb[0..ycount): its tokens so far; q_row: the V noise
 // values of this (step, row) from an injected table, or NULL for the built-in noise keyed by (nseed, idx, nlane, v).
 // Returns the token on every thread; *amax is the arg-max of the penalised logits (the EOS test of t2s_model.py:846).
+// kLp (dec_sample_embed_rows_lp only): the thread that owns the token also stores log(pr[token]) to *slp (LDS), as
+// x - max - log(sum) of the values pr is the softmax of, so a surviving token never underflows to -inf; the caller reads
+// it after a barrier.  With kLp = false the function is the one every other sampler kernel has always compiled.
+template <bool kLp = false>
 __device__ __forceinline__ int sample_row(const evt_sample_params& p, const float* __restrict__ lg, const long* yb,
                                           int idx, int ycount, unsigned nseed, unsigned nlane,
-                                          const float* __restrict__ q_row, float* probs_row, int* amax_out) {
+                                          const float* __restrict__ q_row, float* probs_row, int* amax_out,
+                                          float* slp = nullptr) {
   __shared__ float sv[kSortN];
   __shared__ int si[kSortN];
   __shared__ float cur[kSortN];
@@ -301,6 +306,12 @@ __device__ __forceinline__ int sample_row(const evt_sample_params& p, const floa
     }
   }
   const int tok = block_argmax(best, besti, redv, redi, 16);
+  if constexpr (kLp) {
+    const float ls = logf(sum);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      if (tid + u * 1024 == tok) *slp = x0[u] - mx - ls;
+  }
   *amax_out = amax;
   return tok;
 }

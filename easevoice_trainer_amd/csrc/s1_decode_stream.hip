@@ -11,7 +11,10 @@
 //                          counters in ONE launch for all rows (three launches in a session with shared counters);
 //   dec_sample_embed_rows_p  is the same launch with top_k / top_p / temperature / repetition_penalty of row b read from
 //                          a device table row_sample[b], so requests of one session sample with their own values and
-//                          the captured step graph does not depend on them.
+//                          the captured step graph does not depend on them;
+//   dec_sample_embed_rows_lp is that launch again, which also writes the step's two log-probabilities of the drawn token
+//                          to row_logp[b][YCOUNT]: log_softmax of the raw logits (the model's) and the log of the
+//                          probability it was drawn from after penalty, nucleus, top-k and temperature (the sampler's).
 // A row that stops (EOS, or its limit) is marked in the same launch and is skipped from then on: however late the host
 // reads the status, a stopped row never advances its position or writes past its buffers.
 // The counters are written with ordinary stores by thread 0 of the row's workgroup after a barrier.
@@ -51,20 +54,37 @@ __global__ __launch_bounds__(256) void dec_attn_rows(const float* __restrict__ q
 struct RowEmbed { const float* emb; const float* pe; const float* alpha; float* x; float x_scale; int E, npos, dpos; };
 
 // The end of a step for row b = blockIdx.x, shared by the two kernels below.  `p` is this workgroup's own copy of the
-// sampling parameters: the session-wide one, or that copy with the row's four values written over it.
+// sampling parameters: the session-wide one, or that copy with the row's four values written over it.  kLp is a
+// compile-time switch, so the two kernels without log-probabilities compile the body they always had; with it, the raw
+// logits get a block_max / block_sum of their own before the sampler touches anything, and thread 0 adds two stores.
+template <bool kLp = false>
 __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, const float* __restrict__ logits, long* y,
                                                  int* rs, const float* __restrict__ noise, int* stop_idx,
-                                                 float* probs_out, const int* __restrict__ row_seed, const RowEmbed& ea) {
+                                                 float* probs_out, const int* __restrict__ row_seed, const RowEmbed& ea,
+                                                 float* row_logp = nullptr) {
   const int tid = threadIdx.x, b = blockIdx.x, V = p.V;
   const int idx = rs[EVT_ROW_IDX], ycount = rs[EVT_ROW_YCOUNT], ylen = rs[EVT_ROW_YLEN], limit = rs[EVT_ROW_LIMIT];
   int col = rs[EVT_ROW_NOISE];
   if (col < 0 || col >= p.noise_rows) col = 0;
   long* yb = y + (long)b * p.ymax;
   int amax;
-  const int tok = sample_row(p, logits + (long)b * V, yb, idx, ycount, (unsigned)row_seed[2 * b],
-                             (unsigned)row_seed[2 * b + 1],
-                             noise ? noise + ((long)idx * p.noise_rows + col) * V : nullptr,
-                             probs_out ? probs_out + (long)b * V : nullptr, &amax);
+  float rmax = -INFINITY, rlsum = 0.f;   // max and log(sum exp(. - max)) of the raw logits over this step's Ve columns
+  float* lpsh = nullptr;                 // LDS word for the sampler's log-probability; only the kLp kernel has it
+  if constexpr (kLp) {
+    __shared__ float lp_lds[17];
+    lpsh = lp_lds + 16;
+    const float* lg = logits + (long)b * V;
+    const int Ve = idx < p.no_eos_steps ? V - 1 : V;
+    for (int v = tid; v < Ve; v += 1024) rmax = fmaxf(rmax, lg[v]);
+    rmax = block_max(rmax, lp_lds, 16);
+    for (int v = tid; v < Ve; v += 1024) rlsum += expf(lg[v] - rmax);
+    rlsum = logf(block_sum(rlsum, lp_lds, 16));
+    if (tid == 0) lpsh[0] = NAN;   // stays when no thread owns the token (all-NaN probabilities)
+  }
+  const int tok = sample_row<kLp>(p, logits + (long)b * V, yb, idx, ycount, (unsigned)row_seed[2 * b],
+                                  (unsigned)row_seed[2 * b + 1],
+                                  noise ? noise + ((long)idx * p.noise_rows + col) * V : nullptr,
+                                  probs_out ? probs_out + (long)b * V : nullptr, &amax, lpsh);
   // x_next = emb[token] * x_scale + alpha * pe[y_len + idx]  (t2s_model.py:860-861)
   int ppos = ylen + idx;
   if (ppos >= ea.npos) ppos = ea.npos - 1;
@@ -80,6 +100,14 @@ __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, con
   __syncthreads();       // every read of the row's state above is done; only this workgroup touches it
   if (tid == 0) {
     if (ycount < p.ymax) yb[ycount] = tok;
+    if constexpr (kLp) {
+      if (ycount < p.ymax) {
+        const bool ok = (unsigned)tok < (unsigned)V;
+        float* o = row_logp + ((long)b * p.ymax + ycount) * 2;
+        o[0] = ok ? logits[(long)b * V + tok] - rmax - rlsum : NAN;
+        o[1] = ok ? lpsh[0] : NAN;
+      }
+    }
     if (amax == p.eos || tok == p.eos) {
       stop_idx[b] = idx;
       rs[EVT_ROW_STATUS] = EVT_ROW_STOP_EOS;
@@ -134,6 +162,29 @@ __global__ __launch_bounds__(1024) void dec_sample_embed_rows_p(evt_sample_param
   sample_embed_row(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea);
 }
 
+// dec_sample_embed_rows_p that also records the two log-probabilities of the drawn token at row_logp[b][YCOUNT][0..1]
+// (YCOUNT as read before the counters move: the index at which the token is appended to y).  Rows that return early
+// write nothing.  y, rstate, stop_idx, x and probs_out are those of dec_sample_embed_rows_p bit for bit: the sampler
+// runs the same instructions on the same values, the extra reductions only read the logits.
+__global__ __launch_bounds__(1024) void dec_sample_embed_rows_lp(evt_sample_params p,
+                                                                 const evt_row_sample* __restrict__ row_sample,
+                                                                 const float* __restrict__ logits, long* y, int* rstate,
+                                                                 const float* __restrict__ noise, int* stop_idx,
+                                                                 float* probs_out, const int* __restrict__ row_seed,
+                                                                 const int* __restrict__ row_mask, RowEmbed ea,
+                                                                 float* row_logp) {
+  const int b = blockIdx.x;
+  if (row_mask && !row_mask[b]) return;
+  int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
+  const evt_row_sample r = row_sample[b];   // uniform over the workgroup, see dec_sample_embed_rows_p
+  p.top_k = r.top_k;
+  p.top_p = r.top_p;
+  p.temperature = r.temperature;
+  p.repetition_penalty = r.repetition_penalty;
+  sample_embed_row<true>(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea, row_logp);
+}
+
 }  // namespace
 
 extern "C" {
@@ -186,6 +237,24 @@ int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample
   hipLaunchKernelGGL(dec_sample_embed_rows_p, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
                      (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
                      (const int*)row_mask, ea);
+  return evt_check_launch();
+}
+
+int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                 int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                 const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
+                                 int32_t npos, int32_t dpos, void* stream) {
+  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x ||
+      !row_logp || B <= 0 || E <= 0 || npos <= 0 || dpos < 0)
+    return EVT_EINVAL;
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
+  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  hipLaunchKernelGGL(dec_sample_embed_rows_lp, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
+                     (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
+                     (const int*)row_mask, ea, row_logp);
   return evt_check_launch();
 }
 

@@ -44,7 +44,8 @@ def synthesize_fragments(t2s, voice, batch_phones, all_phoneme_ids, all_bert_fea
 
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
-                      decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None):
+                      decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
+                      choose=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -53,9 +54,20 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     list with one token vector per fragment (fragments of several reference voices in one session).
     fragment_sampling: a list with one dict (keys out of top_k, top_p, temperature, repetition_penalty, early_stop_num)
     or None per fragment, replacing the values above for that fragment alone.  control: a StreamControl of
-    auto_reg/t2s_infer.py; a fragment cancelled through it is yielded as (index, None) and never reaches the s2 decoder."""
+    auto_reg/t2s_infer.py; a fragment cancelled through it is yielded as (index, None) and never reaches the s2 decoder.
+    candidates > 1: every fragment is decoded `candidates` times after one prompt pass (decode_stream's n, with
+    log-probabilities on) and choose(fragment_index, outputs) -- required then -- is called once all of them are in,
+    with the fragment's StreamOutputs in candidate order (a cancelled take has y = None); it returns the number of the
+    take to keep, and only that take goes through the s2 decoder.  A fragment whose takes were all cancelled is yielded
+    as (index, None) without a call.  The project ships no default rule: mean log-probability is no proven quality
+    criterion for this model (loops are likely sequences)."""
     model, dev = t2s.model, t2s.device
     n = len(all_phoneme_ids)
+    candidates = int(candidates)
+    if candidates < 1:
+        raise ValueError(f"candidates = {candidates} must be >= 1")
+    if candidates > 1 and choose is None:
+        raise ValueError("candidates > 1 needs choose(fragment_index, outputs) -> candidate number")
     if prompt_semantic is None:
         raise ValueError("synthesize_stream needs the prompt's semantic tokens")
     prompts = ([p.reshape(-1).to(dev) for p in prompt_semantic] if isinstance(prompt_semantic, (list, tuple))
@@ -67,6 +79,33 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         reqs = [q if fs is None else (*q, dict(fs)) for q, fs in zip(reqs, fragment_sampling)]
     refer = [r.to(dev) for r in refer_specs]
     kw = decode_kwargs or {}
+
+    def audio(r, y, idx):
+        with torch.no_grad():
+            sem = y[-idx:].unsqueeze(0).unsqueeze(0)
+            return voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]
+
+    if candidates > 1:
+        if int(slots) < candidates:
+            raise ValueError(f"slots = {int(slots)} cannot hold the {candidates} candidates of one fragment")
+        stream = model.decode_stream(reqs, slots=min(int(slots), max(n, 1) * candidates), top_k=top_k, top_p=top_p,
+                                     temperature=temperature, early_stop_num=t2s.early_stop_num,
+                                     repetition_penalty=repetition_penalty, control=control, n=candidates, logprobs=True,
+                                     **(sample_kwargs or {}))
+        takes = {}
+        for o in stream:
+            got = takes.setdefault(o.request, {})
+            got[o.candidate] = o
+            if len(got) < candidates:
+                continue
+            outs = [got[c] for c in range(candidates)]
+            del takes[o.request]
+            if all(t.y is None for t in outs):
+                yield o.request, None
+                continue
+            t = outs[int(choose(o.request, outs))]
+            yield o.request, (None if t.y is None else audio(o.request, t.y, t.idx))
+        return
     stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
                                  early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
                                  control=control, **(sample_kwargs or {}))

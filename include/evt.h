@@ -773,6 +773,20 @@ int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample
                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                 const float* alpha, float x_scale, float* x, int32_t B, int32_t E, int32_t npos,
                                 int32_t dpos, void* stream);
+/* evt_dec_sample_embed_rows_p that also writes, for every row it advances, two fp32 log-probabilities of the drawn
+ * token to row_logp[b][YCOUNT] (row_logp: device [B][ymax][2]; YCOUNT as it is BEFORE the launch, the index at which
+ * the token is appended to y[b]):
+ *   [0]  log_softmax of the raw logits[b] over the columns of that step (V - 1 while IDX < no_eos_steps, else V) at
+ *        the token: no repetition penalty, no nucleus / top-k cut, no temperature;
+ *   [1]  the log of the probability the token was drawn from after all of those, x - max - log(sum) of the values the
+ *        sampler's softmax is taken of (never -inf for a token that survived the cuts).
+ * A token outside [0, V) (NaN probabilities) gives NaN in both.  Idle, stopped and masked-out rows write nothing.  y,
+ * rstate, stop_idx, x and probs_out are those of evt_dec_sample_embed_rows_p bit for bit. */
+int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                 int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                 const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
+                                 int32_t npos, int32_t dpos, void* stream);
 
 /* ScaledAdam (src/easevoice/soundstorm/auto_reg/modules/optim.py:206-251,300-390,448-622) over a flat fp32 arena.
  * The reference stacks same-shaped tensors only to batch its torch ops; the arithmetic is per tensor, which is what

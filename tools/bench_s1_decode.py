@@ -14,6 +14,7 @@ time of both sessions with 32 rows alive for --tokens steps, and the prefill tim
     python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
     python tools/bench_s1_decode.py --stream [--stream-n 96]
     python tools/bench_s1_decode.py --stream --mixed 4      (per-request sampling parameters, see run_mixed)
+    python tools/bench_s1_decode.py --stream --candidates 4 --logprobs      (see run_candidates)
 """
 import argparse
 import json
@@ -115,6 +116,58 @@ def run_mixed(args, m, dev, x, bert, prompts):
                                    "all streams share one capacity and one session; the step graph is keyed by the "
                                    "noise table, so each uniform stream (own table) captures again, as a stream per "
                                    "parameter set did when the parameters were part of the key", **out)))
+
+
+def run_candidates(args, m, dev, x, bert, prompts):
+    """--candidates N and / or --logprobs.  (1) 32 slots alive for --tokens steps (32 // N requests with N candidates
+    each), log-probabilities off and -- with --logprobs -- on, alternated in one process: time per replay with the
+    prompt pass excluded.  (2) the admission of ONE request with N candidates (one prompt row copied into N slots)
+    against N single requests (N prompt rows).  One JSON line with prefill_rows, prefill_s and the per-replay times."""
+    lives, xs, berts, pr, _noise, _kw, g = _stream_workload(args, dev, x, bert, prompts)
+    N, T = max(1, args.candidates), args.tokens
+    R = 32 // N
+    infer = m._infer()
+    nz = torch.empty(T + 2, R, N, 1025).exponential_(1, generator=g)
+    nz[..., 1024] = 1e30
+    nz = nz.to(dev)
+    kw = dict(top_k=15, top_p=1, early_stop_num=T, repetition_penalty=1.35)
+    reqs = [(xs[r], berts[r], pr[r]) for r in range(R)]
+    modes = [False, True] if args.logprobs else [False]
+    runs = {lp: [] for lp in modes}
+    for rep in range(args.reps + 1):
+        for lp in modes:                       # alternated: both see the same state of the device
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = list(m.decode_stream(reqs, slots=R * N, n=N, logprobs=lp, noise=nz, **kw))
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            st = infer.stream_stats
+            assert len(outs) == R * N and all(o[1].numel() == args.prompt + T for o in outs)
+            runs[lp].append(dict(seconds=t, prefill_s=sum(st["prefill_s"]), steps=st["steps"],
+                                 prefill_rows=list(st["prefill_rows"]), admitted=list(st["admitted"])))
+    out = {}
+    for lp in modes:
+        rs = runs[lp][1:]
+        out["logprobs_on" if lp else "logprobs_off"] = dict(
+            prefill_rows=rs[0]["prefill_rows"], admitted=rs[0]["admitted"],
+            prefill_s=[round(r["prefill_s"], 5) for r in rs],
+            us_per_replay_all_runs=[round(1e6 * (r["seconds"] - r["prefill_s"]) / r["steps"], 1) for r in rs])
+    if args.logprobs:
+        med = lambda k: _median(out[k]["us_per_replay_all_runs"])
+        out["logprobs_on_over_off"] = round(med("logprobs_on") / med("logprobs_off"), 4)
+    # ---- admission: one request with N candidates against N single requests ----
+    adm = {}
+    for name, rq, n, tab in (("one_request_n", reqs[:1], N, nz[:, :1].contiguous()),
+                             ("n_single_requests", [reqs[0]] * N, 1, nz[:, 0].contiguous())):
+        ms = []
+        for rep in range(4):
+            list(m.decode_stream([(*q, 1) for q in rq], slots=N, n=n, noise=tab, logprobs=args.logprobs, **kw))
+            ms.append(1e3 * infer.stream_stats["prefill_s"][0])
+        adm[name] = dict(prefill_ms=round(min(ms[1:]), 3), prefill_rows=infer.stream_stats["prefill_rows"],
+                         admitted=infer.stream_stats["admitted"])
+    out["admission"] = adm
+    print(json.dumps(dict(workload=f"s1 decode stream, {R} requests x {N} candidates alive for {T} steps, "
+                                   f"x_len<={args.x_len}, prompt={args.prompt}, {args.dtype}, {R * N} slots", **out)))
 
 
 def run_stream(args, m, dev, x, bert, prompts):
@@ -228,6 +281,11 @@ def main():
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="with --stream: request r samples with parameter set r %% N; one session holding all sets "
                          "against N uniform streams run one after the other (nothing else)")
+    ap.add_argument("--candidates", type=int, default=0, metavar="N",
+                    help="with --stream: 32 // N requests with N candidates each in one session, and the admission of "
+                         "one request with N candidates against N single requests (nothing else)")
+    ap.add_argument("--logprobs", action="store_true",
+                    help="with --stream: time per replay with per-token log-probabilities on against off (nothing else)")
     args = ap.parse_args()
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
@@ -252,6 +310,10 @@ def main():
         if args.mixed:
             assert 1 <= args.mixed <= 8, args.mixed
             run_mixed(args, m, dev, x, bert, prompts)
+            return
+        if args.candidates or args.logprobs:
+            assert 0 <= args.candidates <= 32, args.candidates
+            run_candidates(args, m, dev, x, bert, prompts)
             return
         run_stream(args, m, dev, x, bert, prompts)
         return
