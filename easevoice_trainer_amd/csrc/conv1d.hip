@@ -34,7 +34,7 @@ extern "C" int evt_small_kind(const evt_conv1d_params* c);
 extern "C" int evt_cout1_fwd(const evt_conv1d_params* c, const void* x, const void* w_reg, const float* bias, void* y,
                              void* stream);
 extern "C" int evt_cout1_bwd_weight(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
-                                    float* ws, long ws_floats, void* stream);
+                                    float* dbias, float* ws, long ws_floats, void* stream);
 extern "C" int evt_cin1_bwd_weight(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
                                    float* dbias, float* ws, long ws_floats, void* stream);
 extern "C" int evt_cin1_fwd(const evt_conv1d_params* c, const void* x, const void* w_reg, const float* bias, void* y,
@@ -1437,7 +1437,8 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
   const bool ring_w = !deep_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_ring_eligible(p, c->dtype);
   // dbias is fused into the bf16 MFMA weight-gradient kernel when its A operand is dy (plain Conv1d)
   const bool cin1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 2;   // fuses dbias as well
-  const bool fuse_bias = dbias && ((igemm_path && c->dtype == EVT_DT_HALF && !c->transposed) || cin1);
+  const bool cout1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 1;  // and so does the dot-product conv
+  const bool fuse_bias = dbias && ((igemm_path && c->dtype == EVT_DT_HALF && !c->transposed) || cin1 || cout1);
   float* ws = sp ? sp->ws : nullptr;
   const long ws_floats = sp ? (long)sp->ws_floats : 0;
   if (dbias && !fuse_bias) {
@@ -1479,7 +1480,7 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
     evt_set_last_tag("grouped_bwd_weight");
     return evt_grouped_bwd_weight(c, x, dy, y, dw, stream);
   }
-  if (c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 1) return evt_cout1_bwd_weight(c, x, dy, y, dw, ws, ws_floats, stream);
+  if (cout1) return evt_cout1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
   if (cin1) return evt_cin1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
   const bool use_igemm = igemm_path;
   if (c->impl == EVT_IMPL_IGEMM && !use_igemm) return EVT_ENOTSUP;

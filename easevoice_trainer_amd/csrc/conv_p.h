@@ -85,6 +85,8 @@ bool wgrad_halo_eligible(const WgP& p, int dtype);
 int launch_wgrad_halo(const WgP& p, hipStream_t st);
 // fold.hip: out[e] += sum over b < nb of part[b * stride + e], e < n, rows added in a fixed order
 int launch_fold_partials(const float* part, long stride, int nb, float* out, long n, hipStream_t st);
+// the same with a second result behind the first in every row: out2[e] += sum over b of part[b * stride + n + e], e < n2
+int launch_fold_partials2(const float* part, long stride, int nb, float* out, long n, float* out2, long n2, hipStream_t st);
 // how the launchers split the positions: nsplit and stages per split from the stage count, the tile count and p.parts
 // (classic mode: `target` blocks; slab mode: additionally nsplit <= parts)
 void wgrad_pick_split(const WgP& p, long tiles, int nstages, long target, int min_stages, int* nsplit, int* per);

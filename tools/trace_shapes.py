@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.set_defaults(dump_outputs=None)      # bench.run_s2 reads it
     args = ap.parse_args()
     import bench
     from easevoice_trainer_amd.hip import conv as HC
