@@ -17,7 +17,11 @@ Same token sequence as the reference for the same sampling noise; a different ex
     row as well (a device table next to the counters), so requests of one session may differ in them, one captured graph
     serves every parameter set, and a request can be cancelled between two polls (StreamControl).  A request may ask
     for n candidates: one prompt pass, n slots, n noise lanes; with logprobs=True the sampler also writes the model's and
-    the sampler's log-probability of every drawn token (evt_dec_sample_embed_rows_lp).
+    the sampler's log-probability of every drawn token (evt_dec_sample_embed_rows_lp).  A request may carry a forced
+    prefix ("force": its first f tokens are given, not drawn -- evt_dec_sample_embed_rows_f) and its own noise seed
+    ("seed"); StreamControl.preempt(r) takes a running row out of its slot with the tokens it has, and the two keys
+    continue it exactly, here or in another stream; score_stream forces whole sequences and returns their
+    log-probabilities.
 The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
 import collections
 import ctypes as C
@@ -146,7 +150,7 @@ class DecodeSession:
 
 
 ROW_WORDS = 8             # include/evt.h EVT_ROW_*
-ROW_POS, ROW_IDX, ROW_YCOUNT, ROW_YLEN, ROW_LIMIT, ROW_STATUS, ROW_NOISE = range(7)
+ROW_POS, ROW_IDX, ROW_YCOUNT, ROW_YLEN, ROW_LIMIT, ROW_STATUS, ROW_NOISE, ROW_NFORCE = range(8)
 ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 
 
@@ -159,14 +163,19 @@ StreamOutput = collections.namedtuple("StreamOutput", "request y idx candidate l
 
 
 class StreamControl:
-    """handle of a running decode_stream for the caller that consumes it: cancel(r) withdraws request r.  It only
-    records the index; the stream acts at its next poll, so the caller cancels between two next() calls (one thread)."""
+    """handle of a running decode_stream for the caller that consumes it: cancel(r) withdraws request r, preempt(r)
+    takes it out of its slot and hands out the tokens it has so far (decode_stream).  Either only records the index; the
+    stream acts at its next poll, so the caller calls them between two next() calls (one thread)."""
 
     def __init__(self):
         self.cancelled = set()
+        self.preempted = set()
 
     def cancel(self, r):
         self.cancelled.add(int(r))
+
+    def preempt(self, r):
+        self.preempted.add(int(r))
 
 
 class StreamSession:
@@ -197,6 +206,7 @@ class StreamSession:
         self.row_sample = z(B, 4, dt=torch.int32)                 # evt_row_sample [B]: top_k, then the bits of 3 floats
         self.mask = z(B, dt=torch.int32)                          # rows of an admission's step 0
         self.logp, self.lp_on = None, False                       # [B][ymax][2] of a logprobs=True stream, made on demand
+        self.force_on = False                                     # a stream with forced requests: the _f sampler launch
         self.noise_cands = 1                                      # C of an injected [steps][R][C][V] noise table
         self.graph, self.graph_key = None, None
 
@@ -220,7 +230,17 @@ class StreamSession:
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
         (each row's workgroup owns its counters); `mask` restricts it to the rows of an admission.  top_k, top_p,
         temperature and repetition_penalty of a row come from row_sample[b]; `sp` carries the session-wide rest.  A
-        stream with logprobs=True launches the variant that also fills logp[b][YCOUNT]"""
+        stream with logprobs=True launches the variant that also fills logp[b][YCOUNT]; a stream with forced requests
+        launches the one that takes the token of a row's forced steps from y (with or without logp)"""
+        if self.force_on:
+            L.check(L.lib().evt_dec_sample_embed_rows_f(
+                C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
+                L.ptr(self.stop), None,
+                L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
+                C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa),
+                L.ptr(self.logp) if self.lp_on else None, self.B, self.E, pe.size(0), dpos, L.stream_ptr()),
+                "evt_dec_sample_embed_rows_f")
+            return
         if self.lp_on:
             L.check(L.lib().evt_dec_sample_embed_rows_lp(
                 C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
@@ -510,7 +530,7 @@ class T2SInfer:
 
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
                       early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
-                      control=None, n=1, logprobs=False):
+                      control=None, n=1, logprobs=False, forced=False):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
         (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
         content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
@@ -540,7 +560,27 @@ class T2SInfer:
         3-tuples, exactly n per request (y = idx = logprobs = None for a cancelled candidate); logprobs is None when
         not asked for, else fp32 [last + 1, 2]: rows 0 .. len(y) - prompt_len - 1 belong to y[prompt_len:], the last
         row to the step that stopped the candidate.  A lazy iterable fixes the form when it is opened: there a
-        request's own "n" > 1 needs logprobs=True or a session-wide n > 1."""
+        request's own "n" > 1 needs logprobs=True or a session-wide n > 1.
+
+        A request's dict may also carry
+          "force": a 1-D integer tensor or list of f >= 1 tokens that the request's first f steps TAKE instead of
+            drawing (all n candidates: n continuations of one given prefix).  The step index counts through them, so
+            step f reads noise row f.  A forced step stops the row only when its given token is EOS (allowed at the
+            last position alone, never at position 0: step 0 has no EOS column); the model's arg-max is not asked.
+            With logprobs=True a forced step reports the model's log-probability of the given token and the log of
+            the probability the sampler would have drawn it from (-inf when the sampler had cut it).  A token outside
+            [0, V), a misplaced EOS, f above the request's step limit or the session's capacity raise EvtError naming
+            the request.  A stream with any forced request runs evt_dec_sample_embed_rows_f; a list is inspected as a
+            whole, a lazy iterable says forced=True when it is opened (else a drawn request with "force" is refused).
+          "seed": an int s -- the row draws the built-in noise of (s & 0x7FFFFFFF, lane 0) -- or a pair (s, lane) with
+            lane in 0..3; candidate c adds 4c to the lane as ever.  (S + 4 * (r0 // 4), r0 % 4) draws what request r0
+            of a stream seeded S draws, whatever the request's own index, slot or admission time.
+        control.preempt(r): at the next poll every running, unfinished candidate of r is set idle as by cancel, but is
+        yielded with what it has: y = the row's prompt and tokens so far, idx = None (idx None with y not None marks a
+        preempted row), logprobs = those of the steps taken.  A candidate that finished at that poll is delivered, a
+        request still waiting at that poll is yielded as cancelled when its turn comes.  Submitting
+        (x, bert, prompt, {"force": y[len(prompt):], "seed": ...}) to this or a later stream continues the row exactly
+        where it was."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
         if not 1 <= int(slots) <= self.WIDE_ROWS:
@@ -566,19 +606,61 @@ class T2SInfer:
 
         base = dict(zip(SAMPLE_KEYS, (top_k, top_p, temperature, repetition_penalty)))
         base_v = self._sampling(top_k, top_p, temperature, repetition_penalty, "decode_stream")
+        forced, V, eos = bool(forced), self.model.vocab_size, self.model.EOS
+        cap_steps = []          # the step capacity of a lazy stream, known before its first request is drawn
+
+        def force_of(v, who, lim):
+            try:
+                t = torch.as_tensor(v).detach().cpu()
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise L.EvtError(f"{who}: force is no token vector ({e})") from None
+            if t.dim() != 1 or t.numel() < 1 or t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
+                raise L.EvtError(f"{who}: force must be a 1-D integer vector of at least one token")
+            t = t.long()
+            f = t.numel()
+            bad = ((t < 0) | (t >= V)).nonzero()
+            if bad.numel():
+                j = int(bad[0])
+                raise L.EvtError(f"{who}: force[{j}] = {int(t[j])} is outside [0, {V})")
+            at = (t == eos).nonzero().reshape(-1).tolist()
+            if at and at[0] == 0:
+                raise L.EvtError(f"{who}: force[0] is EOS ({eos}), but step 0 has no EOS column")
+            if at and at[0] != f - 1:
+                raise L.EvtError(f"{who}: force[{at[0]}] is EOS ({eos}) before the last position {f - 1}")
+            if f > lim:
+                raise L.EvtError(f"{who}: {f} forced tokens, but the request's step limit is {lim}")
+            if cap_steps and f > cap_steps[0]:
+                raise L.EvtError(f"{who}: {f} forced tokens, but the session's capacity is {cap_steps[0]} steps")
+            return t
+
+        def seed_of(v, who):
+            pair = v if isinstance(v, (tuple, list)) else (v, 0)
+            try:
+                if len(pair) != 2 or any(isinstance(e, bool) for e in pair):
+                    raise TypeError("expected an int or a pair (seed, lane) of ints")
+                sd, lane = operator.index(pair[0]), operator.index(pair[1])
+            except TypeError as e:
+                raise L.EvtError(f"{who}: seed = {v!r} is not an integer or (integer, lane) ({e})") from None
+            if not 0 <= lane < self.MAX_ROWS:
+                raise L.EvtError(f"{who}: seed lane = {lane} must be 0..{self.MAX_ROWS - 1}")
+            return sd & 0x7FFFFFFF, lane
 
         def norm(r, req):
             if len(req) not in (3, 4):
                 raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num or dict])")
             x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
             opt, samp, nr = req[3] if len(req) == 4 else None, base_v, base_n
+            force = own_seed = None
             if isinstance(opt, dict):
-                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num", "n"})
+                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num", "n", "force", "seed"})
                 if unknown:
                     raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)}, "
-                                     "early_stop_num and n)")
+                                     "early_stop_num, n, force and seed)")
                 if "n" in opt:
                     nr = candidates(opt["n"], f"request {r}")
+                force = opt.get("force")
+                if opt.get("seed") is not None:
+                    own_seed = seed_of(opt["seed"], f"request {r}")
                 samp = self._sampling(*({**base, **{k: v for k, v in opt.items() if k in SAMPLE_KEYS}}[k]
                                         for k in SAMPLE_KEYS), f"request {r}")
                 opt = opt.get("early_stop_num")
@@ -597,7 +679,12 @@ class T2SInfer:
             if lazy and nr > 1 and not (logprobs or base_n > 1):
                 raise L.EvtError(f"request {r}: n = {nr} in a lazy stream needs logprobs=True or a session-wide n > 1 "
                                  "(the form of the outputs is fixed when the stream is opened)")
-            return r, x, bert, prompt, lim, samp, nr
+            if force is not None:
+                if lazy and not forced:
+                    raise L.EvtError(f"request {r}: \"force\" in a lazy stream needs decode_stream(..., forced=True) "
+                                     "(the sampler launch is fixed when the stream is opened)")
+                force = force_of(force, f"request {r}", lim)
+            return r, x, bert, prompt, lim, samp, nr, force, own_seed
 
         rich = logprobs or base_n > 1
         if not lazy:
@@ -605,6 +692,7 @@ class T2SInfer:
             if not reqs:
                 return iter(())
             rich = rich or any(q[6] > 1 for q in reqs)
+            forced = forced or any(q[7] is not None for q in reqs)
             Xmax = int(max_text_len) if max_text_len is not None else max(q[1].numel() for q in reqs)
             Pmax = int(max_prompt_len) if max_prompt_len is not None else max(q[3].numel() for q in reqs)
             n_max = max(q[4] for q in reqs)
@@ -620,9 +708,38 @@ class T2SInfer:
             if nsteps is not None:
                 n_max = min(n_max, nsteps)
             cap = (int(max_text_len), int(max_prompt_len), n_max)
+            cap_steps.append(n_max)
             it = (norm(r, q) for r, q in enumerate(requests))
         return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
-                            max(1, int(poll)), control, logprobs, rich)
+                            max(1, int(poll)), control, logprobs, rich, forced)
+
+    def score_stream(self, requests, tokens, slots=32, append_eos=False, **sampling):
+        """Log-probabilities of GIVEN tokens: request r = (x, bert, prompt[, opt]) is forced over all of tokens[r] (a 1-D
+        integer vector; append_eos=True adds EOS behind it), limited to exactly that many steps, with logprobs=True.
+        Yields (r, logprobs) in completion order, logprobs fp32 [f, 2]: per given token the model's log-probability and
+        the log of the probability the sampler would have drawn it from under the request's sampling values (-inf where
+        the sampler cuts the token).  No noise value can change a forced row, so `seed` / `noise` do not matter; the
+        other keywords are decode_stream's.  A thin wrapper over decode_stream: the sequence is scored by the decode
+        steps themselves, one token per step, with the sampler's own arithmetic."""
+        eos = self.model.EOS
+
+        def forced_requests():
+            for r, (req, tok) in enumerate(zip(requests, tokens)):
+                try:
+                    t = torch.as_tensor(tok).detach().cpu().reshape(-1)
+                except (TypeError, ValueError, RuntimeError) as e:
+                    raise L.EvtError(f"request {r}: tokens are no vector ({e})") from None
+                if append_eos and not t.is_floating_point():
+                    t = torch.cat([t.long(), torch.tensor([eos])])
+                opt = req[3] if len(req) == 4 else None
+                opt = dict(opt) if isinstance(opt, dict) else {}
+                opt.update(force=t, early_stop_num=max(0, t.numel() - 1))      # _limit: exactly t.numel() steps
+                yield (req[0], req[1], req[2], opt)
+
+        lazy = not isinstance(requests, (list, tuple))
+        reqs = forced_requests() if lazy else list(forced_requests())
+        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, **sampling):
+            yield o.request, o.logprobs
 
     @staticmethod
     def _fits(q, cap):
@@ -632,7 +749,8 @@ class T2SInfer:
                              f"session's capacity (text {cap[0]}, prompt {cap[1]}, {cap[2]} steps)")
 
     @torch.no_grad()
-    def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs=False):
+    def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs=False,
+                     forced=False):
         """session, weights, sampling parameters and the captured step graph; every slot idle"""
         m = self.model
         cd = m.cd
@@ -648,7 +766,7 @@ class T2SInfer:
             assert noise.size(-1) == m.vocab_size
         S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev)
         S.reset()
-        S.lp_on, S.noise_cands = bool(logprobs), cands
+        S.lp_on, S.noise_cands, S.force_on = bool(logprobs), cands, bool(forced)
         if S.lp_on and S.logp is None:
             S.logp = torch.zeros(S.B, S.ymax, 2, dtype=torch.float32, device=dev)
         sp = L.SampleParams(S.V, m.EOS, int(top_k) if top_k is not None else 0, 1, S.ymax, float(top_p),
@@ -663,6 +781,8 @@ class T2SInfer:
                 None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W))
         if S.lp_on:      # another sampler kernel in the graph; a session without it keeps the key it always had
             gkey = gkey + ("logprobs",)
+        if S.force_on:   # likewise: the sampler launch with forced steps
+            gkey = gkey + ("force",)
         captured = False
         if use_graph and S.graph_key != gkey:
             # every slot is idle here: the warm-up and the capture move no counter and write no cache line, so there is
@@ -681,8 +801,8 @@ class T2SInfer:
 
     @torch.no_grad()
     def _admit(self, S, W, sp, pe, noise, batch, seeds):
-        """batch: [(slots, (r, x, bert, prompt, limit, sampling, n))], `slots` the n slots of the request's candidates in
-        candidate order.  The prompt pass of _decode for these requests only, ONE row per request (texts padded to Xmax,
+        """batch: [(slots, (r, x, bert, prompt, limit, sampling, n, force, seed))], `slots` the n slots of the request's
+        candidates in candidate order.  The prompt pass of _decode for these requests only, ONE row per request (texts padded to Xmax,
         prompts to the longest of them); each row's keys/values go into the cache slabs of all its slots, then the row
         state of every slot and step 0 for those slots: logits of the last prompt position and a masked sample."""
         m = self.model
@@ -693,7 +813,7 @@ class T2SInfer:
         x_lens = [int(q[1].numel()) for _s, q in batch]
         Pk = max(y_lens)
         rows, prs = [], []
-        for _slots, (_r, x, bert, prompt, _lim, _samp, _n) in batch:
+        for _slots, (_r, x, bert, prompt, *_rest) in batch:
             x, bert = x.to(dev), bert.to(dev)
             xe = m.ar_text_embedding(x.unsqueeze(0))
             xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
@@ -728,11 +848,14 @@ class T2SInfer:
         # dimension flattened ([steps][R * C][V], _stream_open), C = S.noise_cands: column r * C + c
         C_ = S.noise_cands
         ncol = (lambda r, c: 0) if noise is None or noise.dim() == 2 else (lambda r, c: r * C_ + c)
-        rs = [[Xmax + y_lens[i], 0, y_lens[i], y_lens[i], q[4], ROW_RUNNING, ncol(q[0], c), 0] for i, c, q in per]
+        # word 7: the row's forced steps; their tokens go behind the prompt in y, where the sampler launch finds them
+        rs = [[Xmax + y_lens[i], 0, y_lens[i], y_lens[i], q[4], ROW_RUNNING, ncol(q[0], c),
+               0 if q[7] is None else q[7].numel()] for i, c, q in per]
         S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
         S.stop[slots_t] = -1
         # candidate c draws lane r % 4 + 4c of the request's group seed (the hash folds the lane in as lane << 16)
-        S.row_seed[slots_t] = torch.tensor([[seeds(q[0])[0], seeds(q[0])[1] + self.MAX_ROWS * c] for _i, c, q in per],
+        own = [q[8] if q[8] is not None else seeds(q[0]) for _i, _c, q in per]      # a request's own (seed, lane)
+        S.row_seed[slots_t] = torch.tensor([[sd, lane + self.MAX_ROWS * c] for (sd, lane), (_i, c, _q) in zip(own, per)],
                                            dtype=torch.int32).to(dev)
         tab = torch.tensor([[0.0, *q[5][1:]] for _i, _c, q in per], dtype=torch.float32)
         tab.view(torch.int32)[:, 0] = torch.tensor([q[5][0] for _i, _c, q in per], dtype=torch.int32)
@@ -740,6 +863,9 @@ class T2SInfer:
         S.x_lens[slots_t] = spread(xl)
         S.y[slots_t] = 0
         S.y[slots_t, :Pk] = spread(pr)
+        for (sl, q), P in zip(batch, y_lens):
+            if q[7] is not None:
+                S.y[torch.tensor(sl, device=dev), P:P + q[7].numel()] = q[7].to(dev)
         S.mask.zero_()
         S.mask[slots_t] = 1
         # ---- step 0 of the admitted rows (the other rows' xb / logits are dead between two steps) ----
@@ -748,7 +874,7 @@ class T2SInfer:
         S._sample_embed(W, sp, noise, pe, 0, S.mask)
 
     def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None,
-                logprobs=False, rich=False):
+                logprobs=False, rich=False, forced=False):
         G, draws = self.MAX_ROWS, []
 
         def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
@@ -762,6 +888,8 @@ class T2SInfer:
                                          graph_captured=False)
         free, running, S, exhausted = list(range(slots)), {}, None, False
         cancelled = control.cancelled if control is not None else ()
+        preempted = getattr(control, "preempted", ()) if control is not None else ()
+        due = set()            # preempt() calls seen at a poll so far: a request still waiting then comes back as cancelled
         out = (lambda r, y, idx, c, lp: StreamOutput(r, y, idx, c, lp)) if rich else (lambda r, y, idx, c, lp: (r, y, idx))
         head = None            # the request at the head of the queue, drawn but still waiting for its n slots
         while True:
@@ -775,7 +903,7 @@ class T2SInfer:
                         break
                     self._fits(head, cap)
                 q = head
-                if q[0] in cancelled:            # withdrawn while it waited: no prompt pass, no slot
+                if q[0] in cancelled or q[0] in due:     # withdrawn while it waited: no prompt pass, no slot
                     head = None
                     stats["events"].append(("cancel", stats["steps"], q[0], None))
                     for c in range(q[6]):
@@ -789,7 +917,7 @@ class T2SInfer:
                 dev = batch[0][1][1].device
                 if S is None:
                     S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
-                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs)
+                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced)
                 cuda = torch.device(dev).type == "cuda"
                 if cuda:
                     torch.cuda.synchronize(dev)
@@ -818,6 +946,7 @@ class T2SInfer:
             stats["steps"] += n
             st = S.state.tolist()                    # the only device->host read of the loop: status and stop of all rows
             done = []
+            due.update(preempted)
             for slot in sorted(running):
                 r, ylen, left, c = running[slot]
                 running[slot][2] = max(0, left - n)
@@ -827,20 +956,27 @@ class T2SInfer:
                     # one pair per step 0..last, written at the index the step's token went to: y[ylen + step]
                     lp = S.logp[slot, ylen:ylen + last + 1].clone() if logprobs else None
                     done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last,
-                                 c, lp))
+                                 c, lp, "finish"))
                 elif r in cancelled:
                     # an ordinary write on the stream of the replays: the row's workgroups see IDLE from the next
                     # replay on and return at once, whatever an admission later makes of the slot
                     S.rstate[slot, ROW_STATUS] = ROW_IDLE
-                    done.append((slot, r, None, None, c, None))
+                    done.append((slot, r, None, None, c, None, "cancel"))
+                elif r in due:
+                    # idle as above; the row's tokens and log-probabilities up to the YCOUNT of this poll's state read
+                    # are cloned on the stream of the replays, before an admission can write the slot
+                    S.rstate[slot, ROW_STATUS] = ROW_IDLE
+                    yc = st[slot * ROW_WORDS + ROW_YCOUNT]
+                    lp = S.logp[slot, ylen:yc].clone() if logprobs else None
+                    done.append((slot, r, S.y[slot, :yc].clone(), None, c, lp, "preempt"))
             if n == 0 and not done:
                 raise L.EvtError("stream session: a row is past its step limit but not stopped")
-            for slot, r, y, idx, c, lp in done:
+            for slot, r, y, idx, c, lp, kind in done:
                 del running[slot]
                 free.append(slot)
-                stats["events"].append(("finish" if y is not None else "cancel", stats["steps"], r, slot))
+                stats["events"].append((kind, stats["steps"], r, slot))
             free.sort()
-            for slot, r, y, idx, c, lp in done:
+            for slot, r, y, idx, c, lp, kind in done:
                 yield out(r, y, idx, c, lp)
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,

@@ -273,3 +273,6 @@ class Text2SemanticDecoder(nn.Module):
 
     def decode_stream(self, requests, **kwargs):
         return self._infer().decode_stream(requests, **kwargs)
+
+    def score_stream(self, requests, tokens, **kwargs):
+        return self._infer().score_stream(requests, tokens, **kwargs)

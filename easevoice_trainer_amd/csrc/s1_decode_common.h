@@ -185,11 +185,15 @@ constexpr int kSortN = 2048;
 // kLp (dec_sample_embed_rows_lp only): the thread that owns the token also stores log(pr[token]) to *slp (LDS), as
 // x - max - log(sum) of the values pr is the softmax of, so a surviving token never underflows to -inf; the caller reads
 // it after a barrier.  With kLp = false the function is the one every other sampler kernel has always compiled.
-template <bool kLp = false>
+// kForce (dec_sample_embed_rows_f only): `ftok` >= 0 is a token GIVEN for this step (the same value on every thread of
+// the workgroup); the draw runs as ever and is returned, but the log-probability stored to *slp is that of column ftok,
+// reported by the thread that owns the column whether or not it won the arg-max: -inf when the sampler had cut it.
+// ftok < 0 (no given token) and kForce = false leave every instruction as it was.
+template <bool kLp = false, bool kForce = false>
 __device__ __forceinline__ int sample_row(const evt_sample_params& p, const float* __restrict__ lg, const long* yb,
                                           int idx, int ycount, unsigned nseed, unsigned nlane,
                                           const float* __restrict__ q_row, float* probs_row, int* amax_out,
-                                          float* slp = nullptr) {
+                                          float* slp = nullptr, int ftok = -1) {
   __shared__ float sv[kSortN];
   __shared__ int si[kSortN];
   __shared__ float cur[kSortN];
@@ -308,9 +312,13 @@ __device__ __forceinline__ int sample_row(const evt_sample_params& p, const floa
   const int tok = block_argmax(best, besti, redv, redi, 16);
   if constexpr (kLp) {
     const float ls = logf(sum);
+    int own = tok;
+    if constexpr (kForce) {
+      if (ftok >= 0) own = ftok;
+    }
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      if (tid + u * 1024 == tok) *slp = x0[u] - mx - ls;
+      if (tid + u * 1024 == own) *slp = x0[u] - mx - ls;
   }
   *amax_out = amax;
   return tok;

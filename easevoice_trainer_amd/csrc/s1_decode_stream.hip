@@ -15,6 +15,9 @@
 //   dec_sample_embed_rows_lp is that launch again, which also writes the step's two log-probabilities of the drawn token
 //                          to row_logp[b][YCOUNT]: log_softmax of the raw logits (the model's) and the log of the
 //                          probability it was drawn from after penalty, nucleus, top-k and temperature (the sampler's).
+//   dec_sample_embed_rows_f is the _p / _lp launch (without / with row_logp) in which a row may have FORCED steps: while
+//                          IDX < rstate[b][NFORCE] the row's token is the one the host wrote at y[b][YCOUNT], not the
+//                          draw -- scoring a given take, resuming a preempted row, continuing a given prefix.
 // A row that stops (EOS, or its limit) is marked in the same launch and is skipped from then on: however late the host
 // reads the status, a stopped row never advances its position or writes past its buffers.
 // The counters are written with ordinary stores by thread 0 of the row's workgroup after a barrier.
@@ -57,7 +60,9 @@ struct RowEmbed { const float* emb; const float* pe; const float* alpha; float* 
 // sampling parameters: the session-wide one, or that copy with the row's four values written over it.  kLp is a
 // compile-time switch, so the two kernels without log-probabilities compile the body they always had; with it, the raw
 // logits get a block_max / block_sum of their own before the sampler touches anything, and thread 0 adds two stores.
-template <bool kLp = false>
+// kForce is a second such switch (dec_sample_embed_rows_f): in a step with IDX < rstate[b][NFORCE] the token is the
+// one found at yb[ycount] and the arg-max EOS rule is off; without it the body is the one compiled before.
+template <bool kLp = false, bool kForce = false>
 __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, const float* __restrict__ logits, long* y,
                                                  int* rs, const float* __restrict__ noise, int* stop_idx,
                                                  float* probs_out, const int* __restrict__ row_seed, const RowEmbed& ea,
@@ -67,6 +72,18 @@ __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, con
   int col = rs[EVT_ROW_NOISE];
   if (col < 0 || col >= p.noise_rows) col = 0;
   long* yb = y + (long)b * p.ymax;
+  // A forced step takes its token from the row's own y buffer.  rs and yb are addressed by blockIdx.x alone and idx,
+  // ycount are the same words on every thread, so `given` is uniform over the workgroup; it decides no barrier anyway
+  // (it selects which column's log-probability is reported, and the token after the draw).  The value becomes an index
+  // of the embedding table and of the logits: anything outside [0, V) is replaced by the marker the all-NaN arg-max
+  // leaves (0x7fffffff), which is stored for the host to see, embeds row 0 and reports NaN log-probabilities.
+  int given = -1;
+  if constexpr (kForce) {
+    if (idx < rs[EVT_ROW_NFORCE] && ycount >= 0 && ycount < p.ymax) {
+      const long t = yb[ycount];
+      given = t >= 0 && t < V ? (int)t : 0x7fffffff;
+    }
+  }
   int amax;
   float rmax = -INFINITY, rlsum = 0.f;   // max and log(sum exp(. - max)) of the raw logits over this step's Ve columns
   float* lpsh = nullptr;                 // LDS word for the sampler's log-probability; only the kLp kernel has it
@@ -81,10 +98,13 @@ __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, con
     rlsum = logf(block_sum(rlsum, lp_lds, 16));
     if (tid == 0) lpsh[0] = NAN;   // stays when no thread owns the token (all-NaN probabilities)
   }
-  const int tok = sample_row<kLp>(p, logits + (long)b * V, yb, idx, ycount, (unsigned)row_seed[2 * b],
-                                  (unsigned)row_seed[2 * b + 1],
-                                  noise ? noise + ((long)idx * p.noise_rows + col) * V : nullptr,
-                                  probs_out ? probs_out + (long)b * V : nullptr, &amax, lpsh);
+  int tok = sample_row<kLp, kForce>(p, logits + (long)b * V, yb, idx, ycount, (unsigned)row_seed[2 * b],
+                                    (unsigned)row_seed[2 * b + 1],
+                                    noise ? noise + ((long)idx * p.noise_rows + col) * V : nullptr,
+                                    probs_out ? probs_out + (long)b * V : nullptr, &amax, lpsh, given);
+  if constexpr (kForce) {
+    if (given >= 0) tok = given;   // the draw is dropped; everything below sees the given token
+  }
   // x_next = emb[token] * x_scale + alpha * pe[y_len + idx]  (t2s_model.py:860-861)
   int ppos = ylen + idx;
   if (ppos >= ea.npos) ppos = ea.npos - 1;
@@ -106,9 +126,16 @@ __device__ __forceinline__ void sample_embed_row(const evt_sample_params& p, con
         float* o = row_logp + ((long)b * p.ymax + ycount) * 2;
         o[0] = ok ? logits[(long)b * V + tok] - rmax - rlsum : NAN;
         o[1] = ok ? lpsh[0] : NAN;
+        if constexpr (kForce) {   // a given token outside the step's Ve columns (EOS at a step without it): no mass
+          if (given >= 0 && ok && tok >= (idx < p.no_eos_steps ? V - 1 : V)) o[0] = -INFINITY;
+        }
       }
     }
-    if (amax == p.eos || tok == p.eos) {
+    bool by_amax = amax == p.eos;
+    if constexpr (kForce) {
+      if (given >= 0) by_amax = false;   // the given sequence decides where it ends, not the model's arg-max
+    }
+    if (by_amax || tok == p.eos) {
       stop_idx[b] = idx;
       rs[EVT_ROW_STATUS] = EVT_ROW_STOP_EOS;
     } else if (idx + 1 >= limit || ycount + 1 >= p.ymax) {
@@ -185,6 +212,32 @@ __global__ __launch_bounds__(1024) void dec_sample_embed_rows_lp(evt_sample_para
   sample_embed_row<true>(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea, row_logp);
 }
 
+// dec_sample_embed_rows_p (kLp = false, row_logp unused) or dec_sample_embed_rows_lp (kLp = true) with forced steps:
+// row b takes the token at y[b][YCOUNT] instead of its draw while IDX < rstate[b][EVT_ROW_NFORCE].  The step index
+// keeps counting through forced steps and keys the noise as ever, so the first sampled step after k forced ones reads
+// noise row k: a row resumed from a forced prefix draws what it would have drawn had it sampled that prefix itself.
+// NFORCE is read through rs (blockIdx.x alone), so the workgroup-uniformity argument of dec_sample_embed_rows_p holds:
+// no barrier of sample_row depends on it.  With NFORCE = 0 every value is that of the _p / _lp kernel bit for bit.
+template <bool kLp>
+__global__ __launch_bounds__(1024) void dec_sample_embed_rows_f(evt_sample_params p,
+                                                                const evt_row_sample* __restrict__ row_sample,
+                                                                const float* __restrict__ logits, long* y, int* rstate,
+                                                                const float* __restrict__ noise, int* stop_idx,
+                                                                float* probs_out, const int* __restrict__ row_seed,
+                                                                const int* __restrict__ row_mask, RowEmbed ea,
+                                                                float* row_logp) {
+  const int b = blockIdx.x;
+  if (row_mask && !row_mask[b]) return;
+  int* rs = rstate + b * EVT_ROW_WORDS;
+  if (rs[EVT_ROW_STATUS] != EVT_ROW_RUNNING) return;
+  const evt_row_sample r = row_sample[b];   // uniform over the workgroup, see dec_sample_embed_rows_p
+  p.top_k = r.top_k;
+  p.top_p = r.top_p;
+  p.temperature = r.temperature;
+  p.repetition_penalty = r.repetition_penalty;
+  sample_embed_row<kLp, true>(p, logits, y, rs, noise, stop_idx, probs_out, row_seed, ea, row_logp);
+}
+
 }  // namespace
 
 extern "C" {
@@ -255,6 +308,30 @@ int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sampl
   hipLaunchKernelGGL(dec_sample_embed_rows_lp, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
                      (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
                      (const int*)row_mask, ea, row_logp);
+  return evt_check_launch();
+}
+
+int evt_dec_sample_embed_rows_f(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
+                                int32_t npos, int32_t dpos, void* stream) {
+  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 ||
+      E <= 0 || npos <= 0 || dpos < 0)
+    return EVT_EINVAL;
+  // the forced tokens live in y, device memory: the host that writes them validates them, the kernel clamps them
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
+  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  if (row_logp)
+    hipLaunchKernelGGL(dec_sample_embed_rows_f<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample,
+                       logits, (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
+                       (const int*)row_mask, ea, row_logp);
+  else
+    hipLaunchKernelGGL(dec_sample_embed_rows_f<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample,
+                       logits, (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
+                       (const int*)row_mask, ea, row_logp);
   return evt_check_launch();
 }
 

@@ -28,7 +28,7 @@ class GemmEpilogue(C.Structure):
 
 
 class LinearSlot:
-    __slots__ = ("name", "weight", "bias", "N", "Np", "K", "layout", "reg", "alt", "bank", "_pcache")
+    __slots__ = ("name", "weight", "bias", "N", "Np", "K", "layout", "reg", "alt", "bank", "_pcache", "pad")
 
     def __init__(self, name, weight, bias, bank):
         self.name, self.weight, self.bias, self.bank = name, weight, bias, bank
@@ -37,6 +37,7 @@ class LinearSlot:
         if self.Np != self.N and bias is not None:
             raise L.EvtError(f"linear {name}: a padded output width ({self.N} -> {self.Np}) with a bias is not supported")
         self._pcache = {}
+        self.pad = None      # zero-padded [Np, K] copy the images are folded from, see LinearBank._tables
 
     def params(self, M, relu):
         p = self._pcache.get((M, relu))
@@ -56,8 +57,10 @@ class LinearSlot:
 
 class LinearBank:
     """Prepared weight images of a set of Linear weights.  `specs`: iterable of (name, weight Parameter [N, K], bias
-    Parameter [N] or None).  A weight whose N is padded (slot.Np > N) must sit in storage that is readable -- and zero
-    -- up to Np rows (runtime.ParamArena(reserve=...))."""
+    Parameter [N] or None).  The fold reads Np rows of a weight whose N is padded (slot.Np > N).  Inside an engine the
+    weight sits in storage that is readable -- and zero -- up to Np rows (runtime.ParamArena(reserve=...)) and is read
+    in place; a weight whose storage ends earlier (a bare model's own parameter) is folded from a zero-padded copy that
+    prepare() refreshes, so that no launch reads past an allocation."""
 
     def __init__(self, specs, dtype: torch.dtype, device):
         L.set_half(dtype)
@@ -135,7 +138,13 @@ class LinearBank:
         items, rows, groups = [], [], []
         for i, s in enumerate(self.slots):
             it = L.WPrepItem()
-            it.v, it.g = s.weight.data_ptr(), None
+            w = s.weight
+            if s.Np != s.N and w.untyped_storage().nbytes() // w.element_size() - w.storage_offset() < s.Np * s.K:
+                if s.pad is None or s.pad.device != w.device or s.pad.dtype != w.dtype:
+                    s.pad = torch.zeros(s.Np, s.K, dtype=w.dtype, device=w.device)
+            else:
+                s.pad = None
+            it.v, it.g = (w if s.pad is None else s.pad).data_ptr(), None
             it.reg, it.alt = s.reg.data_ptr(), s.alt.data_ptr()
             it.dw = it.dv = it.dg = None
             it.lay, it.dtype = s.layout, self.dt
@@ -161,6 +170,9 @@ class LinearBank:
             self._tables()
             force = True
         if force or self.dirty or stamp != self._stamp:
+            for s in self.slots:
+                if s.pad is not None:
+                    s.pad[:s.N].copy_(s.weight.detach())
             # groups of eight rows: both images leave as 16-byte pieces (csrc/elementwise.hip: wn_fold8_kernel)
             L.check(L.lib().evt_wn_fold_groups(L.ptr(self._items), L.ptr(self._groups), self._ngroups, L.stream_ptr()),
                     "evt_wn_fold_groups")

@@ -53,8 +53,11 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     speed_factor, while the other rows' tokens wait in the session.  prompt_semantic: [1, P] for all fragments, or a
     list with one token vector per fragment (fragments of several reference voices in one session).
     fragment_sampling: a list with one dict (keys out of top_k, top_p, temperature, repetition_penalty, early_stop_num)
-    or None per fragment, replacing the values above for that fragment alone.  control: a StreamControl of
-    auto_reg/t2s_infer.py; a fragment cancelled through it is yielded as (index, None) and never reaches the s2 decoder.
+    or None per fragment, replacing the values above for that fragment alone; the dicts go to decode_stream as they are,
+    so "seed" (the fragment's own noise seed) and "force" (given first tokens, e.g. those of a preempted take) work here
+    too.  control: a StreamControl of auto_reg/t2s_infer.py; a fragment cancelled through it is yielded as (index, None)
+    and never reaches the s2 decoder, and so is a fragment preempted through it (decode_stream hands out its partial
+    tokens with idx = None; a caller who wants to resume it drives decode_stream itself).
     candidates > 1: every fragment is decoded `candidates` times after one prompt pass (decode_stream's n, with
     log-probabilities on) and choose(fragment_index, outputs) -- required then -- is called once all of them are in,
     with the fragment's StreamOutputs in candidate order (a cancelled take has y = None); it returns the number of the
@@ -100,17 +103,17 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                 continue
             outs = [got[c] for c in range(candidates)]
             del takes[o.request]
-            if all(t.y is None for t in outs):
+            if all(t.y is None or t.idx is None for t in outs):
                 yield o.request, None
                 continue
             t = outs[int(choose(o.request, outs))]
-            yield o.request, (None if t.y is None else audio(o.request, t.y, t.idx))
+            yield o.request, (None if t.y is None or t.idx is None else audio(o.request, t.y, t.idx))
         return
     stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
                                  early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
                                  control=control, **(sample_kwargs or {}))
     for r, y, idx in stream:
-        if y is None:                      # cancelled: no tokens, no s2 decode
+        if y is None or idx is None:       # cancelled, or preempted with partial tokens: no s2 decode
             yield r, None
             continue
         with torch.no_grad():

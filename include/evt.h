@@ -740,7 +740,8 @@ int evt_dec_advance(int32_t* ctr, int32_t dpos, void* stream);
 #define EVT_ROW_LIMIT 4    /* the row stops after the step IDX == LIMIT - 1 at the latest */
 #define EVT_ROW_STATUS 5   /* EVT_ROW_IDLE | RUNNING | STOP_EOS | STOP_LIMIT */
 #define EVT_ROW_NOISE 6    /* column of an injected noise table [steps][noise_rows][V] this row reads */
-#define EVT_ROW_SPARE 7
+#define EVT_ROW_NFORCE 7   /* forced steps: while IDX < NFORCE, evt_dec_sample_embed_rows_f takes the token from y */
+#define EVT_ROW_SPARE EVT_ROW_NFORCE   /* the word's name while it was unused; the other entry points ignore it */
 #define EVT_ROW_IDLE 0
 #define EVT_ROW_RUNNING 1
 #define EVT_ROW_STOP_EOS 2
@@ -787,6 +788,24 @@ int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sampl
                                  const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                  const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
                                  int32_t npos, int32_t dpos, void* stream);
+/* evt_dec_sample_embed_rows_lp in which row_logp may be NULL (then it is evt_dec_sample_embed_rows_p) and a row may have
+ * FORCED steps.  With nforce = rstate[b][EVT_ROW_NFORCE], a step of row b with IDX < nforce takes its token from
+ * y[b][YCOUNT], where the caller has written it, instead of the sampler's draw.  Everything after the token is as ever:
+ * the append (which rewrites the value), x[b], the counters, the LIMIT test.  The row stops with STOP_EOS when the given
+ * token is eos; the arg-max rule is NOT applied in a forced step (the given sequence decides where it ends) and both
+ * rules apply again from step nforce on.  IDX counts through forced steps and keys the noise as ever, so the first
+ * sampled step after k forced ones reads noise row k (built-in noise: hash of IDX = k): a row forced over a prefix of
+ * what it once sampled continues exactly as it did.  row_logp of a forced step:
+ *   [0]  log_softmax of the raw logits over the step's columns at the given token (-inf for eos at a step without it);
+ *   [1]  the log of the probability the sampler would have drawn the token from after penalty, nucleus, top-k and
+ *        temperature: -inf when the sampler had cut it.
+ * A given token outside [0, V) is stored as 0x7fffffff, embeds row 0 and reports NaN; the caller validates what it
+ * writes.  A row with nforce = 0 is, in every bit, a row of evt_dec_sample_embed_rows_lp / _p. */
+int evt_dec_sample_embed_rows_f(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
+                                int64_t* y, int32_t* rstate, const float* noise, int32_t* stop_idx, float* probs_out,
+                                const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
+                                const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
+                                int32_t npos, int32_t dpos, void* stream);
 
 /* ScaledAdam (src/easevoice/soundstorm/auto_reg/modules/optim.py:206-251,300-390,448-622) over a flat fp32 arena.
  * The reference stacks same-shaped tensors only to batch its torch ops; the arithmetic is per tensor, which is what

@@ -15,6 +15,7 @@ time of both sessions with 32 rows alive for --tokens steps, and the prefill tim
     python tools/bench_s1_decode.py --stream [--stream-n 96]
     python tools/bench_s1_decode.py --stream --mixed 4      (per-request sampling parameters, see run_mixed)
     python tools/bench_s1_decode.py --stream --candidates 4 --logprobs      (see run_candidates)
+    python tools/bench_s1_decode.py --stream --force 64      (forced first tokens of every request, see run_force)
 """
 import argparse
 import json
@@ -170,6 +171,43 @@ def run_candidates(args, m, dev, x, bert, prompts):
                                    f"x_len<={args.x_len}, prompt={args.prompt}, {args.dtype}, {R * N} slots", **out)))
 
 
+def run_force(args, m, dev, x, bert, prompts):
+    """--force K: 32 slots alive for --tokens steps, every request with its first K tokens given ("force": the sampler
+    launch evt_dec_sample_embed_rows_f, K forced steps and --tokens - K sampled ones) against the same requests without
+    them (evt_dec_sample_embed_rows_p), alternated in one process: time per replay with the prompt pass excluded.  With
+    --logprobs both sides record log-probabilities (the forced launch against evt_dec_sample_embed_rows_lp)."""
+    _lives, xs, berts, pr, _noise, _kw, g = _stream_workload(args, dev, x, bert, prompts)
+    T, R, K = args.tokens, 32, args.force
+    assert 1 <= K <= T, (K, T)
+    infer = m._infer()
+    nz = torch.empty(T + 2, R, 1025).exponential_(1, generator=g)
+    nz[..., 1024] = 1e30
+    nz = nz.to(dev)
+    kw = dict(top_k=15, top_p=1, early_stop_num=T, repetition_penalty=1.35, logprobs=args.logprobs, noise=nz)
+    given = torch.randint(0, 1024, (R, K), generator=g)
+    plain = [(xs[r], berts[r], pr[r]) for r in range(R)]
+    forced = [(*q, dict(force=given[r])) for r, q in enumerate(plain)]
+    runs = {False: [], True: []}
+    for rep in range(args.reps + 1):
+        for f in (False, True):                # alternated: both see the same state of the device
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = list(m.decode_stream(forced if f else plain, slots=R, **kw))
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            st = infer.stream_stats
+            assert len(outs) == R and all(o[1].numel() == args.prompt + T for o in outs)
+            if f:
+                assert all(torch.equal(o[1][args.prompt:args.prompt + K].cpu(), given[o[0]]) for o in outs)
+            runs[f].append(1e6 * (t - sum(st["prefill_s"])) / st["steps"])
+    out = dict(plain_us_per_replay_all_runs=[round(v, 1) for v in runs[False][1:]],
+               forced_us_per_replay_all_runs=[round(v, 1) for v in runs[True][1:]])
+    out["forced_over_plain"] = round(_median(runs[True][1:]) / _median(runs[False][1:]), 4)
+    print(json.dumps(dict(workload=f"s1 decode stream, {R} requests alive for {T} steps, the first {K} tokens of each "
+                                   f"forced against none, logprobs={args.logprobs}, x_len<={args.x_len}, "
+                                   f"prompt={args.prompt}, {args.dtype}, {R} slots", **out)))
+
+
 def run_stream(args, m, dev, x, bert, prompts):
     """grouped against refilled decoding of the same requests (see the module docstring)"""
     lives, xs, berts, pr, noise, kw, g = _stream_workload(args, dev, x, bert, prompts)
@@ -284,6 +322,9 @@ def main():
     ap.add_argument("--candidates", type=int, default=0, metavar="N",
                     help="with --stream: 32 // N requests with N candidates each in one session, and the admission of "
                          "one request with N candidates against N single requests (nothing else)")
+    ap.add_argument("--force", type=int, default=0, metavar="K",
+                    help="with --stream: time per replay with the first K tokens of every request forced (the forced "
+                         "sampler launch) against the plain stream; --logprobs turns them on for both (nothing else)")
     ap.add_argument("--logprobs", action="store_true",
                     help="with --stream: time per replay with per-token log-probabilities on against off (nothing else)")
     args = ap.parse_args()
@@ -310,6 +351,9 @@ def main():
         if args.mixed:
             assert 1 <= args.mixed <= 8, args.mixed
             run_mixed(args, m, dev, x, bert, prompts)
+            return
+        if args.force:
+            run_force(args, m, dev, x, bert, prompts)
             return
         if args.candidates or args.logprobs:
             assert 0 <= args.candidates <= 32, args.candidates
