@@ -27,6 +27,8 @@ extern "C" int evt_grouped_fwd(const evt_conv1d_params* c, const void* x, const 
                                void* stream);
 extern "C" int evt_grouped_bwd_data(const evt_conv1d_params* c, const void* dy, const void* y, const void* w_reg,
                                     void* dx, void* stream);
+extern "C" int evt_grouped_bwd_data_add(const evt_conv1d_params* c, const void* dy, const void* y, const void* w_reg,
+                                        const void* dx_add, void* dx, void* stream);
 extern "C" int evt_grouped_bwd_weight(const evt_conv1d_params* c, const void* x, const void* dy, const void* y,
                                       float* dw, void* stream);
 
@@ -1333,10 +1335,10 @@ int evt_conv1d_bwd_data(const evt_conv1d_params* c, const void* dy, const void* 
   if (w_alt && evt_conv::rows16_eligible(c, c->nseq * c->lin, c->cin, c->cout, ysv || gate || dx_add))
     return evt_conv::launch_rows16(dy, w_alt, nullptr, dx, c->nseq * c->lin, c->cin, c->cout, st);
   evt_set_last_tag("conv_naive_bwd_data");
-  if (c->impl != EVT_IMPL_NAIVE && !gate && !dx_add && evt_grouped_supported(c)) {
+  if (c->impl != EVT_IMPL_NAIVE && !gate && evt_grouped_supported(c)) {
     if (!w_reg) return EVT_EINVAL;
     evt_set_last_tag("grouped_bwd_data");
-    return evt_grouped_bwd_data(c, dy, y, w_reg, dx, stream);
+    return evt_grouped_bwd_data_add(c, dy, y, w_reg, dx_add, dx, stream);
   }
   if (c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) != 0) {
     if (!w_reg) return EVT_EINVAL;

@@ -262,10 +262,5 @@ def _branch_bwd(slots, acts, ys, mg, lg_grad, in_shape, dt):
             L.check(L.lib().evt_dact_mul(dt, L.ptr(dy), L.ptr(y_act), int(act), C.c_float(slope), L.ptr(dy_eff),
                                          C.c_int64(dy.numel()), L.stream_ptr()), "evt_dact_mul")
             dy, y_arg, a_kind, a_slope = dy_eff, None, L.ACT_NONE, 1.0
-        if add is not None and s.module.groups > 1:
-            # the grouped kernels take no add operand (the dispatcher would fall back to the generic path)
-            dy = HC._bwd_data(s, dy.contiguous(), y_arg, None, None, half, lin, 1.0, a_kind, a_slope)
-            dy.add_(add)
-        else:
-            dy = HC._bwd_data(s, dy.contiguous(), y_arg, None, add, half, lin, 1.0, a_kind, a_slope)
+        dy = HC._bwd_data(s, dy.contiguous(), y_arg, None, add, half, lin, 1.0, a_kind, a_slope)
     return dy

@@ -62,8 +62,12 @@ def main():
     shapes.append(("dP5 512->1024 s3 H152", 2 * B * 5, 152, 512, 1024, 5, 3, 2, 1, 1, False, 1.0, 1))
     shapes.append(("dP11 128->512 s3 H207", 2 * B * 11, 207, 128, 512, 5, 3, 2, 1, 1, False, 1.0, 1))
     shapes.append(("dS 1024->1024 k5 L80", 2 * B, 80, 1024, 1024, 5, 1, 2, 1, 1, False, 1.0, 1))
-    shapes.append(("dS grouped 16->64 k41 s4 g4", 2 * B, 20480, 16, 64, 41, 4, 20, 1, 4, False, 1.0, 1))
-    shapes.append(("dS grouped 256->1024 k41 s4 g64", 2 * B, 1280, 256, 1024, 41, 4, 20, 1, 64, False, 1.0, 1))
+    # DiscriminatorS grouped k41 s4: [real ; generated] (n = 2B), and the generated half alone (n = B: what the generator
+    # step's backward-data runs on)
+    for ci, co, g, Lx in [(16, 64, 4, 20480), (64, 256, 16, 5120), (256, 1024, 64, 1280), (1024, 1024, 256, 320)]:
+        shapes.append((f"dS grouped {ci}->{co} k41 s4 g{g}", 2 * B, Lx, ci, co, 41, 4, 20, 1, g, False, 1.0, 1))
+    for ci, co, g, Lx in [(16, 64, 4, 20480), (64, 256, 16, 5120), (256, 1024, 64, 1280), (1024, 1024, 256, 320)]:
+        shapes.append((f"dS grouped {ci}->{co} k41 s4 g{g} half batch", B, Lx, ci, co, 41, 4, 20, 1, g, False, 1.0, 1))
     shapes.append(("WN in 192->384 k5 T200", B, 200, 192, 384, 5, 1, 2, 1, 1, False, 1.0, 0))
     shapes.append(("WN rs 192->384 k1 T200", B, 200, 192, 384, 1, 1, 0, 1, 1, False, 1.0, 0))
     shapes.append(("FFN 192->768 k3 T200", B, 200, 192, 768, 3, 1, 1, 1, 1, False, 1.0, 1))

@@ -96,6 +96,7 @@ def main():
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--depth", type=int, default=1, help="package frames shown per op (innermost first)")
+    ap.set_defaults(dump_outputs=None)      # bench.run_s2 reads it
     args = ap.parse_args()
     args.graphs = 0
     global DEPTH
