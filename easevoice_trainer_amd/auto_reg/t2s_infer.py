@@ -336,7 +336,12 @@ class T2SInfer:
         return self._sessions[key]
 
     def stream_session(self, B, Xmax, Lneed, yneed, dtype, device):
-        """the session cache of session(): capacities rounded to 512, stream sessions share the wide-session LRU"""
+        """the session cache of session(): capacities rounded to 512, stream sessions share the wide-session LRU.  A
+        session of more than WIDE_ROWS slots (decode_stream(wide=True)) is refused when its key/value cache,
+        2 * layers * B * Lmax * E * itemsize bytes (12.9 GB of bf16 at B = 128, Lmax = 2048), would need more than half
+        of the free device memory: before anything is allocated, and with the figures in the message.  Free memory is
+        what the device reports plus what torch's allocator holds unused, counted after the least recently used session
+        has made room (a refused session therefore still costs that one; it is made again when asked for)"""
         Lmax, ymax = -(-Lneed // 512) * 512, -(-yneed // 512) * 512
         key = (B, Lmax, ymax, dtype, str(device), "stream", Xmax)
         if key in self._wide:
@@ -344,6 +349,14 @@ class T2SInfer:
         else:
             while len(self._wide) >= self.WIDE_SESSIONS:
                 del self._sessions[self._wide.pop(0)]
+        if B > self.WIDE_ROWS and key not in self._sessions and torch.device(device).type == "cuda":
+            m = self.model
+            need = 2 * m.num_layers * B * Lmax * m.model_dim * torch.empty((), dtype=dtype).element_size()
+            free = (torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device)
+                    - torch.cuda.memory_allocated(device))
+            if 2 * need > free:
+                raise L.EvtError(f"a stream session of {B} slots and {Lmax} cache positions needs {need} bytes of "
+                                 f"key/value cache, more than half of the {free} bytes free on {device}")
         self._wide.append(key)
         if key not in self._sessions:
             self._sessions[key] = StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device)
@@ -352,6 +365,7 @@ class T2SInfer:
     MAX_ROWS = 4        # rows of a session on the kernels of csrc/s1_decode.hip (kMaxB); also the seed group of a row
     WIDE_ROWS = 32      # rows of a wide session (csrc/s1_decode_rows.hip); larger batches run in groups of 32
     WIDE_SESSIONS = 2   # wide sessions kept at once
+    STREAM_ROWS = 128   # slots of a stream session opened with wide=True: four row groups of evt_dec_gemm_rows
 
     @torch.no_grad()
     def _decode(self, xs, berts, prompts, no_eos_steps, top_k, top_p, early_stop_num, temperature, repetition_penalty,
@@ -530,7 +544,7 @@ class T2SInfer:
 
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
                       early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
-                      control=None, n=1, logprobs=False, forced=False):
+                      control=None, n=1, logprobs=False, forced=False, wide=False):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
         (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
         content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
@@ -540,8 +554,9 @@ class T2SInfer:
         poll -- a running row is set idle and its slot freed for the admission that follows, a waiting request is
         skipped without a prompt pass, either is yielded as (r, None, None); a request that finished at that poll is
         delivered.  Returns a generator of (request_index, y, idx) in COMPLETION order, y and idx as
-        infer_panel_batch_infer returns them per text.  Up to `slots` (1..32) texts decode at once in one graph-replayed
-        session; every `poll` steps the rows' status is read, finished rows are handed out and their slots refilled
+        infer_panel_batch_infer returns them per text.  Up to `slots` (1..32; 1..128 with wide=True, see below) texts
+        decode at once in one graph-replayed session; every `poll` steps the rows' status is read, finished rows are
+        handed out and their slots refilled
         with the next waiting requests (one prompt pass for all of them).  A list has the capacity (longest text,
         longest prompt, largest limit) computed from itself; a lazy iterable needs max_text_len / max_prompt_len and
         is bounded by `early_stop_num`.  A request that does not fit raises EvtError before anything is launched for
@@ -580,11 +595,18 @@ class T2SInfer:
         preempted row), logprobs = those of the steps taken.  A candidate that finished at that poll is delivered, a
         request still waiting at that poll is yielded as cancelled when its turn comes.  Submitting
         (x, bert, prompt, {"force": y[len(prompt):], "seed": ...}) to this or a later stream continues the row exactly
-        where it was."""
+        where it was.
+
+        wide=True allows slots up to STREAM_ROWS = 128: the linear layers run the rows in groups of 32 on one more grid
+        dimension, and a row's tokens do not depend on the number of slots.  It is asked for, not silently given,
+        because the session's cache grows with the slots: 2 * layers * slots * Lmax * E * itemsize bytes, 12.9 GB in
+        bf16 and 25.8 GB in fp32 at 128 slots and Lmax = 2048, and WIDE_SESSIONS of them are kept.  A session of more
+        than 32 slots that would need more than half of the free device memory is refused with an EvtError."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
-        if not 1 <= int(slots) <= self.WIDE_ROWS:
-            raise L.EvtError(f"slots must be 1..{self.WIDE_ROWS}, got {slots}")
+        most = self.STREAM_ROWS if wide else self.WIDE_ROWS
+        if not 1 <= int(slots) <= most:
+            raise L.EvtError(f"slots must be 1..{most}, got {slots}")
         slots, logprobs = int(slots), bool(logprobs)
         nsteps = None if noise is None else int(noise.size(0))
         ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
@@ -713,7 +735,7 @@ class T2SInfer:
         return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
                             max(1, int(poll)), control, logprobs, rich, forced)
 
-    def score_stream(self, requests, tokens, slots=32, append_eos=False, **sampling):
+    def score_stream(self, requests, tokens, slots=32, append_eos=False, wide=False, **sampling):
         """Log-probabilities of GIVEN tokens: request r = (x, bert, prompt[, opt]) is forced over all of tokens[r] (a 1-D
         integer vector; append_eos=True adds EOS behind it), limited to exactly that many steps, with logprobs=True.
         Yields (r, logprobs) in completion order, logprobs fp32 [f, 2]: per given token the model's log-probability and
@@ -738,7 +760,7 @@ class T2SInfer:
 
         lazy = not isinstance(requests, (list, tuple))
         reqs = forced_requests() if lazy else list(forced_requests())
-        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, **sampling):
+        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, **sampling):
             yield o.request, o.logprobs
 
     @staticmethod
@@ -853,7 +875,8 @@ class T2SInfer:
                0 if q[7] is None else q[7].numel()] for i, c, q in per]
         S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
         S.stop[slots_t] = -1
-        # candidate c draws lane r % 4 + 4c of the request's group seed (the hash folds the lane in as lane << 16)
+        # candidate c draws lane r % 4 + 4c of the request's group seed (the hash folds the lane in as lane << 16): at
+        # most 3 + 4 * 127 = 511 with n = STREAM_ROWS candidates, well inside the 16 bits the hash gives the lane
         own = [q[8] if q[8] is not None else seeds(q[0]) for _i, _c, q in per]      # a request's own (seed, lane)
         S.row_seed[slots_t] = torch.tensor([[sd, lane + self.MAX_ROWS * c] for (sd, lane), (_i, c, _q) in zip(own, per)],
                                            dtype=torch.int32).to(dev)
@@ -981,13 +1004,15 @@ class T2SInfer:
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
                                        early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,
-                                       poll=8, logprobs=False, **kwargs):
+                                       poll=8, logprobs=False, wide=False, **kwargs):
         """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
         the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
         of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths.
         top_k, top_p, temperature, repetition_penalty and early_stop_num: a scalar for all texts, or a sequence with
         one value per text.  logprobs=True returns (ys, idxs, lps), lps[r] the fp32 [steps, 2] log-probabilities of text
-        r as decode_stream hands them out."""
+        r as decode_stream hands them out.  `slots` is first clamped to the number of texts (no slot would stay idle),
+        then checked by decode_stream: 1..32, with wide=True 1..128 -- so a larger value passes when there are no more
+        texts than that, as slots=33 always did."""
         if prompts is None:
             if logprobs:
                 raise L.EvtError("logprobs needs prompts (the refilled session)")
@@ -1003,14 +1028,14 @@ class T2SInfer:
             if len(v) != R:
                 raise L.EvtError(f"{k}: {len(v)} values for {R} texts")
             v[:] = [e.item() if torch.is_tensor(e) else e for e in v]
-        wide = {k: (per[k][0] if k in per and R else v) for k, v in given.items()}     # per-text values replace these
+        base = {k: (per[k][0] if k in per and R else v) for k, v in given.items()}     # per-text values replace these
         if per:
             reqs = [(x[r], bert_feature[r], prompts[r], {k: v[r] for k, v in per.items()}) for r in range(R)]
         else:
             reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(R)]
         ys, idxs, lps = [None] * len(reqs), [None] * len(reqs), [None] * len(reqs)
         for o in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed, poll=poll,
-                                    logprobs=logprobs, **wide):
+                                    logprobs=logprobs, wide=wide, **base):
             ys[o[0]], idxs[o[0]] = o[1], o[2]
             if logprobs:
                 lps[o[0]] = o.logprobs

@@ -1,5 +1,5 @@
-// s1 decode linear for a batch of up to 32 rows (infer_panel_batch_infer, t2s_model.py:563-730, with the TTS service's
-// default of 20 texts per call) for gfx950.
+// s1 decode linear for a batch of up to 128 rows, in row groups of 32 (infer_panel_batch_infer, t2s_model.py:563-730,
+// with the TTS service's default of 20 texts per call; stream sessions of up to 128 slots) for gfx950.
 //
 // evt_dec_gemv keeps the whole input [B][K] in LDS and every wave walks its own weight rows with VALU dot products, so it
 // stops at four rows.  Here one workgroup owns a 16-row tile of W and ALL rows of x: every weight byte is read from HBM
@@ -12,19 +12,24 @@
 //   requested before anything else.  The 8 wave partials are summed through LDS in wave order (no atomics: two launches
 //   give the same bits).
 //   LayerNorm prologue: one wave per batch row computes (mean, 1/std) from a + r while the staging loads are in flight.
+//   More than 32 rows: row groups of 32 on blockIdx.y.  Block (x, g) is the block described above for the weight rows
+//   16x .. 16x+15 and the batch rows 32g .. min(32g + 32, B) - 1: a, r, y and x_out are offset by the group, everything
+//   else (statistics, staging buffer, partial tiles, the b-tiles in use) is the group's own, and x_out is written by the
+//   blockIdx.x == 0 block of each group.  A row's arithmetic does not depend on the launch it is in, so every output
+//   row of a wide launch has the bits a launch of that row's group alone gives; B <= 32 launches the grid it always
+//   launched.  The G blocks of a weight tile re-read it; at G <= 4 that is meant to hit L2 / the Infinity Cache.
 #include "evt_common.h"
+#include "s1_decode_rows_index.h"
 #include "../../include/evt.h"
 
 namespace {
 
-constexpr int kRows = 32;            // batch rows per launch: two 16-column MFMA tiles
-constexpr int kNW = 8;               // waves per workgroup
-constexpr int kThreads = kNW * 64;
-constexpr int kKC = 512;             // K chunk staged in LDS
+// rows per group / per launch, waves, threads, K chunk and the staging count: s1_decode_rows_index.h
+using evt_rows::kRows; using evt_rows::kRowsMax; using evt_rows::kNW; using evt_rows::kThreads; using evt_rows::kKC;
+using evt_rows::kXPT;
 constexpr int kXS = kKC + 4;         // LDS row stride (floats): the 16 rows of a b-tile start on different banks
 constexpr int kKW = kKC / kNW;       // K slice of a wave per chunk: 64 = 4 lane groups x 16
 constexpr int kPS = kRows + 1;       // row stride of the partial tiles in LDS
-constexpr int kXPT = kRows * kKC / 4 / kThreads;   // float4 of one chunk of x per thread while staging (8)
 constexpr int kLds = kRows * kXS * (int)sizeof(float);
 static_assert(kNW * 16 * kPS <= kRows * kXS, "partials fit in the staging buffer");
 
@@ -32,7 +37,7 @@ template <typename T, int NCH>
 __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ W, const float* __restrict__ bias,
                                                           const float* __restrict__ a, const float* __restrict__ r,
                                                           const float* __restrict__ ln_g, const float* __restrict__ ln_b,
-                                                          float eps, float* x_out, float* __restrict__ y, int B, int N,
+                                                          float eps, float* x_out, float* __restrict__ y, int Bt, int N,
                                                           int relu) {
   extern __shared__ float xs[];      // [kRows][kXS] x of the current chunk; then the wave partials [kNW][16][kPS]
   __shared__ float mu[kRows], rstd[kRows];
@@ -42,7 +47,14 @@ __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int nbt = (B + 15) >> 4;           // b-tiles in use (1 or 2), uniform over the launch
+  // the block's row group: rows g0 .. g0 + B - 1 of the launch, B = 1..32 (the last group may be short)
+  const int g0 = evt_rows::group_first(blockIdx.y);
+  const int B = evt_rows::group_rows(Bt, g0);
+  a += evt_rows::row_offset(g0, K);
+  if (r) r += evt_rows::row_offset(g0, K);
+  if (x_out) x_out += evt_rows::row_offset(g0, K);
+  y += evt_rows::row_offset(g0, N);
+  const int nbt = evt_rows::b_tiles(B);    // b-tiles in use (1 or 2), uniform over the group
   // ---- every weight of the tile in flight first ----
   uint4 w[NCH][U];
   {
@@ -55,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ 
         w[c][u] = n < N ? *reinterpret_cast<const uint4*>(row + c * kKC + u * V) : make_uint4(0, 0, 0, 0);
   }
   // staging layout: thread -> columns 4*k4 .. 4*k4+3 of rows (tid >> 7) + 4*i
-  const int k4 = tid & (kKC / 4 - 1), rb = tid >> 7;
+  const int k4 = evt_rows::stage_k4(tid), rb = evt_rows::stage_row0(tid);
   const int rows_used = nbt * 16;
   float4 xr[kXPT];
   auto load_chunk = [&](int c) {
@@ -64,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ 
       const int b = rb + 4 * i;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (b < B) {
-        const long o = (long)b * K + c * kKC + 4 * k4;
+        const long o = evt_rows::stage_offset(b, K, c, k4);
         v = *reinterpret_cast<const float4*>(a + o);
         if (r) {
           const float4 q = *reinterpret_cast<const float4*>(r + o);
@@ -76,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ 
   };
   load_chunk(0);
   // the epilogue's operands are requested now as well
-  const int eb = tid >> 4, en = tid & 15;
+  const int eb = evt_rows::epi_row(tid), en = evt_rows::epi_col(tid);
   const float bz = (bias && n0 + en < N) ? bias[n0 + en] : 0.f;
   if (r) {
     // LayerNorm statistics of a + r, one wave per batch row (same formula as evt_dec_gemv: E[x^2] - E[x]^2)
@@ -118,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void dec_gemm_rows(const T* __restrict__ 
         v.y = (v.y - m) * s * g.y + be.y;
         v.z = (v.z - m) * s * g.z + be.z;
         v.w = (v.w - m) * s * g.w + be.w;
-        if (x_out && blockIdx.x == 0) *reinterpret_cast<float4*>(x_out + (long)b * K + c * kKC + 4 * k4) = v;
+        if (x_out && blockIdx.x == 0) *reinterpret_cast<float4*>(x_out + evt_rows::stage_offset(b, K, c, k4)) = v;
       }
       *reinterpret_cast<float4*>(xs + b * kXS + 4 * k4) = v;
     }
@@ -191,8 +203,8 @@ int launch_rows(const void* W, const float* bias, const float* a, const float* r
       return EVT_ELAUNCH;
     lds_set = true;
   }
-  hipLaunchKernelGGL((dec_gemm_rows<T, NCH>), dim3((N + 15) / 16), dim3(kThreads), kLds, st, (const T*)W, bias, a, r, g,
-                     bt, eps, x_out, y, B, N, relu);
+  hipLaunchKernelGGL((dec_gemm_rows<T, NCH>), dim3(evt_rows::grid_x(N), evt_rows::grid_y(B)), dim3(kThreads), kLds, st,
+                     (const T*)W, bias, a, r, g, bt, eps, x_out, y, B, N, relu);
   return evt_check_launch();
 }
 
@@ -220,7 +232,7 @@ extern "C" int evt_dec_gemm_rows(int32_t wdtype, const void* W, const float* bia
   if (!aligned16(W) || !aligned16(a) || (r && (!aligned16(r) || !aligned16(ln_g) || !aligned16(ln_b))) ||
       (x_out && !aligned16(x_out)))
     return EVT_EINVAL;
-  if (B > kRows || K % kKC || K > 4 * kKC) return EVT_ENOTSUP;
+  if (B > kRowsMax || K % kKC || K > 4 * kKC) return EVT_ENOTSUP;
   hipStream_t st = (hipStream_t)stream;
   if (wdtype == EVT_DT_HALF) return dispatch_rows<h16_t>(K, W, bias, a, r, ln_g, ln_b, ln_eps, x_out, y, B, N, relu, st);
   if (wdtype == EVT_DT_F32) return dispatch_rows<float>(K, W, bias, a, r, ln_g, ln_b, ln_eps, x_out, y, B, N, relu, st);

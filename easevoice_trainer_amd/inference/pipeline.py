@@ -45,11 +45,12 @@ def synthesize_fragments(t2s, voice, batch_phones, all_phoneme_ids, all_bert_fea
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
-                      choose=None):
+                      choose=None, wide=False):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
-    free row); each is turned into audio on its own by the s2 decoder as soon as its tokens are there, at any
+    free row; wide=True allows up to 128 slots, decode_stream's `wide`); each is turned into audio on its own by the
+    s2 decoder as soon as its tokens are there, at any
     speed_factor, while the other rows' tokens wait in the session.  prompt_semantic: [1, P] for all fragments, or a
     list with one token vector per fragment (fragments of several reference voices in one session).
     fragment_sampling: a list with one dict (keys out of top_k, top_p, temperature, repetition_penalty, early_stop_num)
@@ -94,7 +95,7 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         stream = model.decode_stream(reqs, slots=min(int(slots), max(n, 1) * candidates), top_k=top_k, top_p=top_p,
                                      temperature=temperature, early_stop_num=t2s.early_stop_num,
                                      repetition_penalty=repetition_penalty, control=control, n=candidates, logprobs=True,
-                                     **(sample_kwargs or {}))
+                                     wide=wide, **(sample_kwargs or {}))
         takes = {}
         for o in stream:
             got = takes.setdefault(o.request, {})
@@ -111,7 +112,7 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         return
     stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
                                  early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
-                                 control=control, **(sample_kwargs or {}))
+                                 control=control, wide=wide, **(sample_kwargs or {}))
     for r, y, idx in stream:
         if y is None or idx is None:       # cancelled, or preempted with partial tokens: no s2 decode
             yield r, None

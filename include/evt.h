@@ -669,17 +669,20 @@ int evt_ce_rows_fwd_bwd_ld(int32_t dtype, const void* logits, const int64_t* tar
 #define EVT_DEC_YLEN 3   /* prompt length: the new token's position is YLEN + IDX (t2s_model.py:861) */
 #define EVT_DEC_SEED 4   /* per-call sampling seed, xor-ed with evt_sample_params.seed */
 /* y[b][n] = act(bias[n] + sum_k W[n][k] * x[b][k]); W [N][K] row-major in `wdtype`, vectors fp32, B <= 4 (sessions of up
- * to four rows; evt_dec_gemm_rows below serves up to 32), K % 512 == 0.
+ * to four rows; evt_dec_gemm_rows below serves up to 128), K % 512 == 0.
  * r == NULL: x = a.  r != NULL: x = LayerNorm(a + r) * ln_g + ln_b (the post-LN residual of T2SBlock.decode_next_token,
  * t2s_model.py:208-221, recomputed per workgroup); x_out (may be NULL) receives it for the next residual and must not
  * alias a or r.  relu != 0 applies max(0, .) (T2SMLP.forward, t2s_model.py:74-77). */
 int evt_dec_gemv(int32_t wdtype, const void* W, const float* bias, const float* a, const float* r, const float* ln_g,
                  const float* ln_b, float ln_eps, float* x_out, float* y, int32_t B, int32_t N, int32_t K, int32_t relu,
                  void* stream);
-/* evt_dec_gemv for 1 <= B <= 32 rows (the wide decode sessions of 5..32 texts, t2s_model.py:563-730): same arguments and
- * numerics (x fp32, 16-bit weights widened exactly, fp32 products and sums; only the order of the sum differs), but every
- * weight byte is read from HBM once per launch for all rows (fp32-input MFMA over 16-row tiles of W).  K % 512 == 0,
- * K <= 2048; W, a, r, ln_g, ln_b and x_out 16-byte aligned.  Deterministic: no atomics. */
+/* evt_dec_gemv for 1 <= B <= 128 rows (the wide decode sessions of 5..32 texts, t2s_model.py:563-730, and stream sessions
+ * of up to 128 slots): same arguments and numerics (x fp32, 16-bit weights widened exactly, fp32 products and sums; only
+ * the order of the sum differs), but every weight byte is read from HBM once per launch for all rows (fp32-input MFMA
+ * over 16-row tiles of W).  More than 32 rows run as row groups of 32, one more grid dimension: every output row has the
+ * bits a launch of that row's group alone (rows 32g .. 32g+31 of a, r) gives, and a weight tile is read once per
+ * group (the re-reads are meant to hit L2 / the Infinity Cache; not measured).  B > 128: EVT_ENOTSUP.  K % 512 == 0, K <= 2048; W, a, r, ln_g, ln_b and x_out 16-byte aligned.
+ * Deterministic: no atomics. */
 int evt_dec_gemm_rows(int32_t wdtype, const void* W, const float* bias, const float* a, const float* r,
                       const float* ln_g, const float* ln_b, float ln_eps, float* x_out, float* y, int32_t B, int32_t N,
                       int32_t K, int32_t relu, void* stream);

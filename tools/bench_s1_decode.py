@@ -11,8 +11,16 @@ through infer_panel_batch_infer (groups of 32, each waiting for its slowest row)
 tokens/s and us per step of both, the stream's admissions and prefill time, median and last completion time, the step
 time of both sessions with 32 rows alive for --tokens steps, and the prefill time of 1, 8 and 32 admitted rows.
 
+--stream --slots S [S ...] times the refilled session alone at each of the slot counts (wide=True above 32), the same
+seeded texts through every one, the slot counts alternated --reps times each, and asserts that every slot count produced
+identical tokens; one JSON line with, per slot count, the median run's seconds, steps, useful tokens/s, us per step with
+the prompt passes excluded, admissions and the share of the time spent in prompt passes.  --slots has no default value:
+without it --stream keeps running the comparison above (grouped against refilled, 32 slots, with its rows32 and
+admission sections), whose JSON line earlier profiles were recorded with; `--slots 32` is the 32-slot line of the new form.
+
     python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
     python tools/bench_s1_decode.py --stream [--stream-n 96]
+    python tools/bench_s1_decode.py --stream --stream-n 512 --slots 32 64 96 128      (see run_slots)
     python tools/bench_s1_decode.py --stream --mixed 4      (per-request sampling parameters, see run_mixed)
     python tools/bench_s1_decode.py --stream --candidates 4 --logprobs      (see run_candidates)
     python tools/bench_s1_decode.py --stream --force 64      (forced first tokens of every request, see run_force)
@@ -208,6 +216,55 @@ def run_force(args, m, dev, x, bert, prompts):
                                    f"prompt={args.prompt}, {args.dtype}, {R} slots", **out)))
 
 
+def run_slots(args, m, dev, x, bert, prompts):
+    """--slots S [S ...]: the texts of --stream through one refilled session per slot count.  Every session is kept for
+    the whole run (the tool raises the model's WIDE_SESSIONS to the number of slot counts), so a timed pass neither
+    allocates a cache nor captures a graph; the first pass of each slot count does both and is not timed."""
+    lives, xs, berts, pr, noise, kw, _g = _stream_workload(args, dev, x, bert, prompts)
+    N, poll = args.stream_n, kw["poll"]
+    infer = m._infer()
+    infer.WIDE_SESSIONS = max(infer.WIDE_SESSIONS, len(args.slots))
+    reqs = [(xs[r], berts[r], pr[r]) for r in range(N)]
+    useful = sum(lives)
+    runs, first = {S: [] for S in args.slots}, None
+    identical = True
+    for rep in range(args.reps + 1):
+        for S in args.slots:                   # alternated: every slot count sees the same state of the device
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ys = [None] * N
+            for r, y, _i in m.decode_stream(reqs, slots=S, wide=S > 32, noise=noise, **kw):
+                ys[r] = y
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            st = infer.stream_stats
+            assert [y.numel() for y in ys] == [args.prompt + s for s in lives], S
+            if first is None:
+                first = ys
+            elif not all(torch.equal(a, b) for a, b in zip(first, ys)):
+                identical = False
+            runs[S].append(dict(seconds=t, steps=st["steps"], prefill_s=sum(st["prefill_s"]), admissions=st["admissions"],
+                                captured=bool(st["graph_captured"])))
+    out = {}
+    for S, v in runs.items():
+        timed = v[1:]
+        med = sorted(timed, key=lambda e: e["seconds"])[len(timed) // 2]
+        t, pre = med["seconds"], med["prefill_s"]
+        out[str(S)] = dict(seconds=round(t, 4), steps=med["steps"], useful_tokens=useful,
+                           tokens_per_s=round(useful / t, 1), us_per_step=round(1e6 * (t - pre) / med["steps"], 1),
+                           admissions=med["admissions"], prefill_share=round(pre / t, 4),
+                           seconds_all_runs=[round(e["seconds"], 4) for e in timed],
+                           graph_captures_timed_passes=sum(e["captured"] for e in timed))
+    base = out[str(args.slots[0])]["tokens_per_s"]
+    for S in args.slots[1:]:
+        out[str(S)]["tokens_per_s_over_first"] = round(out[str(S)]["tokens_per_s"] / base, 3)
+    print(json.dumps(dict(workload=f"s1 decode stream, {N} texts living 64..512 steps, x_len<={args.x_len}, "
+                                   f"prompt={args.prompt}, {args.dtype}, poll {poll}, slots {args.slots} alternated, "
+                                   f"median of {args.reps}; us_per_step excludes the prompt passes, prefill_share is "
+                                   "their share of the seconds", identical_tokens=identical, slots=out)), flush=True)
+    assert identical, "the slot counts did not produce identical tokens"
+
+
 def run_stream(args, m, dev, x, bert, prompts):
     """grouped against refilled decoding of the same requests (see the module docstring)"""
     lives, xs, berts, pr, noise, kw, g = _stream_workload(args, dev, x, bert, prompts)
@@ -316,6 +373,10 @@ def main():
     ap.add_argument("--stream", action="store_true",
                     help="time the refilled session against infer_panel_batch_infer on --stream-n texts (nothing else)")
     ap.add_argument("--stream-n", type=int, default=96)
+    ap.add_argument("--slots", type=int, nargs="+", default=None, metavar="S",
+                    help="with --stream: the refilled session alone at each of these slot counts (1..128, wide=True above "
+                         "32), alternated, with identical tokens asserted (nothing else); default: the comparison with "
+                         "infer_panel_batch_infer at 32 slots")
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="with --stream: request r samples with parameter set r %% N; one session holding all sets "
                          "against N uniform streams run one after the other (nothing else)")
@@ -348,6 +409,10 @@ def main():
     noise = noise.to(dev)
     if args.stream:
         os.environ["EVT_DECODE_GRAPH"] = "1"
+        if args.slots:
+            assert all(1 <= S <= 128 for S in args.slots), args.slots
+            run_slots(args, m, dev, x, bert, prompts)
+            return
         if args.mixed:
             assert 1 <= args.mixed <= 8, args.mixed
             run_mixed(args, m, dev, x, bert, prompts)
