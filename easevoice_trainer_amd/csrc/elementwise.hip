@@ -343,6 +343,17 @@ __global__ void lrelu_kernel(const T* x, float slope, T* out, long n) {
   }
 }
 
+// x[s][t][:] = 0 for t >= lens[s] * mul, in place (the dead tails of a ragged batch in front of a consumer without a masked
+// load); one 16-byte store per lane and dead vector, live positions are not touched; cpr = 16-byte vectors per position
+__global__ void mask_tail_kernel(uint4* x, const int32_t* lens, int mul, int L, int cpr, long nv) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / cpr;
+    const int seq = (int)(row / L);
+    const int t = (int)(row - (long)seq * L);
+    if (t >= (long)lens[seq] * mul) x[i] = make_uint4(0, 0, 0, 0);
+  }
+}
+
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
 template <typename T>
@@ -672,6 +683,18 @@ int evt_leaky_relu(int32_t dtype, const void* x, float slope, void* out, int64_t
     hipLaunchKernelGGL(lrelu_kernel<float>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, (const float*)x, slope,
                        (float*)out, (long)n);
   else return EVT_EINVAL;
+  return evt_check_launch();
+}
+
+int evt_mask_tail(int32_t dtype, void* x, const int32_t* lens, int32_t mul, int32_t nseq, int32_t L, int32_t C,
+                  void* stream) {
+  if (!x || !lens || mul < 1 || nseq <= 0 || L <= 0 || C <= 0) return EVT_EINVAL;
+  if (dtype != EVT_DT_HALF && dtype != EVT_DT_F32) return EVT_EINVAL;
+  const int per = dtype == EVT_DT_F32 ? 4 : 8;             // elements per 16-byte vector
+  if (C % per || ((uintptr_t)x & 15)) return EVT_EINVAL;
+  const long nv = (long)nseq * L * (C / per);
+  hipLaunchKernelGGL(mask_tail_kernel, dim3(grid_for(nv)), dim3(256), 0, (hipStream_t)stream, (uint4*)x, lens, (int)mul,
+                     (int)L, C / per, nv);
   return evt_check_launch();
 }
 

@@ -37,8 +37,11 @@ struct RUP {
 };
 
 // CI: channels (16 or 32); NK: K steps of 32 per convolution = padded taps * CI / 32
-template <int CI, int NK>
-__device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* smem, const int blk, const int nblk) {
+// RAG: row s is live on [0, Ls), Ls = min(L, lens[s] * mul) (evt_resunit_fwd_multi_lens): every test of a position against
+// the sequence end takes the row's Ls, and y on [Ls, L) is stored as zero; !RAG is the code as it was (lim() folds to p.L)
+template <int CI, int NK, bool RAG = false>
+__device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* smem, const int blk, const int nblk,
+                                                 const int32_t* lens = nullptr, const int mul = 1) {
   constexpr int MT = CI / 16;
   constexpr int PITCH = CI * 2;
   constexpr int LOGP = CI == 16 ? 1 : 2;
@@ -69,8 +72,17 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
   const long wave_id = (long)blk * 4 + wave, nwaves = (long)nblk * 4;
   const int npieces = p.xrows * PPR;
   uint4 xr[XPT];
+  auto lim = [&](const int seq) {                          // end of the live part of row `seq`
+    if constexpr (RAG) {
+      const long l = (long)lens[seq] * mul;
+      return l < 0 ? 0 : (l < p.L ? (int)l : p.L);
+    } else {
+      return p.L;
+    }
+  };
   auto load_unit = [&](long u) {
     const int seq = (int)(u / p.ups);
+    const int Ls = lim(seq);
     const int row0 = (int)(u - (long)seq * p.ups) * 64 - H2 - h1;
     const h16_t* xg = p.x + (long)seq * p.L * CI;
 #pragma unroll
@@ -78,7 +90,7 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
       const int idx = lane + i * 64;
       const int r = idx >> LOGP, part = idx & (PPR - 1);
       const int in_row = row0 + r;
-      const bool ok = idx < npieces && in_row >= 0 && in_row < p.L;
+      const bool ok = idx < npieces && in_row >= 0 && in_row < Ls;
       xr[i] = ok ? *reinterpret_cast<const uint4*>(xg + (long)in_row * CI + part * 8) : make_uint4(0, 0, 0, 0);
     }
   };
@@ -87,6 +99,17 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
     const int seq = (int)(u / p.ups);
     const int q0 = (int)(u - (long)seq * p.ups) * 64;
     const long sbase = (long)seq * p.L * CI;
+    const int Ls = lim(seq);
+    if constexpr (RAG) {
+      if (q0 >= Ls) {                                      // a unit wholly in the dead tail: zeros, nothing to compute
+        for (int idx = lane; idx < 64 * PPR; idx += 64) {
+          const int q = q0 + (idx >> LOGP);
+          if (q < p.L) *reinterpret_cast<uint4*>(p.y + sbase + (long)q * CI + (idx & (PPR - 1)) * 8) = make_uint4(0, 0, 0, 0);
+        }
+        if (u + nwaves < p.total) load_unit(u + nwaves);
+        continue;
+      }
+    }
     // activate and publish this unit's rows (previous unit's fragment reads are complete: in-order DS); the unit's own
     // 64 rows of lrelu(x) also go to global for the backward launch
 #pragma unroll
@@ -97,7 +120,7 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
         const uint4 a = lrelu8(xr[i], p.slope);
         *reinterpret_cast<uint4*>(xs + piece_off<CI>(r, part)) = a;
         const int o = r - h1 - H2;                    // position q0 + o
-        if (p.xa && o >= 0 && o < 64 && q0 + o < p.L)
+        if (p.xa && o >= 0 && o < 64 && q0 + o < Ls)
           *reinterpret_cast<uint4*>(p.xa + sbase + (long)(q0 + o) * CI + part * 8) = a;
       }
     }
@@ -118,7 +141,7 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
       for (int j = 0; j < NT1; ++j) {
         const int pos = j * 16 + n;
         const int m = q0 - H2 + pos;
-        const bool inside = m >= 0 && m < p.L;
+        const bool inside = m >= 0 && m < Ls;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           h16_t o4[4];
@@ -151,13 +174,20 @@ __device__ __forceinline__ void resunit_fwd_body(const RUP& p, unsigned char* sm
         const int q = q0 + j * 16 + n;
 #pragma unroll
         for (int i = 0; i < MT; ++i)
-          rv[j][i] = q < p.L ? *reinterpret_cast<const uint2*>(p.x + sbase + (long)q * CI + i * 16 + g * 4) : make_uint2(0, 0);
+          rv[j][i] = q < Ls ? *reinterpret_cast<const uint2*>(p.x + sbase + (long)q * CI + i * 16 + g * 4) : make_uint2(0, 0);
       }
       conv_stage<CI, NK, MT, NT2>(acc, wl2, ms, 1, n, g);
 #pragma unroll
       for (int j = 0; j < NT2; ++j) {
         const int q = q0 + j * 16 + n;
         if (q >= p.L) continue;
+        if constexpr (RAG) {
+          if (q >= Ls) {                                   // dead tail of a live unit: a clean zero for the next consumer
+#pragma unroll
+            for (int i = 0; i < MT; ++i) *reinterpret_cast<uint2*>(p.y + sbase + (long)q * CI + i * 16 + g * 4) = make_uint2(0, 0);
+            continue;
+          }
+        }
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const h16_t* pr = reinterpret_cast<const h16_t*>(&rv[j][i]);
@@ -190,6 +220,20 @@ __global__ __launch_bounds__(256) void resunit_fwd_multi(RUPM pm) {
   if (b < pm.blk_end[0]) resunit_fwd_body<CI, NK3>(pm.job[0], smem, b, pm.blk_end[0]);
   else if (b < pm.blk_end[1]) resunit_fwd_body<CI, NK7>(pm.job[1], smem, b - pm.blk_end[0], pm.blk_end[1] - pm.blk_end[0]);
   else resunit_fwd_body<CI, NK11>(pm.job[2], smem, b - pm.blk_end[1], pm.blk_end[2] - pm.blk_end[1]);
+}
+
+struct RUPML { RUPM m; const int32_t* lens; int mul; };
+
+template <int CI>
+__global__ __launch_bounds__(256) void resunit_fwd_multi_lens(RUPML pl) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  constexpr int NK3 = CI == 16 ? 2 : 3, NK7 = CI == 16 ? 4 : 7, NK11 = CI == 16 ? 6 : 11;
+  const RUPM& pm = pl.m;
+  const int b = blockIdx.x;
+  if (b < pm.blk_end[0]) resunit_fwd_body<CI, NK3, true>(pm.job[0], smem, b, pm.blk_end[0], pl.lens, pl.mul);
+  else if (b < pm.blk_end[1])
+    resunit_fwd_body<CI, NK7, true>(pm.job[1], smem, b - pm.blk_end[0], pm.blk_end[1] - pm.blk_end[0], pl.lens, pl.mul);
+  else resunit_fwd_body<CI, NK11, true>(pm.job[2], smem, b - pm.blk_end[1], pm.blk_end[2] - pm.blk_end[1], pl.lens, pl.mul);
 }
 
 inline int rup8(int v) { return (v + 7) / 8 * 8; }
@@ -238,6 +282,47 @@ bool job_ok(const evt_resunit_params* a) {
   return true;
 }
 
+// jobs -> the grouped launch's parameters, block ranges (*end blocks in all) and LDS bytes; same_nseq: every job has the
+// rows of the first (the ragged launch shares one lens table)
+int plan_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, RUPM& pm, size_t* lds_out, int* end_out, int* C_out, bool same_nseq) {
+  if (!jobs || njobs < 1 || njobs > 3) return EVT_EINVAL;
+  size_t lds = 0;
+  double cost[3] = {0, 0, 0};
+  const int C = jobs[0].p.C;
+  for (int j = 0; j < njobs; ++j) {
+    const evt_resunit_fwd_job& jb = jobs[j];
+    if (!evt_resunit_supported(&jb.p) || jb.p.C != C) return EVT_ENOTSUP;
+    if (same_nseq && (jb.p.nseq != jobs[0].p.nseq || jb.p.L != jobs[0].p.L)) return EVT_ENOTSUP;
+    if (!jb.x || !jb.w1_reg || !jb.w2_reg || !jb.y) return EVT_EINVAL;
+    const int slot = jb.p.k == 3 ? 0 : (jb.p.k == 7 ? 1 : 2);
+    if (cost[slot] != 0) return EVT_ENOTSUP;              // one job per kernel size
+    RUP& p = pm.job[slot];
+    p.x = (const h16_t*)jb.x; p.w1 = (const h16_t*)jb.w1_reg; p.w2 = (const h16_t*)jb.w2_reg; p.b1 = jb.b1; p.b2 = jb.b2;
+    p.xa = (h16_t*)jb.xa; p.mid = (h16_t*)jb.mid_a; p.y = (h16_t*)jb.y;
+    p.nseq = jb.p.nseq; p.L = jb.p.L; p.k = jb.p.k; p.dil = jb.p.dil; p.slope = jb.p.slope;
+    const size_t l = fwd_geometry(p, C);
+    if (!l) return EVT_ENOTSUP;
+    if (l > lds) lds = l;
+    cost[slot] = (double)p.total * (1.0 + 0.12 * jb.p.k);  // measured single launches: 20 / 21 / 21.5 us (C = 16), 21 / 25 / 29 (C = 32)
+  }
+  const int per_cu = (int)((160 * 1024) / lds) < 4 ? (int)((160 * 1024) / lds) : 4;
+  const long cap = 256L * per_cu;
+  const double tot = cost[0] + cost[1] + cost[2];
+  int end = 0;
+  for (int s = 0; s < 3; ++s) {
+    if (cost[s] > 0) {
+      long nb = (long)(cap * cost[s] / tot + 0.5);
+      const long need = (pm.job[s].total + 3) / 4;
+      if (nb > need) nb = need;
+      if (nb < 1) nb = 1;
+      end += (int)nb;
+    }
+    pm.blk_end[s] = end;
+  }
+  *lds_out = lds; *end_out = end; *C_out = C;
+  return EVT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -268,40 +353,10 @@ int evt_resunit_fwd(const evt_resunit_params* a, const void* x, const void* w1_r
 }
 
 int evt_resunit_fwd_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, void* stream) {
-  if (!jobs || njobs < 1 || njobs > 3) return EVT_EINVAL;
   RUPM pm{};
   size_t lds = 0;
-  double cost[3] = {0, 0, 0};
-  const int C = jobs[0].p.C;
-  for (int j = 0; j < njobs; ++j) {
-    const evt_resunit_fwd_job& jb = jobs[j];
-    if (!evt_resunit_supported(&jb.p) || jb.p.C != C) return EVT_ENOTSUP;
-    if (!jb.x || !jb.w1_reg || !jb.w2_reg || !jb.y) return EVT_EINVAL;
-    const int slot = jb.p.k == 3 ? 0 : (jb.p.k == 7 ? 1 : 2);
-    if (cost[slot] != 0) return EVT_ENOTSUP;              // one job per kernel size
-    RUP& p = pm.job[slot];
-    p.x = (const h16_t*)jb.x; p.w1 = (const h16_t*)jb.w1_reg; p.w2 = (const h16_t*)jb.w2_reg; p.b1 = jb.b1; p.b2 = jb.b2;
-    p.xa = (h16_t*)jb.xa; p.mid = (h16_t*)jb.mid_a; p.y = (h16_t*)jb.y;
-    p.nseq = jb.p.nseq; p.L = jb.p.L; p.k = jb.p.k; p.dil = jb.p.dil; p.slope = jb.p.slope;
-    const size_t l = fwd_geometry(p, C);
-    if (!l) return EVT_ENOTSUP;
-    if (l > lds) lds = l;
-    cost[slot] = (double)p.total * (1.0 + 0.12 * jb.p.k);  // measured single launches: 20 / 21 / 21.5 us (C = 16), 21 / 25 / 29 (C = 32)
-  }
-  const int per_cu = (int)((160 * 1024) / lds) < 4 ? (int)((160 * 1024) / lds) : 4;
-  const long cap = 256L * per_cu;
-  const double tot = cost[0] + cost[1] + cost[2];
-  int end = 0;
-  for (int s = 0; s < 3; ++s) {
-    if (cost[s] > 0) {
-      long nb = (long)(cap * cost[s] / tot + 0.5);
-      const long need = (pm.job[s].total + 3) / 4;
-      if (nb > need) nb = need;
-      if (nb < 1) nb = 1;
-      end += (int)nb;
-    }
-    pm.blk_end[s] = end;
-  }
+  int end = 0, C = 0;
+  if (const int rc = plan_multi(jobs, njobs, pm, &lds, &end, &C, false)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (C == 16) {
     static bool attr = false;
@@ -313,6 +368,28 @@ int evt_resunit_fwd_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, void* 
     if (set_lds_once(&resunit_fwd_multi<32>, &attr)) return EVT_ELAUNCH;
     evt_set_last_tag("resunit_fwd_multi<bf16, 32, x%d>", njobs);
     hipLaunchKernelGGL((resunit_fwd_multi<32>), dim3(end), dim3(256), lds, st, pm);
+  }
+  return evt_check_launch();
+}
+
+int evt_resunit_fwd_multi_lens(const evt_resunit_fwd_job* jobs, int32_t njobs, const int32_t* lens, int32_t mul, void* stream) {
+  if (!lens || mul < 1) return EVT_EINVAL;
+  RUPML pl{};
+  size_t lds = 0;
+  int end = 0, C = 0;
+  if (const int rc = plan_multi(jobs, njobs, pl.m, &lds, &end, &C, true)) return rc;
+  pl.lens = lens; pl.mul = mul;
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 16) {
+    static bool attr = false;
+    if (set_lds_once(&resunit_fwd_multi_lens<16>, &attr)) return EVT_ELAUNCH;
+    evt_set_last_tag("resunit_fwd_multi<bf16, 16, x%d, lens>", njobs);
+    hipLaunchKernelGGL((resunit_fwd_multi_lens<16>), dim3(end), dim3(256), lds, st, pl);
+  } else {
+    static bool attr = false;
+    if (set_lds_once(&resunit_fwd_multi_lens<32>, &attr)) return EVT_ELAUNCH;
+    evt_set_last_tag("resunit_fwd_multi<bf16, 32, x%d, lens>", njobs);
+    hipLaunchKernelGGL((resunit_fwd_multi_lens<32>), dim3(end), dim3(256), lds, st, pl);
   }
   return evt_check_launch();
 }

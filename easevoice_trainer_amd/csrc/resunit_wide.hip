@@ -42,6 +42,8 @@ struct WUP {
   int xrows;             // staged input rows = P + 2 (hA + hB)
 };
 
+struct WUPL : WUP { const int32_t* lens; int mul; };   // + the rows' lengths: lens [nseq] in units of mul positions
+
 template <int C> __device__ __forceinline__ int wslot(int row, int slot) {
   // 16-byte slot `slot` of row `row` -> slot index inside the row: rows per 256-byte bank window = 512 / (2C)
   if constexpr (C == 64) return slot ^ (((row >> 1) & 3) << 1);
@@ -55,8 +57,13 @@ template <int C> __device__ __forceinline__ int wslot(int row, int slot) {
 // (mid_a, parked in the intermediate tile's own LDS rows: each lane reads its 8 bytes right before it overwrites them
 // with dmid) are all staged in the one pass at the top; the first two weight fragments of a convolution are requested
 // before the barrier in front of it; biases at the very top.
-template <int C, int WM, int WN, int NT1, int NT2, bool BWD, int R>
-__global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
+//
+// PT = WUPL (forward only, evt_resunit_wide_fwd_lens; RAG below): row s is live on [0, Ls), Ls = min(L, lens[s] * mul);
+// every test of a position against the sequence end takes Ls, and y on [Ls, L) is stored as zero.  PT = WUP is the
+// kernel as it was (Ls is p.L).
+template <int C, int WM, int WN, int NT1, int NT2, bool BWD, int R, typename PT = WUP>
+__global__ __launch_bounds__(256, 2) void resunit_wide(PT p) {
+  constexpr bool RAG = !std::is_same<PT, WUP>::value;
   constexpr int PITCH = C * 2;
   constexpr int SPR = C / 8;                 // 16-byte slots per row
   constexpr int MTW = C / 16 / WM;           // output-channel tiles per wave
@@ -78,6 +85,23 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
   const int ktot = NCH * p.k * 32;           // K elements per image row
   const int nks = NCH * p.k;                 // K steps of 32 (always even: NCH is)
   const int last = nks - 1;
+  const int Ls = [&]() {
+    if constexpr (RAG) {
+      const long l = (long)p.lens[seq] * p.mul;
+      return l < 0 ? 0 : (l < p.L ? (int)l : p.L);
+    } else {
+      return p.L;
+    }
+  }();
+  if constexpr (RAG) {
+    if (q0 >= Ls) {                          // a tile wholly in the dead tail: zeros, nothing to compute (whole block)
+      for (int idx = tid; idx < P * SPR; idx += 256) {
+        const int q = q0 + idx / SPR;
+        if (q < p.L) *reinterpret_cast<uint4*>(p.outB + sbase + (long)q * C + (idx % SPR) * 8) = make_uint4(0, 0, 0, 0);
+      }
+      return;
+    }
+  }
 
   float biasA[MTW][4], biasB[MTW][4];
 #pragma unroll
@@ -98,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
         const int idx = base + u * 256 + tid;
         const int r = idx / SPR, sl = idx - r * SPR;
         const int pos = pos0 + r;
-        v[u] = (idx < npieces && pos >= 0 && pos < p.L) ? *reinterpret_cast<const uint4*>(src + sbase + (long)pos * C + sl * 8)
+        v[u] = (idx < npieces && pos >= 0 && pos < Ls) ? *reinterpret_cast<const uint4*>(src + sbase + (long)pos * C + sl * 8)
                                                         : make_uint4(0, 0, 0, 0);
       }
 #pragma unroll
@@ -117,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
       const int o = r - hA - hB;
       if (o >= 0 && o < P) {
         *reinterpret_cast<uint4*>(rs + o * PITCH + wslot<C>(o, sl) * 16) = raw;
-        if (p.in_act && q0 + o < p.L) *reinterpret_cast<uint4*>(p.in_act + sbase + (long)(q0 + o) * C + sl * 8) = a;
+        if (p.in_act && q0 + o < Ls) *reinterpret_cast<uint4*>(p.in_act + sbase + (long)(q0 + o) * C + sl * 8) = a;
       }
     });
   } else {
@@ -217,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
     for (int j = 0; j < NT1; ++j) {
       const int m = m0 + j * 16 + n;
       const int pos = q0 - hB + m;
-      const bool inside = pos >= 0 && pos < p.L && m < P + 2 * hB;
+      const bool inside = pos >= 0 && pos < Ls && m < P + 2 * hB;
 #pragma unroll
       for (int i = 0; i < MTW; ++i) {
         const int c = (wm * MTW + i) * 16 + g * 4;
@@ -258,6 +282,14 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
       const int o = o0 + j * 16 + n;
       const int q = q0 + o;
       if (q >= p.L) continue;
+      if constexpr (RAG) {
+        if (q >= Ls) {                       // dead tail of a live tile: a clean zero for the next consumer
+#pragma unroll
+          for (int i = 0; i < MTW; ++i)
+            *reinterpret_cast<uint2*>(p.outB + sbase + (long)q * C + (wm * MTW + i) * 16 + g * 4) = make_uint2(0, 0);
+          continue;
+        }
+      }
 #pragma unroll
       for (int i = 0; i < MTW; ++i) {
         const int c = (wm * MTW + i) * 16 + g * 4;
@@ -281,8 +313,9 @@ __global__ __launch_bounds__(256, 2) void resunit_wide(WUP p) {
   }
 }
 
+// lens != NULL: the ragged forward (PT = WUPL), same geometry
 template <int C, int WM, int WN, int NT1, int NT2, bool BWD, int R = 4>
-int launch(WUP p, hipStream_t st) {
+int launch(WUP p, hipStream_t st, const int32_t* lens = nullptr, int mul = 1) {
   constexpr int P = 16 * NT2 * WN, MROWS = 16 * NT1 * WN;
   const int H = (p.k - 1) / 2, hA = p.dilA * H, hB = p.dilB * H;
   if (P + 2 * hB > MROWS) return EVT_ENOTSUP;
@@ -293,6 +326,23 @@ int launch(WUP p, hipStream_t st) {
   p.tps = (p.L + P - 1) / P;
   const size_t lds = (size_t)(((p.xrows + 7) & ~7) + MROWS + P) * C * 2;
   if (lds > 160 * 1024) return EVT_ENOTSUP;
+  if constexpr (!BWD) {
+    if (lens) {
+      static bool attr_l = false;
+      if (!attr_l) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&resunit_wide<C, WM, WN, NT1, NT2, false, R, WUPL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+          return EVT_ELAUNCH;
+        attr_l = true;
+      }
+      evt_set_last_tag("resunit_wide_fwd<bf16, %d, %dx%d, nt %d-%d, lens>", C, WM, WN, NT1, NT2);
+      WUPL pl{};
+      static_cast<WUP&>(pl) = p;
+      pl.lens = lens; pl.mul = mul;
+      hipLaunchKernelGGL((resunit_wide<C, WM, WN, NT1, NT2, false, R, WUPL>), dim3(p.nseq * p.tps), dim3(256), lds, st, pl);
+      return evt_check_launch();
+    }
+  }
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&resunit_wide<C, WM, WN, NT1, NT2, BWD, R>),
@@ -344,6 +394,21 @@ int evt_resunit_wide_fwd(const evt_resunit_params* a, const void* x, const void*
   // fragment-read -> MFMA chain with nothing else to run (t = 19 us + 2 x MFMA time over k = 3 / 7 / 11).
   if (a->C == 128) return launch<128, 4, 1, 11, 10, false, 4>(p, st);
   return launch<64, 4, 1, 11, 10, false, 4>(p, st);
+}
+
+int evt_resunit_wide_fwd_lens(const evt_resunit_params* a, const void* x, const void* w1_reg, const void* w2_reg,
+                              const float* b1, const float* b2, void* xa, void* mid_a, void* y, const int32_t* lens,
+                              int32_t mul, void* stream) {
+  if (!evt_resunit_wide_supported(a)) return EVT_ENOTSUP;
+  if (!x || !w1_reg || !w2_reg || !y || !lens || mul < 1) return EVT_EINVAL;
+  WUP p{};
+  p.in = (const h16_t*)x; p.wA = (const h16_t*)w1_reg; p.wB = (const h16_t*)w2_reg; p.bA = b1; p.bB = b2;
+  p.in_act = (h16_t*)xa; p.outA = (h16_t*)mid_a; p.outB = (h16_t*)y;
+  p.nseq = a->nseq; p.L = a->L; p.k = a->k; p.dilA = a->dil; p.dilB = 1; p.slope = a->slope; p.in_scale = 1.f;
+  hipStream_t st = (hipStream_t)stream;
+  // the tile shape of evt_resunit_wide_fwd: a live output is then the arithmetic of a one-row launch with L = Ls
+  if (a->C == 128) return launch<128, 4, 1, 11, 10, false, 4>(p, st, lens, mul);
+  return launch<64, 4, 1, 11, 10, false, 4>(p, st, lens, mul);
 }
 
 int evt_resunit_wide_bwd_data(const evt_resunit_params* a, const void* dy, float dy_scale, const void* xa, const void* mid_a,

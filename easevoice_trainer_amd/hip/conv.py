@@ -943,7 +943,72 @@ def resunit_bwd(s1, s2, dy, xa, mid_a, slope, dy_scale=1.0):
     return dx
 
 
-def res_unit(x, c1: EvtConv1d, c2: EvtConv1d, slope: float):
+def mask_tail(x, lens, mul=1, owner=None):
+    """x[s, t, :] = 0 for t >= lens[s] * mul, IN PLACE (x contiguous [nseq, L, C], lens int32 [nseq] on x's device): the dead
+    tails of a ragged batch in front of a consumer that has no masked load (csrc/elementwise.hip::evt_mask_tail)"""
+    if x.dim() != 3 or not x.is_contiguous():
+        raise L.EvtError("mask_tail takes a contiguous [nseq, L, C] tensor")
+    _check_lens(x, lens, mul)
+    e0 = _t0()
+    L.check(L.lib().evt_mask_tail(L.dt_of(x), L.ptr(x), L.ptr(lens), int(mul), x.size(0), x.size(1), x.size(2),
+                                  L.stream_ptr()), "evt_mask_tail")
+    if e0 is not None:
+        _t1_elt(e0, "mask_tail_kernel", x.numel() * x.element_size(), owner)
+    return x
+
+
+def _check_lens(x, lens, mul):
+    if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
+            or lens.numel() != x.size(0) or not lens.is_contiguous() or int(mul) < 1):
+        raise L.EvtError(f"ragged launch: lens must be a contiguous int32 [{x.size(0)}] tensor on {x.device} and mul >= 1")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise L.EvtError("the ragged (lens) paths of the vocoder are inference only: run them under torch.no_grad()")
+
+
+def _bias(m):
+    return m.bias.data if m.bias is not None else None
+
+
+def _res_unit_lens(x, s1, s2, slope, lens, mul):
+    """res_unit on a ragged batch, no grad: row s is live on [0, lens[s] * mul) and comes out with a zero tail.  Narrow, wide
+    or unfused exactly as ResUnitFn.forward chooses; the unfused path expects x with a zero tail already (the fused kernels
+    mask their loads) and masks behind each of its two convolutions, whose biases fill the tail."""
+    _check_lens(x, lens, mul)
+    m1, m2 = s1.module, s2.module
+    lib = L.lib()
+    fused = _resunit_params(s1, s2, x, slope)
+    if fused is not None:
+        y = torch.empty_like(x)
+        jobs = (L.ResUnitFwdJob * 1)()
+        jb = jobs[0]
+        jb.p = fused
+        jb.x, jb.w1_reg, jb.w2_reg = x.data_ptr(), s1.reg.data_ptr(), s2.reg.data_ptr()
+        jb.b1, jb.b2 = _dptr(_bias(m1)), _dptr(_bias(m2))
+        jb.xa, jb.mid_a, jb.y = None, None, y.data_ptr()
+        e0 = _t0()
+        L.check(lib.evt_resunit_fwd_multi_lens(jobs, 1, L.ptr(lens), int(mul), L.stream_ptr()), "evt_resunit_fwd_multi_lens")
+        if e0 is not None:
+            _t1_unit(e0, m1, m2, x)
+        return y
+    wide = _resunit_wide_params(s1, s2, x, slope)
+    if wide is not None:
+        y = torch.empty_like(x)
+        e0 = _t0()
+        L.check(lib.evt_resunit_wide_fwd_lens(C.byref(wide), L.ptr(x), L.ptr(s1.reg), L.ptr(s2.reg), L.ptr(_bias(m1)),
+                                              L.ptr(_bias(m2)), L.ptr(None), L.ptr(None), L.ptr(y), L.ptr(lens), int(mul),
+                                              L.stream_ptr()), "evt_resunit_wide_fwd_lens")
+        if e0 is not None:
+            _t1_unit(e0, m1, m2, x)
+        return y
+    xa = _lrelu(x, slope, m1)
+    mid_a = mask_tail(_fwd(s1, xa, None, 1.0, L.ACT_LRELU, slope), lens, mul, m1)
+    return mask_tail(_fwd(s2, mid_a, x, 1.0, L.ACT_NONE, 1.0), lens, mul, m2)
+
+
+def res_unit(x, c1: EvtConv1d, c2: EvtConv1d, slope: float, lens=None, mul: int = 1):
+    """lens (int32 [nseq], in units of `mul` positions): the no-grad path for a ragged batch, see _res_unit_lens"""
+    if lens is not None:
+        return _res_unit_lens(x, c1._slot, c2._slot, float(slope), lens, mul)
     return ResUnitFn.apply(x, c1._slot.bank.anchor, c1._slot, c2._slot, float(slope))
 
 
@@ -1091,9 +1156,36 @@ class ResStageFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
-def res_stage(x, blocks, slope: float, scale: float):
+def _res_stage_lens(x, plan, slope, scale, lens, mul):
+    """ResStageFn.forward on a ragged batch, no grad: the grouped launches mask their loads of x by the rows' lengths and
+    store zero tails, so the stage mean has a zero tail too; nothing is kept for a backward"""
+    _check_lens(x, lens, mul)
+    lib = L.lib()
+    cur = [x] * len(plan[0][0])
+    for pairs, ps in plan:
+        jobs = (L.ResUnitFwdJob * len(pairs))()
+        outs = []
+        for i, ((s1, s2), p) in enumerate(zip(pairs, ps)):
+            y = torch.empty_like(x)
+            jb = jobs[i]
+            jb.p = p
+            jb.x, jb.w1_reg, jb.w2_reg = cur[i].data_ptr(), s1.reg.data_ptr(), s2.reg.data_ptr()
+            jb.b1, jb.b2 = _dptr(_bias(s1.module)), _dptr(_bias(s2.module))
+            jb.xa, jb.mid_a, jb.y = None, None, y.data_ptr()
+            outs.append(y)
+        e0 = _t0()
+        L.check(lib.evt_resunit_fwd_multi_lens(jobs, len(pairs), L.ptr(lens), int(mul), L.stream_ptr()),
+                "evt_resunit_fwd_multi_lens")
+        if e0 is not None:
+            _t1_multi(e0, "fwd", pairs, x, False)
+        cur = outs
+    return _add3(cur[0], cur[1], cur[2], scale, torch.empty_like(x), plan[0][0][0][0].module)
+
+
+def res_stage(x, blocks, slope: float, scale: float, lens=None, mul: int = 1):
     """mean over `blocks` (ResBlock1 modules) of block(x), through the grouped kernels; None when the stage is not covered
-    (the caller then runs the blocks one by one)"""
+    (the caller then runs the blocks one by one).  lens (int32 [nseq], in units of `mul` positions): the no-grad path for a
+    ragged batch, chosen by the same plan."""
     plan = _stage_plan(x, blocks, slope)
     if plan is None:
         return None
@@ -1104,6 +1196,8 @@ def res_stage(x, blocks, slope: float, scale: float):
     # jobs are handed over in kernel-size order 3 / 7 / 11
     order = sorted(range(len(blocks)), key=lambda i: blocks[i].convs1[0].k)
     plan = [([pairs[i] for i in order], [ps[i] for i in order]) for pairs, ps in plan]
+    if lens is not None:
+        return _res_stage_lens(x, plan, float(slope), float(scale), lens, mul)
     return ResStageFn.apply(x, plan[0][0][0][0].bank.anchor, plan, float(slope), float(scale))
 
 

@@ -42,10 +42,54 @@ def synthesize_fragments(t2s, voice, batch_phones, all_phoneme_ids, all_bert_fea
     return out
 
 
+def _poll_groups(stream, stats, per_waiting):
+    """The outputs of a decode_stream generator, grouped by the poll that completed them: lists of outputs the session had
+    ready at the same time.  The session records every output in stream_stats["events"] (a finish / cancel / preempt event
+    per row; one "cancel" event without a slot for a request withdrawn while it waited, which is handed out once per
+    candidate = per_waiting times) before it yields the first of them, so after an output the events say how many more
+    are already there: those are taken at once, and the generator is never advanced into its next poll for a group.
+    stats() -> the session's stream_stats or None (a decoder that keeps none: every output is its own group)."""
+    seen, expected, received, group = 0, 0, 0, []
+    for o in stream:
+        received += 1
+        st = stats()
+        events = None if st is None else st.get("events")
+        if events is None:
+            yield [o]
+            continue
+        for kind, _steps, _r, slot in events[seen:]:
+            if kind != "admit":
+                expected += per_waiting if slot is None else 1
+        seen = len(events)
+        group.append(o)
+        if received >= expected:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def _decode_group(voice, dev, batch_phones, refer, kw, items):
+    """items: [(fragment index, y, idx)] of one poll, at most s2_batch of them -> their waveforms, through ONE decode_batch
+    call (a single fragment: the decode call of the one-by-one path)"""
+    with torch.no_grad():
+        if len(items) == 1:
+            r, y, idx = items[0]
+            sem = y[-idx:].unsqueeze(0).unsqueeze(0)
+            return [voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=1.0, **kw)[0, 0, :]]
+        sems = [y[-idx:] for _r, y, idx in items]
+        phones = [batch_phones[r].to(dev) for r, _y, _idx in items]
+        codes = torch.nn.utils.rnn.pad_sequence(sems, batch_first=True).unsqueeze(0)
+        text = torch.nn.utils.rnn.pad_sequence(phones, batch_first=True)
+        # one entry per row, all the same object: decode_batch encodes the shared reference(s) once
+        return voice.model.decode_batch(codes, [int(t.numel()) for t in sems], text, [int(t.numel()) for t in phones],
+                                        [refer] * len(items), **kw)
+
+
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
-                      choose=None, wide=False):
+                      choose=None, wide=False, s2_batch=1):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -64,8 +108,17 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     with the fragment's StreamOutputs in candidate order (a cancelled take has y = None); it returns the number of the
     take to keep, and only that take goes through the s2 decoder.  A fragment whose takes were all cancelled is yielded
     as (index, None) without a call.  The project ships no default rule: mean log-probability is no proven quality
-    criterion for this model (loops are likely sequences)."""
+    criterion for this model (loops are likely sequences).
+    s2_batch = k > 1 (with speed_factor == 1; any other speed decodes one by one as with k = 1): fragments whose tokens
+    the s1 session delivers from the SAME poll go through the s2 decoder in groups of at most k, one decode_batch call
+    per group (SynthesizerTrn.decode_batch: every row is what decode gives for it alone), and are yielded in the order
+    they arrived; cancelled and preempted fragments pass through as (index, None) in that order.  It never waits for a
+    later poll: a fragment that finishes alone is decoded alone.  With candidates > 1 the chosen takes go through the
+    groups.  decode_kwargs then go to decode_batch (noise_scale; a `noise` of batch 1 is shared by the rows)."""
     model, dev = t2s.model, t2s.device
+    s2_batch = int(s2_batch)
+    if s2_batch < 1:
+        raise ValueError(f"s2_batch = {s2_batch} must be >= 1")
     n = len(all_phoneme_ids)
     candidates = int(candidates)
     if candidates < 1:
@@ -89,13 +142,61 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             return voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]
 
+    if candidates > 1 and int(slots) < candidates:
+        raise ValueError(f"slots = {int(slots)} cannot hold the {candidates} candidates of one fragment")
+
+    def open_stream():
+        if candidates > 1:
+            return model.decode_stream(reqs, slots=min(int(slots), max(n, 1) * candidates), top_k=top_k, top_p=top_p,
+                                       temperature=temperature, early_stop_num=t2s.early_stop_num,
+                                       repetition_penalty=repetition_penalty, control=control, n=candidates, logprobs=True,
+                                       wide=wide, **(sample_kwargs or {}))
+        return model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
+                                   early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
+                                   control=control, wide=wide, **(sample_kwargs or {}))
+
+    if s2_batch > 1 and speed_factor == 1.0:
+        stream = open_stream()
+
+        def stats():
+            owner = model._infer() if hasattr(model, "_infer") else model
+            return getattr(owner, "stream_stats", None)
+
+        takes = {}
+        for group in _poll_groups(stream, stats, candidates):
+            ready = []               # this poll's fragments in arrival order: (index, y, idx), y None = no decode
+            for o in group:
+                if candidates == 1:
+                    r, y, idx = o
+                    ready.append((r, None, None) if y is None or idx is None else (r, y, idx))
+                    continue
+                got = takes.setdefault(o.request, {})
+                got[o.candidate] = o
+                if len(got) < candidates:
+                    continue
+                outs = [got[c] for c in range(candidates)]
+                del takes[o.request]
+                if all(t.y is None or t.idx is None for t in outs):
+                    ready.append((o.request, None, None))
+                    continue
+                t = outs[int(choose(o.request, outs))]
+                ready.append((o.request, None, None) if t.y is None or t.idx is None else (o.request, t.y, t.idx))
+            while ready:
+                if ready[0][1] is None:
+                    yield ready.pop(0)[0], None
+                    continue
+                # up to s2_batch fragments to decode, with the cancelled ones that arrived between them
+                take, live = 0, 0
+                while take < len(ready) and (ready[take][1] is None or live < s2_batch):
+                    live += ready[take][1] is not None
+                    take += 1
+                chunk, ready = ready[:take], ready[take:]
+                wavs = iter(_decode_group(voice, dev, batch_phones, refer, kw, [c for c in chunk if c[1] is not None]))
+                for r, y, _idx in chunk:
+                    yield r, (None if y is None else next(wavs))
+        return
+    stream = open_stream()
     if candidates > 1:
-        if int(slots) < candidates:
-            raise ValueError(f"slots = {int(slots)} cannot hold the {candidates} candidates of one fragment")
-        stream = model.decode_stream(reqs, slots=min(int(slots), max(n, 1) * candidates), top_k=top_k, top_p=top_p,
-                                     temperature=temperature, early_stop_num=t2s.early_stop_num,
-                                     repetition_penalty=repetition_penalty, control=control, n=candidates, logprobs=True,
-                                     wide=wide, **(sample_kwargs or {}))
         takes = {}
         for o in stream:
             got = takes.setdefault(o.request, {})
@@ -110,9 +211,6 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
             t = outs[int(choose(o.request, outs))]
             yield o.request, (None if t.y is None or t.idx is None else audio(o.request, t.y, t.idx))
         return
-    stream = model.decode_stream(reqs, slots=max(1, min(int(slots), n)), top_k=top_k, top_p=top_p, temperature=temperature,
-                                 early_stop_num=t2s.early_stop_num, repetition_penalty=repetition_penalty,
-                                 control=control, wide=wide, **(sample_kwargs or {}))
     for r, y, idx in stream:
         if y is None or idx is None:       # cancelled, or preempted with partial tokens: no s2 decode
             yield r, None

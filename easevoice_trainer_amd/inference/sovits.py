@@ -13,7 +13,7 @@ from ..runtime import ModelRuntime
 
 class SoVITSVoice:
     """`decode(codes, text, refer, noise_scale, speed)` and `extract_latent(ssl)` of SynthesizerTrn (models.py:974-1018)
-    on a loaded export."""
+    on a loaded export, and `decode_batch` for a ragged batch of fragments."""
 
     def __init__(self, weights, device="cuda:0", dtype=torch.bfloat16):
         ck = torch.load(weights, map_location="cpu", weights_only=False) if isinstance(weights, str) else weights
@@ -42,6 +42,16 @@ class SoVITSVoice:
         refer = [mv(r) for r in refer] if isinstance(refer, (list, tuple)) else mv(refer)
         return self.model.decode(mv(codes), mv(text), refer, noise_scale=noise_scale, speed=speed,
                                  noise=None if noise is None else mv(noise))
+
+    @torch.no_grad()
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None):
+        """SynthesizerTrn.decode_batch: a ragged batch of fragments in one pass -> a list of B 1-D waveforms, row b what
+        decode gives for fragment b alone"""
+        L.set_half(self.dtype)
+        mv = lambda t: t.to(self.device)
+        mvr = lambda r: [mvr(e) for e in r] if isinstance(r, (list, tuple)) else mv(r)
+        return self.model.decode_batch(mv(codes), code_lens, mv(text), text_lens, mvr(refer), noise_scale=noise_scale,
+                                       noise=None if noise is None else mv(noise))
 
     @torch.no_grad()
     def extract_latent(self, ssl):

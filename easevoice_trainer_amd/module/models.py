@@ -17,6 +17,7 @@ mrte_model.py:9-61, core_vq.py:172-228), re-laid-out for the hardware:
 There is no CPU / eager fallback: the modules need a WeightBank (hip/conv.py) and a GPU.
 """
 
+import functools
 import os
 
 import torch
@@ -24,7 +25,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from ..hip import lib as L
-from ..hip.conv import Add3ScaleFn, EvtConv1d, GatedActFn, res_stage, res_unit
+from ..hip.conv import Add3ScaleFn, EvtConv1d, GatedActFn, mask_tail, res_stage, res_unit
 from ..hip.enc import new_site, rel_self_attention, unbind_rows, wn_residual, wn_residual_last
 from ..hip.frontend import RvqEncoder, ncl_to_nlc
 from ..hip.wn import wn_stack
@@ -528,9 +529,9 @@ class ResBlock1(nn.Module):
             EvtConv1d(channels, channels, kernel_size, dilation=1, padding=get_padding(kernel_size, 1), weight_norm=True)
             for _ in dilation])
 
-    def forward(self, x):
+    def forward(self, x, lens=None, mul=1):
         for c1, c2 in zip(self.convs1, self.convs2):
-            x = res_unit(x, c1, c2, LRELU_SLOPE)
+            x = res_unit(x, c1, c2, LRELU_SLOPE) if lens is None else res_unit(x, c1, c2, LRELU_SLOPE, lens, mul)
         return x
 
 
@@ -558,20 +559,39 @@ class Generator(nn.Module, _ComputeDtype):
         if gin_channels != 0:
             self.cond = pointwise(gin_channels, upsample_initial_channel)
 
-    def forward(self, x, g=None):
-        """x [B, T, inter] -> waveform [B, T*prod(up), 1]"""
-        x = self.conv_pre(x.to(self.cd).contiguous())
+    def forward(self, x, g=None, lens=None):
+        """x [B, T, inter] -> waveform [B, T*prod(up), 1].  lens (int32 [B], frames; inference, no grad): a ragged batch --
+        row b is live on its first lens[b] frames and comes out as what forward gives for that row alone; behind it the
+        three samples on which conv_post (k = 7, no bias) still sees the row's end, then zeros: callers cut rows to
+        length.  Every stage keeps the dead tails at zero in front of its convolutions (whose biases would otherwise
+        bleed into a row's last samples): the fused ResBlock kernels mask their loads and store zero tails, mask_tail
+        does it for the rest; a single convolution of a zero-tailed input is exact on the live part."""
+        x = x.to(self.cd).contiguous()
+        if lens is not None:
+            # conv_pre reads three frames behind a row's end: zeros there, in a copy (the caller's tensor is not written)
+            x = mask_tail(x.clone(), lens, 1, self.conv_pre)
+        x = self.conv_pre(x)
         if g is not None:
             x = (x + self.cond(g).unsqueeze(1)).to(self.cd)
+        mul = 1
+        if lens is not None:
+            x = mask_tail(x.contiguous(), lens, 1, self.conv_pre)     # the first up-sampler has no masked load
         for i in range(self.num_upsamples):
             x = self.ups[i](x, in_slope=LRELU_SLOPE)          # leaky_relu(0.1) fused on load
             blocks = [self.resblocks[i * self.num_kernels + j] for j in range(self.num_kernels)]
+            if lens is not None:
+                mul *= self.ups[i].stride
             if x.is_cuda:
                 # narrow stages: step j of the three blocks is one grouped launch each way (hip/conv.py::ResStageFn)
-                xs = res_stage(x, blocks, LRELU_SLOPE, 1.0 / self.num_kernels)
+                xs = res_stage(x, blocks, LRELU_SLOPE, 1.0 / self.num_kernels, lens, mul)
                 if xs is not None:
                     x = xs
                     continue
+            if lens is not None:
+                # the up-sampler's bias sits behind each row's end: the unfused steps below (and the three residual sums)
+                # take a zero tail; the wide fused kernel would mask its own load
+                x = mask_tail(x, lens, mul, self.ups[i])
+                blocks = [functools.partial(b, lens=lens, mul=mul) for b in blocks]
             lane = None
             if x.is_cuda and len(blocks) == 3:
                 from ..hip.disc import _On, dec_lane
@@ -873,6 +893,70 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
             z = self.flow(z_p, ym, g=ge, reverse=True, lens=y_lengths.to(torch.int32))
             o = self.dec(z * ym, g=ge)
         return o.transpose(1, 2)
+
+    def _style(self, refer):
+        """one reference spectrogram [1, spec, Tr], or a list of them (their style vectors averaged, as decode does) -> [1, gin]"""
+        ges = []
+        for r in (refer if isinstance(refer, (list, tuple)) else [refer]):
+            r_cl = r.transpose(1, 2)
+            r_cl = r_cl if self.version == "v1" else r_cl[..., :704]
+            ges.append(self.ref_enc(r_cl, torch.ones(r_cl.size(0), r_cl.size(1), 1, device=r.device)))
+        return torch.stack(ges, 0).mean(0)
+
+    @torch.no_grad()
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None):
+        """decode for a RAGGED batch of fragments in one pass: codes [1, B, Tcmax] and text [B, Ttmax] right-padded,
+        code_lens / text_lens [B] (tensors or sequences of ints).  refer: one reference spectrogram [1, spec, Tr] (or a
+        list of them, averaged) shared by all rows, or a list of exactly B entries, one per row (a list of length B is
+        always read that way), each a spectrogram or a list of them; reference lengths may differ (the style encoder runs per reference: it does not
+        mask in front of its convolutions, so references are never padded together).  noise [B, inter, >= Tmax] or None.
+        Returns a list of B 1-D waveforms of code_lens[b] * (2 if 25hz) * prod(upsample_rates) samples, row b being what
+        decode gives for fragment b alone: the encoders, MRTE, the flow and the style attention take the lengths as
+        they do in training, and the vocoder runs its length-aware forward (Generator.forward(lens=...)).  No speed
+        parameter: the reference defines its interpolation per sequence, anything but 1 stays on decode."""
+        dev = codes.device
+        if codes.dim() != 3 or codes.size(0) != 1 or text.dim() != 2 or text.size(0) != codes.size(1):
+            raise L.EvtError(f"decode_batch takes codes [1, B, Tc] and text [B, Tt], got {tuple(codes.shape)} and {tuple(text.shape)}")
+        B, Tc = codes.size(1), codes.size(2)
+        code_lens = torch.as_tensor(code_lens, dtype=torch.long).reshape(-1)
+        text_lens = torch.as_tensor(text_lens, dtype=torch.long).reshape(-1)
+        cl, tl = [int(v) for v in code_lens.tolist()], [int(v) for v in text_lens.tolist()]
+        if len(cl) != B or len(tl) != B or min(cl) < 1 or max(cl) > Tc or min(tl) < 1 or max(tl) > text.size(1):
+            raise L.EvtError(f"decode_batch: code_lens / text_lens must hold {B} lengths in [1, {Tc}] / [1, {text.size(1)}]")
+        f = 2 if self.semantic_frame_rate == "25hz" else 1
+        T = Tc * f
+        amp = self.cd in (torch.bfloat16, torch.float16)
+        with torch.autocast("cuda", dtype=self.cd if amp else torch.bfloat16, enabled=amp):
+            per_row = isinstance(refer, (list, tuple)) and len(refer) == B
+            if per_row:
+                seen = {}        # rows that name the same reference object share one pass of the style encoder
+                for r in refer:
+                    if id(r) not in seen:
+                        seen[id(r)] = self._style(r)
+                ge = torch.cat([seen[id(r)] for r in refer], 0)
+            else:
+                ge = self._style(refer)
+                if ge.size(0) != 1:
+                    raise L.EvtError("decode_batch: a shared reference is one spectrogram [1, spec, Tr] (or a list of them)")
+                ge = ge.expand(B, -1).contiguous()
+            y_lengths = (code_lens * f).to(dev)
+            text_lengths = text_lens.to(dev)
+            quantized = self.quantizer.decode(codes)
+            if f == 2:
+                quantized = quantized.repeat_interleave(2, dim=1)
+            y_mask = commons.sequence_mask(y_lengths, T).unsqueeze(-1).to(torch.float32)
+            text_mask = commons.sequence_mask(text_lengths, text.size(1)).unsqueeze(-1).to(torch.float32)
+            _x, m_p, logs_p = self.enc_p(quantized, y_mask, text, text_mask, ge, y_lengths, text_lengths)
+            if noise is None:
+                noise = torch.randn(B, m_p.size(2), m_p.size(1), device=m_p.device)
+            eps = noise[:, :, :m_p.size(1)].transpose(1, 2).to(m_p.dtype)
+            z_p = m_p + eps * torch.exp(logs_p) * noise_scale
+            ym = y_mask.to(self.cd)
+            lens32 = y_lengths.to(torch.int32)
+            z = self.flow(z_p, ym, g=ge, reverse=True, lens=lens32)
+            o = self.dec(z * ym, g=ge, lens=lens32)                       # [B, T * up, 1], zero tails
+        up = o.size(1) // T
+        return [o[b, :cl[b] * f * up, 0] for b in range(B)]
 
     def forward(self, ssl, y, y_lengths, text, text_lengths, eps=None, ids_slice=None):
         """ssl [B, 768, T], y [B, spec, T] linear spectrogram, text [B, Tt] -> same tuple as the reference:

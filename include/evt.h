@@ -226,6 +226,15 @@ typedef struct evt_resunit_fwd_job {
 } evt_resunit_fwd_job;
 int evt_resunit_fwd_multi(const evt_resunit_fwd_job* jobs, int32_t njobs, void* stream);
 
+/* evt_resunit_fwd_multi for a RAGGED batch (inference): row s is live on positions [0, Ls), Ls = min(L, lens[s] * mul),
+ * and stored with stride L as before; lens: device int32 [nseq], shared by the jobs (which therefore have one nseq and
+ * L); mul: samples of this stage per unit of lens (lens in frames, mul = the product of the up-sampling rates so far).
+ * x at positions >= Ls reads as zero whatever the memory holds, the intermediate is zero there (c2's padding), y on
+ * [Ls, L) is STORED as zero, xa / mid_a (may be NULL) are written on the live part only.  Tiles start at the row's
+ * position 0, so a live output is bit for bit what the one-row launch with L = Ls gives. */
+int evt_resunit_fwd_multi_lens(const evt_resunit_fwd_job* jobs, int32_t njobs, const int32_t* lens, int32_t mul,
+                               void* stream);
+
 /* The whole backward of the same step in ONE launch (what torch.autograd runs as two conv backward-data, two conv
  * backward-weight and two bias reductions for modules.py:299-308):
  *   dmid = (c2^T dy') * lrelu'(mid_a),  dx = (c1^T dmid) * lrelu'(xa) + dy',  dy' = dy * dy_scale (rounded to bf16: the
@@ -262,6 +271,11 @@ int evt_resunit_bwd_multi(const evt_resunit_bwd_job* jobs, int32_t njobs, float*
 int32_t evt_resunit_wide_supported(const evt_resunit_params* p);
 int evt_resunit_wide_fwd(const evt_resunit_params* p, const void* x, const void* w1_reg, const void* w2_reg, const float* b1,
                          const float* b2, void* xa, void* mid_a, void* y, void* stream);
+/* evt_resunit_wide_fwd for a ragged batch: lens / mul and the treatment of x, the intermediate, y, xa and mid_a (both may
+ * be NULL) as in evt_resunit_fwd_multi_lens. */
+int evt_resunit_wide_fwd_lens(const evt_resunit_params* p, const void* x, const void* w1_reg, const void* w2_reg,
+                              const float* b1, const float* b2, void* xa, void* mid_a, void* y, const int32_t* lens,
+                              int32_t mul, void* stream);
 int evt_resunit_wide_bwd_data(const evt_resunit_params* p, const void* dy, float dy_scale, const void* xa, const void* mid_a,
                               const void* w1_alt, const void* w2_alt, void* dmid, void* dx, void* stream);
 
@@ -307,6 +321,12 @@ int evt_wn_layer_fwd(int32_t dtype, const void* x, const void* w_in_frag, const 
 /* out = (a + b + c) * scale ; b, c may be NULL.  (Generator stage mean, models.py:457-466) */
 int evt_add3_scale(int32_t dtype, const void* a, const void* b, const void* c, float scale, void* out,
                    int64_t n, void* stream);
+
+/* x[s][t][:] = 0 for t >= lens[s] * mul, in place; x [nseq][L][C], lens device int32 [nseq].  The dead tails of a ragged
+ * batch in front of a consumer that has no masked load (the vocoder's first up-sampler, the unfused ResBlock steps).
+ * C * element size a multiple of 16, x 16-byte aligned. */
+int evt_mask_tail(int32_t dtype, void* x, const int32_t* lens, int32_t mul, int32_t nseq, int32_t L, int32_t C,
+                  void* stream);
 
 /* out = leaky_relu(x, slope).  The HiFi-GAN residual unit (modules.py:299-308) keeps an activated copy of its input
  * so that its convolutions and weight gradients take plain operands (LDS-DMA kernels).  16-byte aligned. */

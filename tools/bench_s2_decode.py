@@ -1,0 +1,132 @@
+"""Throughput of the s2 decoder on finished fragments: SynthesizerTrn.decode one fragment at a time (what
+inference/pipeline.py::synthesize_stream does per fragment) against SynthesizerTrn.decode_batch on groups of 4, 8 and 16
+fragments of different lengths, in the same process.
+
+Workload: 64 fragments of 2..10 s (seeded lengths, 25 codes and 12 phonemes per second), one reference spectrogram,
+configs/s2.json at the benchmark's model size with random-init weights, bf16.  Groups are taken in arrival order (no
+sorting by length: a stream cannot choose which fragments finish together), so a group pads to its longest member.
+
+Protocol: every mode runs once untimed (all its shapes are then warm), then --reps timed passes with the modes alternated;
+a pass is timed with device events around all its calls and ends in a synchronise.  Reported per mode: the median pass,
+fragments/s and audio-seconds/s, and the spread (min / max seconds).  The yardstick is the `one` line of the same run.
+A measurement path without a GPU fails.
+
+    python tools/bench_s2_decode.py [--reps 5] [--fragments 64] [--out profiles/s2_decode_batch.json]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+
+os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")   # before the HIP runtime loads: easevoice_trainer_amd/__init__.py
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def workload(n, seed=11):
+    rnd = random.Random(seed)
+    g = torch.Generator().manual_seed(seed)
+    secs = [rnd.uniform(2.0, 10.0) for _ in range(n)]
+    codes = [torch.randint(0, 1024, (max(1, round(s * 25)),), generator=g) for s in secs]
+    texts = [torch.randint(0, 732, (max(1, round(s * 12)),), generator=g) for s in secs]
+    refer = torch.rand(1, 1025, 200, generator=g) * 2.0
+    return codes, texts, refer
+
+
+def build_voice(dev, dtype):
+    from easevoice_trainer_amd.inference.sovits import SoVITSVoice
+    from easevoice_trainer_amd.module import models
+
+    hps = json.load(open(os.path.join(ROOT, "configs", "s2.json")))
+    torch.manual_seed(hps["train"]["seed"])
+    net = models.SynthesizerTrn(hps["data"]["filter_length"] // 2 + 1, hps["train"]["segment_size"] // hps["data"]["hop_length"],
+                                n_speakers=hps["data"]["n_speakers"], **hps["model"])
+    cb = net.quantizer.vq.layers[0]._codebook
+    with torch.no_grad():
+        cb.embed.normal_()
+        cb.inited.fill_(1.0)
+    weight = {k: v.detach().clone() for k, v in net.state_dict().items() if "enc_q" not in k}
+    return SoVITSVoice({"weight": weight, "config": hps, "info": "bench"}, device=str(dev), dtype=dtype)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fragments", type=int, default=64)
+    ap.add_argument("--batches", type=int, nargs="+", default=[4, 8, 16])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "s2_decode_batch.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise RuntimeError("bench_s2_decode needs a GPU: nothing is measured without one")
+    dev = torch.device("cuda:0")
+    voice = build_voice(dev, torch.bfloat16)
+    codes, texts, refer = workload(args.fragments)
+    codes = [c.to(dev) for c in codes]
+    texts = [t.to(dev) for t in texts]
+    refer = refer.to(dev)
+    audio_s = sum(c.numel() for c in codes) / 25.0
+    pad = torch.nn.utils.rnn.pad_sequence
+
+    def run_one():
+        return [voice.decode(c.view(1, 1, -1), t.view(1, -1), refer)[0, 0] for c, t in zip(codes, texts)]
+
+    def run_batch(k):
+        out = []
+        for i in range(0, len(codes), k):
+            cs, ts = codes[i:i + k], texts[i:i + k]
+            out += voice.decode_batch(pad(cs, batch_first=True).unsqueeze(0), [c.numel() for c in cs],
+                                      pad(ts, batch_first=True), [t.numel() for t in ts], refer)
+        return out
+
+    modes = [("one", run_one)] + [(f"batch{k}", (lambda k=k: run_batch(k))) for k in args.batches]
+    for name, fn in modes:                        # warm-up: every shape of every mode once
+        outs = fn()
+        torch.cuda.synchronize()
+        assert [o.numel() for o in outs] == [c.numel() * 2 * 640 for c in codes], name
+        assert all(bool(torch.isfinite(o).all()) for o in outs), name
+    # same inputs, same prior noise: a batched row against the row alone (bf16)
+    noise = torch.randn(4, 192, 2 * max(c.numel() for c in codes[:4]) + 8, device=dev)
+    got = voice.decode_batch(pad(codes[:4], batch_first=True).unsqueeze(0), [c.numel() for c in codes[:4]],
+                             pad(texts[:4], batch_first=True), [t.numel() for t in texts[:4]], refer, noise=noise)
+    check = []
+    for b in range(4):
+        a = voice.decode(codes[b].view(1, 1, -1), texts[b].view(1, -1), refer, noise=noise[b:b + 1])[0, 0].float()
+        check.append(float((got[b].float() - a).abs().max() / (a.abs().max() + 1e-12)))
+    times = {name: [] for name, _ in modes}
+    for _ in range(args.reps):
+        for name, fn in modes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / 1e3)
+    res = {"tool": "tools/bench_s2_decode.py", "device": torch.cuda.get_device_name(0), "dtype": "bf16",
+           "fragments": len(codes), "audio_seconds": round(audio_s, 2), "reps": args.reps,
+           "fragment_seconds_min_max": [min(c.numel() for c in codes) / 25.0, max(c.numel() for c in codes) / 25.0],
+           "batched_row_vs_alone_rel_maxabs": [round(v, 5) for v in check], "modes": {}}
+    for name, _ in modes:
+        v = sorted(times[name])
+        med = v[len(v) // 2]
+        res["modes"][name] = {"seconds_median": round(med, 4), "seconds_min": round(v[0], 4), "seconds_max": round(v[-1], 4),
+                              "fragments_per_s": round(len(codes) / med, 1), "audio_s_per_s": round(audio_s / med, 1)}
+    base = res["modes"]["one"]["seconds_median"]
+    for name, m in res["modes"].items():
+        m["speedup_vs_one"] = round(base / m["seconds_median"], 3)
+    best = max((n for n in res["modes"] if n != "one"), key=lambda n: res["modes"][n]["speedup_vs_one"])
+    res["verdict"] = (f"{best} is {res['modes'][best]['speedup_vs_one']}x the one-at-a-time path"
+                      if res["modes"][best]["speedup_vs_one"] > 1.0 else "no batch size beats the one-at-a-time path")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
