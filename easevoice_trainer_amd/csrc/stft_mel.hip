@@ -181,6 +181,7 @@ __global__ __launch_bounds__(256) void mel_bwd_kernel(const float* dmel, const f
 extern "C" {
 
 int64_t evt_mel_workspace_floats(int32_t nseq, int32_t wav_len, int32_t n_fft, int32_t hop, int32_t n_mels) {
+  if (hop <= 0) return 0;  // no frames to hold: evt_mel_fwd / evt_mel_bwd refuse this geometry
   const int pad = (n_fft - hop) / 2;
   const int frames = (wav_len + 2 * pad - n_fft) / hop + 1;
   return (int64_t)nseq * frames * (2 * (n_fft / 2 + 1) + n_mels);

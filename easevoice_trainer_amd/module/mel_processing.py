@@ -59,6 +59,8 @@ class _MelFn(torch.autograd.Function):
     def forward(ctx, wav, window, basis, n_fft, hop, want_spec):
         nseq, wav_len = wav.shape
         n_mels = basis.size(0)
+        if hop <= 0:
+            raise L.EvtError(f"hop_size {hop}: a positive hop is needed")
         pad = (n_fft - hop) // 2
         frames = (wav_len + 2 * pad - n_fft) // hop + 1
         lib = L.lib()

@@ -360,7 +360,7 @@ int evt_mel_fwd(const float* wav, const float* window, const float* mel_basis, f
 /* dwav[nseq][wav_len] = d(sum(dmel * mel))/d(wav); ws is the (re,im,mag,melpre) workspace written by fwd. */
 int evt_mel_bwd(const float* dmel, const float* window, const float* mel_basis, const float* ws_spec_re_im,
                 float* dwav, int32_t nseq, int32_t wav_len, int32_t n_fft, int32_t hop, int32_t n_mels, void* stream);
-/* workspace floats needed by evt_mel_fwd/bwd */
+/* workspace floats needed by evt_mel_fwd/bwd; 0 for hop <= 0 (which they refuse) */
 int64_t evt_mel_workspace_floats(int32_t nseq, int32_t wav_len, int32_t n_fft, int32_t hop, int32_t n_mels);
 
 /* ---------------------------------------------------------------------------------------

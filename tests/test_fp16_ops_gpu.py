@@ -17,6 +17,7 @@ import test_mha_gpu as TM
 import test_mpd_fold_gpu as TF
 import test_resunit_bwd_gpu as TRB
 import test_resunit_gpu as TR
+import test_seg_loss_gpu as TS
 
 pytestmark = pytest.mark.gpu
 F16 = torch.float16
@@ -91,6 +92,13 @@ def test_discriminator_losses_fold_f16(gpu, f16):
         TF.test_fold_equals_torch_composition(gpu, T, F16)
     for layout in ("channels_last_views", "bct_contiguous"):
         TK.test_masked_kl_matches_reference(gpu, layout, F16, 173)
+
+
+def test_segment_losses_f16(gpu, f16):
+    """the segment-loss kernel in the IEEE-half build: the dyadic (bit-exact) and the alignment case bodies"""
+    for name in TS.R.SEG_LISTS:
+        TS.dyadic_case(gpu, F16, name)
+    TS.alignment_case(gpu, F16)
 
 
 def test_a_bf16_tensor_is_refused_while_the_f16_build_is_selected(gpu, f16):
