@@ -5,6 +5,7 @@
 //   weight_norm            src/easevoice/module/modules.py:162,174,184,228-296; models.py:427-436,486-536,563-574
 //   stage mean             src/easevoice/module/models.py:457-466
 //   gated activation       src/easevoice/module/commons.py:94-101
+//   speed resampling       src/easevoice/module/models.py:246-248
 //   feature/LSGAN losses   src/easevoice/module/losses.py:7-43
 //   AdamW, grad norm       src/train/sovits.py:294-319,505,522; src/easevoice/module/commons.py:140-155
 #include "evt_common.h"
@@ -354,6 +355,42 @@ __global__ void mask_tail_kernel(uint4* x, const int32_t* lens, int mul, int L, 
   }
 }
 
+// y[s][j][:] = linear resampling of row s of x from Ti = in_lens[s] to To = out_lens[s] positions (upsample_linear1d with
+// align_corners = False, evaluated in fp32, rounded once to T), 0 for j >= To: the per-row speed of a ragged decode
+// (models.py:246-248 per sequence).  One 16-byte vector of y per lane and step; x is read on [0, Ti) only -- both taps are
+// held below Ti -- and every vector of y is stored, so no mask launch follows.  To == Ti gives src == j and l1 == 0: a copy,
+// through the same arithmetic.  cpr = 16-byte vectors per position
+template <typename T>
+__global__ void resample_rows_kernel(const uint4* x, const int32_t* in_lens, const int32_t* out_lens, int Lin, int Lout,
+                                     int cpr, long nv, uint4* y) {
+  constexpr int V = 16 / sizeof(T);
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / cpr;
+    const int cv = (int)(i - row * cpr);
+    const int seq = (int)(row / Lout);
+    const int j = (int)(row - (long)seq * Lout);
+    const int Ti = min(max(in_lens[seq], 0), Lin), To = min(max(out_lens[seq], 0), Lout);
+    uint4 out = make_uint4(0, 0, 0, 0);
+    if (j < To && Ti > 0) {
+      const float scale = (float)Ti / (float)To;
+      const float src = fmaxf(scale * (j + 0.5f) - 0.5f, 0.f);
+      const int i0 = min((int)src, Ti - 1);                 // (int)src < Ti in exact arithmetic; held there in fp32 too
+      const bool inner = i0 < Ti - 1;
+      const int i1 = i0 + inner;
+      // on the row's last position both taps are that position: weight 0 instead of src - i0, so that the result is x there
+      // exactly and not (1 - l1) x + l1 x with its roundings (a row of one position comes out as that position)
+      const float l1 = inner ? src - (float)i0 : 0.f, l0 = 1.f - l1;
+      const uint4 a = x[((long)seq * Lin + i0) * cpr + cv], b = x[((long)seq * Lin + i1) * cpr + cv];
+      const T* ha = reinterpret_cast<const T*>(&a);
+      const T* hb = reinterpret_cast<const T*>(&b);
+      T* ho = reinterpret_cast<T*>(&out);
+#pragma unroll
+      for (int e = 0; e < V; ++e) ho[e] = from_f<T>(l0 * to_f<T>(ha[e]) + l1 * to_f<T>(hb[e]));
+    }
+    y[i] = out;
+  }
+}
+
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
 template <typename T>
@@ -695,6 +732,23 @@ int evt_mask_tail(int32_t dtype, void* x, const int32_t* lens, int32_t mul, int3
   const long nv = (long)nseq * L * (C / per);
   hipLaunchKernelGGL(mask_tail_kernel, dim3(grid_for(nv)), dim3(256), 0, (hipStream_t)stream, (uint4*)x, lens, (int)mul,
                      (int)L, C / per, nv);
+  return evt_check_launch();
+}
+
+int evt_resample_rows(int32_t dtype, const void* x, const int32_t* in_lens, const int32_t* out_lens, int32_t nseq,
+                      int32_t Lin, int32_t Lout, int32_t C, void* y, void* stream) {
+  if (!x || !in_lens || !out_lens || !y || nseq <= 0 || Lin <= 0 || Lout <= 0 || C <= 0) return EVT_EINVAL;
+  if (dtype != EVT_DT_HALF && dtype != EVT_DT_F32) return EVT_EINVAL;
+  const int per = dtype == EVT_DT_F32 ? 4 : 8;             // elements per 16-byte vector
+  if (C % per || (((uintptr_t)x | (uintptr_t)y) & 15)) return EVT_EINVAL;
+  const long nv = (long)nseq * Lout * (C / per);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == EVT_DT_HALF)
+    hipLaunchKernelGGL(resample_rows_kernel<h16_t>, dim3(grid_for(nv)), dim3(256), 0, st, (const uint4*)x, in_lens,
+                       out_lens, (int)Lin, (int)Lout, C / per, nv, (uint4*)y);
+  else
+    hipLaunchKernelGGL(resample_rows_kernel<float>, dim3(grid_for(nv)), dim3(256), 0, st, (const uint4*)x, in_lens,
+                       out_lens, (int)Lin, (int)Lout, C / per, nv, (uint4*)y);
   return evt_check_launch();
 }
 

@@ -957,6 +957,24 @@ def mask_tail(x, lens, mul=1, owner=None):
     return x
 
 
+def resample_rows(x, in_lens, out_lens, Lout, owner=None):
+    """x [nseq, Lin, C] contiguous -> y [nseq, Lout, C]: row s resampled linearly from in_lens[s] to out_lens[s] positions
+    (F.interpolate(mode="linear") on the row alone, evaluated in fp32), zero behind out_lens[s]; in_lens / out_lens int32
+    [nseq] on x's device.  x is not read behind a row's in_lens and all of y is written
+    (csrc/elementwise.hip::evt_resample_rows)"""
+    if x.dim() != 3 or not x.is_contiguous() or int(Lout) < 1:
+        raise L.EvtError("resample_rows takes a contiguous [nseq, Lin, C] tensor and Lout >= 1")
+    _check_lens(x, in_lens, 1)
+    _check_lens(x, out_lens, 1)
+    y = torch.empty(x.size(0), int(Lout), x.size(2), dtype=x.dtype, device=x.device)
+    e0 = _t0()
+    L.check(L.lib().evt_resample_rows(L.dt_of(x), L.ptr(x), L.ptr(in_lens), L.ptr(out_lens), x.size(0), x.size(1),
+                                      int(Lout), x.size(2), L.ptr(y), L.stream_ptr()), "evt_resample_rows")
+    if e0 is not None:
+        _t1_elt(e0, "resample_rows_kernel", (x.numel() + y.numel()) * x.element_size(), owner)
+    return y
+
+
 def _check_lens(x, lens, mul):
     if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
             or lens.numel() != x.size(0) or not lens.is_contiguous() or int(mul) < 1):

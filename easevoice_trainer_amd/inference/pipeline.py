@@ -69,14 +69,18 @@ def _poll_groups(stream, stats, per_waiting):
         yield group
 
 
-def _decode_group(voice, dev, batch_phones, refer, kw, items):
+def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None):
     """items: [(fragment index, y, idx)] of one poll, at most s2_batch of them -> their waveforms, through ONE decode_batch
-    call (a single fragment: the decode call of the one-by-one path)"""
+    call (a single fragment: the decode call of the one-by-one path).  speeds: None, or one speed per fragment of the
+    whole request (fragment_speed); decode_batch gets the group's values only when one of them is not 1"""
     with torch.no_grad():
         if len(items) == 1:
             r, y, idx = items[0]
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
-            return [voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=1.0, **kw)[0, 0, :]]
+            one = 1.0 if speeds is None else speeds[r]
+            return [voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :]]
+        if speeds is not None and any(speeds[r] != 1.0 for r, _y, _idx in items):
+            kw = dict(kw, speed=[speeds[r] for r, _y, _idx in items])
         sems = [y[-idx:] for _r, y, idx in items]
         phones = [batch_phones[r].to(dev) for r, _y, _idx in items]
         codes = torch.nn.utils.rnn.pad_sequence(sems, batch_first=True).unsqueeze(0)
@@ -89,7 +93,7 @@ def _decode_group(voice, dev, batch_phones, refer, kw, items):
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
-                      choose=None, wide=False, s2_batch=1):
+                      choose=None, wide=False, s2_batch=1, fragment_speed=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -114,7 +118,12 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     per group (SynthesizerTrn.decode_batch: every row is what decode gives for it alone), and are yielded in the order
     they arrived; cancelled and preempted fragments pass through as (index, None) in that order.  It never waits for a
     later poll: a fragment that finishes alone is decoded alone.  With candidates > 1 the chosen takes go through the
-    groups.  decode_kwargs then go to decode_batch (noise_scale; a `noise` of batch 1 is shared by the rows)."""
+    groups.  decode_kwargs then go to decode_batch (noise_scale; a `noise` of batch 1 is shared by the rows).
+    fragment_speed: None, or a list with one speed per fragment (speed_factor must then be 1.0): fragment r is decoded
+    at fragment_speed[r].  With s2_batch > 1 the groups stay batched -- a group goes through one
+    decode_batch(speed=[the group's speeds]) call, which resamples every row on its own lengths, and through the call
+    without the keyword when all its speeds are 1 --; with s2_batch == 1, for a fragment that finishes alone and with
+    candidates > 1 outside the groups it is decode(speed=fragment_speed[r])."""
     model, dev = t2s.model, t2s.device
     s2_batch = int(s2_batch)
     if s2_batch < 1:
@@ -131,6 +140,12 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                else [prompt_semantic.reshape(-1).to(dev)] * n)
     if fragment_sampling is not None and len(fragment_sampling) != n:
         raise ValueError(f"fragment_sampling has {len(fragment_sampling)} entries for {n} fragments")
+    if fragment_speed is not None:
+        if speed_factor != 1.0:
+            raise ValueError(f"fragment_speed gives every fragment its own speed: speed_factor must be 1.0, not {speed_factor}")
+        if len(fragment_speed) != n:
+            raise ValueError(f"fragment_speed has {len(fragment_speed)} entries for {n} fragments")
+        fragment_speed = [float(v) for v in fragment_speed]
     reqs = [(p.to(dev), b.to(dev), pr) for p, b, pr in zip(all_phoneme_ids, all_bert_features, prompts)]
     if fragment_sampling is not None:
         reqs = [q if fs is None else (*q, dict(fs)) for q, fs in zip(reqs, fragment_sampling)]
@@ -140,7 +155,8 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     def audio(r, y, idx):
         with torch.no_grad():
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
-            return voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]
+            one = speed_factor if fragment_speed is None else fragment_speed[r]
+            return voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :]
 
     if candidates > 1 and int(slots) < candidates:
         raise ValueError(f"slots = {int(slots)} cannot hold the {candidates} candidates of one fragment")
@@ -191,7 +207,8 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                     live += ready[take][1] is not None
                     take += 1
                 chunk, ready = ready[:take], ready[take:]
-                wavs = iter(_decode_group(voice, dev, batch_phones, refer, kw, [c for c in chunk if c[1] is not None]))
+                wavs = iter(_decode_group(voice, dev, batch_phones, refer, kw, [c for c in chunk if c[1] is not None],
+                                          fragment_speed))
                 for r, y, _idx in chunk:
                     yield r, (None if y is None else next(wavs))
         return
@@ -215,7 +232,4 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         if y is None or idx is None:       # cancelled, or preempted with partial tokens: no s2 decode
             yield r, None
             continue
-        with torch.no_grad():
-            sem = y[-idx:].unsqueeze(0).unsqueeze(0)
-            wav = voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=speed_factor, **kw)[0, 0, :]
-        yield r, wav
+        yield r, audio(r, y, idx)

@@ -44,14 +44,14 @@ class SoVITSVoice:
                                  noise=None if noise is None else mv(noise))
 
     @torch.no_grad()
-    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None):
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1):
         """SynthesizerTrn.decode_batch: a ragged batch of fragments in one pass -> a list of B 1-D waveforms, row b what
-        decode gives for fragment b alone"""
+        decode gives for fragment b alone (at speed, or at speed[b] where a sequence of B speeds is given)"""
         L.set_half(self.dtype)
         mv = lambda t: t.to(self.device)
         mvr = lambda r: [mvr(e) for e in r] if isinstance(r, (list, tuple)) else mv(r)
         return self.model.decode_batch(mv(codes), code_lens, mv(text), text_lens, mvr(refer), noise_scale=noise_scale,
-                                       noise=None if noise is None else mv(noise))
+                                       noise=None if noise is None else mv(noise), speed=speed)
 
     @torch.no_grad()
     def extract_latent(self, ssl):

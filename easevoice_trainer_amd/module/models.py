@@ -18,6 +18,7 @@ There is no CPU / eager fallback: the modules need a WeightBank (hip/conv.py) an
 """
 
 import functools
+import math
 import os
 
 import torch
@@ -25,7 +26,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from ..hip import lib as L
-from ..hip.conv import Add3ScaleFn, EvtConv1d, GatedActFn, mask_tail, res_stage, res_unit
+from ..hip.conv import Add3ScaleFn, EvtConv1d, GatedActFn, mask_tail, res_stage, res_unit, resample_rows
 from ..hip.enc import new_site, rel_self_attention, unbind_rows, wn_residual, wn_residual_last
 from ..hip.frontend import RvqEncoder, ncl_to_nlc
 from ..hip.wn import wn_stack
@@ -259,10 +260,14 @@ class TextEncoder(nn.Module, _ComputeDtype):
         self.encoder2 = Encoder(hidden_channels, filter_channels, n_heads, n_layers // 2, kernel_size, p_dropout)
         self.proj = pointwise(hidden_channels, out_channels * 2)
 
-    def forward(self, y, y_mask, text, text_mask, ge, y_lengths=None, text_lengths=None, speed=1):
+    def forward(self, y, y_mask, text, text_mask, ge, y_lengths=None, text_lengths=None, speed=1, out_lens=None):
         """y [B, T, 768] (quantized ssl), text [B, Tt] ids, ge [B, 512]; the encoders mask their own input / output.
         speed != 1 (inference only, models.py:246-248) resamples the encoded sequence to int(T/speed)+1 frames before
-        the projection and returns the resampled mask as a fourth value."""
+        the projection and returns the resampled mask as a fourth value.
+        out_lens (B ints, with speed == 1; decode_batch's per-row speeds): row b is resampled from its own y_lengths[b]
+        to out_lens[b] frames by one evt_resample_rows launch -- the same interpolation on the row alone --, the output
+        has max(out_lens) frames with zero tails, and the fourth value is sequence_mask(out_lens): what the reference's
+        nearest-resampled mask of ones is."""
         yl = (y_lengths if y_lengths is not None else y_mask.sum(dim=(1, 2))).to(torch.int32)
         tl = (text_lengths if text_lengths is not None else text_mask.sum(dim=(1, 2))).to(torch.int32)
         y = self.ssl_proj(y * y_mask)
@@ -275,9 +280,17 @@ class TextEncoder(nn.Module, _ComputeDtype):
             n = int(y.size(1) / speed) + 1
             y = F.interpolate(y.transpose(1, 2).float(), size=n, mode="linear").transpose(1, 2).to(y.dtype).contiguous()
             y_mask = F.interpolate(y_mask.transpose(1, 2), size=n, mode="nearest").transpose(1, 2).contiguous()
+        if out_lens is not None:
+            if speed != 1:
+                raise L.EvtError("TextEncoder.forward: out_lens (per-row resampling) goes with speed == 1")
+            ol = torch.as_tensor(out_lens, dtype=torch.int32).reshape(-1)
+            n = int(ol.max())
+            ol = ol.to(y.device)
+            y = resample_rows(y.contiguous(), yl.contiguous(), ol, n, self.proj)
+            y_mask = commons.sequence_mask(ol, n).unsqueeze(-1).to(y_mask.dtype)
         stats = (self.proj(y) * y_mask).float()
         m, logs = torch.split(stats, self.out_channels, dim=-1)
-        return (y, m, logs) if speed == 1 else (y, m, logs, y_mask)
+        return (y, m, logs) if speed == 1 and out_lens is None else (y, m, logs, y_mask)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -904,7 +917,7 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         return torch.stack(ges, 0).mean(0)
 
     @torch.no_grad()
-    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None):
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1):
         """decode for a RAGGED batch of fragments in one pass: codes [1, B, Tcmax] and text [B, Ttmax] right-padded,
         code_lens / text_lens [B] (tensors or sequences of ints).  refer: one reference spectrogram [1, spec, Tr] (or a
         list of them, averaged) shared by all rows, or a list of exactly B entries, one per row (a list of length B is
@@ -912,8 +925,14 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         mask in front of its convolutions, so references are never padded together).  noise [B, inter, >= Tmax] or None.
         Returns a list of B 1-D waveforms of code_lens[b] * (2 if 25hz) * prod(upsample_rates) samples, row b being what
         decode gives for fragment b alone: the encoders, MRTE, the flow and the style attention take the lengths as
-        they do in training, and the vocoder runs its length-aware forward (Generator.forward(lens=...)).  No speed
-        parameter: the reference defines its interpolation per sequence, anything but 1 stays on decode."""
+        they do in training, and the vocoder runs its length-aware forward (Generator.forward(lens=...)).
+        speed: one number for all rows or a sequence of B numbers, each finite and > 0.  All equal to 1: the pass above,
+        launch for launch.  Otherwise row b, T_b = code_lens[b] * (2 if 25hz) frames long, leaves the prior encoder
+        resampled to n_b = int(T_b / speed[b]) + 1 frames (n_b = T_b where speed[b] == 1: decode does not interpolate
+        there) -- the reference's per-sequence interpolation (models.py:246-248) on every row's own lengths, one
+        evt_resample_rows launch --, n_b is the row's length from there on, waveform b has n_b * prod(upsample_rates)
+        samples and is what decode(speed=speed[b]) gives for fragment b alone.  noise must then be [B, inter, >= max(n_b)]
+        (wider than Tmax for a speed below 1)."""
         dev = codes.device
         if codes.dim() != 3 or codes.size(0) != 1 or text.dim() != 2 or text.size(0) != codes.size(1):
             raise L.EvtError(f"decode_batch takes codes [1, B, Tc] and text [B, Tt], got {tuple(codes.shape)} and {tuple(text.shape)}")
@@ -925,6 +944,20 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
             raise L.EvtError(f"decode_batch: code_lens / text_lens must hold {B} lengths in [1, {Tc}] / [1, {text.size(1)}]")
         f = 2 if self.semantic_frame_rate == "25hz" else 1
         T = Tc * f
+        if torch.is_tensor(speed):
+            speed = speed.tolist()
+        speeds = [float(v) for v in speed] if isinstance(speed, (list, tuple)) else [float(speed)] * B
+        if len(speeds) != B:
+            raise L.EvtError(f"decode_batch: speed holds {len(speeds)} values for {B} rows")
+        for b, v in enumerate(speeds):
+            if not (math.isfinite(v) and v > 0):
+                raise L.EvtError(f"decode_batch: speed of row {b} is {v}, it must be finite and > 0")
+        # frames per row behind the prior encoder: the reference's int(T / speed) + 1 on the row's own length
+        out_len = None if all(v == 1 for v in speeds) else [n * f if v == 1 else int(n * f / v) + 1 for n, v in zip(cl, speeds)]
+        if out_len is not None and noise is not None and (noise.dim() != 3 or noise.size(0) not in (1, B)
+                                                           or noise.size(2) < max(out_len)):
+            raise L.EvtError(f"decode_batch: noise must be [{B}, inter, >= {max(out_len)}] at these speeds (a table of "
+                             f"batch 1 is shared by the rows), got {tuple(noise.shape)}")
         amp = self.cd in (torch.bfloat16, torch.float16)
         with torch.autocast("cuda", dtype=self.cd if amp else torch.bfloat16, enabled=amp):
             per_row = isinstance(refer, (list, tuple)) and len(refer) == B
@@ -946,7 +979,14 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
                 quantized = quantized.repeat_interleave(2, dim=1)
             y_mask = commons.sequence_mask(y_lengths, T).unsqueeze(-1).to(torch.float32)
             text_mask = commons.sequence_mask(text_lengths, text.size(1)).unsqueeze(-1).to(torch.float32)
-            _x, m_p, logs_p = self.enc_p(quantized, y_mask, text, text_mask, ge, y_lengths, text_lengths)
+            if out_len is None:
+                _x, m_p, logs_p = self.enc_p(quantized, y_mask, text, text_mask, ge, y_lengths, text_lengths)
+                frames = [n * f for n in cl]
+            else:
+                _x, m_p, logs_p, y_mask = self.enc_p(quantized, y_mask, text, text_mask, ge, y_lengths, text_lengths,
+                                                     out_lens=out_len)
+                frames, T = out_len, max(out_len)
+                y_lengths = torch.tensor(out_len, dtype=torch.long).to(dev)
             if noise is None:
                 noise = torch.randn(B, m_p.size(2), m_p.size(1), device=m_p.device)
             eps = noise[:, :, :m_p.size(1)].transpose(1, 2).to(m_p.dtype)
@@ -956,7 +996,7 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
             z = self.flow(z_p, ym, g=ge, reverse=True, lens=lens32)
             o = self.dec(z * ym, g=ge, lens=lens32)                       # [B, T * up, 1], zero tails
         up = o.size(1) // T
-        return [o[b, :cl[b] * f * up, 0] for b in range(B)]
+        return [o[b, :frames[b] * up, 0] for b in range(B)]
 
     def forward(self, ssl, y, y_lengths, text, text_lengths, eps=None, ids_slice=None):
         """ssl [B, 768, T], y [B, spec, T] linear spectrogram, text [B, Tt] -> same tuple as the reference:

@@ -328,6 +328,20 @@ int evt_add3_scale(int32_t dtype, const void* a, const void* b, const void* c, f
 int evt_mask_tail(int32_t dtype, void* x, const int32_t* lens, int32_t mul, int32_t nseq, int32_t L, int32_t C,
                   void* stream);
 
+/* Per-row linear resampling along the positions: the speed change of the prior encoder's output (models.py:246-248,
+ * F.interpolate(mode="linear") per sequence) for a RAGGED batch, every row with its own input and output length.
+ * x [nseq][Lin][C] -> y [nseq][Lout][C], in_lens / out_lens device int32 [nseq], clamped on the device to [0, Lin] /
+ * [0, Lout].  Row s with Ti = in_lens[s], To = out_lens[s], in fp32 (torch's upsample_linear1d, align_corners = False):
+ *   scale = (float)Ti / (float)To;  src = max(scale * (j + 0.5f) - 0.5f, 0);  i0 = (int)src;  i1 = i0 + (i0 < Ti - 1)
+ *   l1 = src - i0  (0 where i0 is the row's last position: both taps are that position, y is x there exactly)
+ *   y[s][j] = (1 - l1) * x[s][i0] + l1 * x[s][i1]   for j < To,  rounded once to the storage type
+ *   y[s][j] = 0                                     for To <= j < Lout (and everywhere when Ti == 0)
+ * x is never read at positions >= Ti, every element of y is written (no evt_mask_tail behind it), a row with To == Ti
+ * is a copy.  No host synchronisation: legal in a captured graph.  C * element size a multiple of 16, x and y 16-byte
+ * aligned; EVT_EINVAL otherwise, and for a NULL pointer, a size <= 0 or a dtype the build does not serve. */
+int evt_resample_rows(int32_t dtype, const void* x, const int32_t* in_lens, const int32_t* out_lens, int32_t nseq,
+                      int32_t Lin, int32_t Lout, int32_t C, void* y, void* stream);
+
 /* out = leaky_relu(x, slope).  The HiFi-GAN residual unit (modules.py:299-308) keeps an activated copy of its input
  * so that its convolutions and weight gradients take plain operands (LDS-DMA kernels).  16-byte aligned. */
 int evt_leaky_relu(int32_t dtype, const void* x, float slope, void* out, int64_t n, void* stream);

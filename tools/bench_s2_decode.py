@@ -11,7 +11,14 @@ a pass is timed with device events around all its calls and ends in a synchronis
 fragments/s and audio-seconds/s, and the spread (min / max seconds).  The yardstick is the `one` line of the same run.
 A measurement path without a GPU fails.
 
+--speed S (one speed for all fragments) or --mixed-speeds (a seeded choice out of 0.8, 1.0 and 1.25 per fragment) time the
+same modes at those speeds: decode(speed=...) one at a time against decode_batch(speed=[...]) on the groups, whose rows are
+resampled on their own lengths (evt_resample_rows).  Such a run is kept under its own name ("speed_1.25", "mixed") in
+profiles/s2_decode_batch_speed.json, next to the runs the file already holds.
+
     python tools/bench_s2_decode.py [--reps 5] [--fragments 64] [--out profiles/s2_decode_batch.json]
+    python tools/bench_s2_decode.py --speed 1.25
+    python tools/bench_s2_decode.py --mixed-speeds
 """
 import argparse
 import json
@@ -58,8 +65,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fragments", type=int, default=64)
     ap.add_argument("--batches", type=int, nargs="+", default=[4, 8, 16])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "s2_decode_batch.json"))
+    ap.add_argument("--speed", type=float, default=None, help="one speed for every fragment")
+    ap.add_argument("--mixed-speeds", action="store_true", help="a seeded choice out of 0.8, 1.0, 1.25 per fragment")
+    ap.add_argument("--out", default=None, help="default: profiles/s2_decode_batch.json, at a speed profiles/s2_decode_batch_speed.json")
     args = ap.parse_args()
+    if args.speed is not None and args.mixed_speeds:
+        raise SystemExit("--speed and --mixed-speeds exclude each other")
+    at_speed = args.speed is not None or args.mixed_speeds
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "s2_decode_batch_speed.json" if at_speed else "s2_decode_batch.json")
     if not torch.cuda.is_available():
         raise RuntimeError("bench_s2_decode needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
@@ -68,33 +82,43 @@ def main():
     codes = [c.to(dev) for c in codes]
     texts = [t.to(dev) for t in texts]
     refer = refer.to(dev)
-    audio_s = sum(c.numel() for c in codes) / 25.0
+    if args.mixed_speeds:
+        rnd = random.Random(23)
+        speeds = [rnd.choice([0.8, 1.0, 1.25]) for _ in codes]
+    else:
+        speeds = [1.0 if args.speed is None else float(args.speed)] * len(codes)
+    # frames per fragment behind the resampler (50 per second of output): the reference's int(T / speed) + 1
+    frames = [2 * c.numel() if v == 1 else int(2 * c.numel() / v) + 1 for c, v in zip(codes, speeds)]
+    audio_s = sum(frames) / 50.0
     pad = torch.nn.utils.rnn.pad_sequence
 
     def run_one():
-        return [voice.decode(c.view(1, 1, -1), t.view(1, -1), refer)[0, 0] for c, t in zip(codes, texts)]
+        return [voice.decode(c.view(1, 1, -1), t.view(1, -1), refer, speed=v)[0, 0] for c, t, v in zip(codes, texts, speeds)]
 
     def run_batch(k):
         out = []
         for i in range(0, len(codes), k):
             cs, ts = codes[i:i + k], texts[i:i + k]
+            kw = dict(speed=speeds[i:i + k]) if at_speed else {}
             out += voice.decode_batch(pad(cs, batch_first=True).unsqueeze(0), [c.numel() for c in cs],
-                                      pad(ts, batch_first=True), [t.numel() for t in ts], refer)
+                                      pad(ts, batch_first=True), [t.numel() for t in ts], refer, **kw)
         return out
 
     modes = [("one", run_one)] + [(f"batch{k}", (lambda k=k: run_batch(k))) for k in args.batches]
     for name, fn in modes:                        # warm-up: every shape of every mode once
         outs = fn()
         torch.cuda.synchronize()
-        assert [o.numel() for o in outs] == [c.numel() * 2 * 640 for c in codes], name
+        assert [o.numel() for o in outs] == [n * 640 for n in frames], name
         assert all(bool(torch.isfinite(o).all()) for o in outs), name
     # same inputs, same prior noise: a batched row against the row alone (bf16)
-    noise = torch.randn(4, 192, 2 * max(c.numel() for c in codes[:4]) + 8, device=dev)
+    noise = torch.randn(4, 192, max(2 * max(c.numel() for c in codes[:4]), max(frames[:4])) + 8, device=dev)
     got = voice.decode_batch(pad(codes[:4], batch_first=True).unsqueeze(0), [c.numel() for c in codes[:4]],
-                             pad(texts[:4], batch_first=True), [t.numel() for t in texts[:4]], refer, noise=noise)
+                             pad(texts[:4], batch_first=True), [t.numel() for t in texts[:4]], refer, noise=noise,
+                             **(dict(speed=speeds[:4]) if at_speed else {}))
     check = []
     for b in range(4):
-        a = voice.decode(codes[b].view(1, 1, -1), texts[b].view(1, -1), refer, noise=noise[b:b + 1])[0, 0].float()
+        a = voice.decode(codes[b].view(1, 1, -1), texts[b].view(1, -1), refer, speed=speeds[b],
+                         noise=noise[b:b + 1])[0, 0].float()
         check.append(float((got[b].float() - a).abs().max() / (a.abs().max() + 1e-12)))
     times = {name: [] for name, _ in modes}
     for _ in range(args.reps):
@@ -108,6 +132,7 @@ def main():
             times[name].append(e0.elapsed_time(e1) / 1e3)
     res = {"tool": "tools/bench_s2_decode.py", "device": torch.cuda.get_device_name(0), "dtype": "bf16",
            "fragments": len(codes), "audio_seconds": round(audio_s, 2), "reps": args.reps,
+           "speed": ("mixed: seeded choice out of 0.8, 1.0, 1.25 per fragment" if args.mixed_speeds else speeds[0]),
            "fragment_seconds_min_max": [min(c.numel() for c in codes) / 25.0, max(c.numel() for c in codes) / 25.0],
            "batched_row_vs_alone_rel_maxabs": [round(v, 5) for v in check], "modes": {}}
     for name, _ in modes:
@@ -122,8 +147,14 @@ def main():
     res["verdict"] = (f"{best} is {res['modes'][best]['speedup_vs_one']}x the one-at-a-time path"
                       if res["modes"][best]["speedup_vs_one"] > 1.0 else "no batch size beats the one-at-a-time path")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    doc = res
+    if at_speed:
+        # one file for the runs at a speed: the `one` line of each run is that run's baseline (nobody measured this before)
+        res["baseline"] = "modes.one of this run: decode(speed=...) one fragment at a time"
+        doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": res["tool"], "runs": {}}
+        doc["runs"]["mixed" if args.mixed_speeds else f"speed_{speeds[0]:g}"] = res
     with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
+        json.dump(doc, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
 
