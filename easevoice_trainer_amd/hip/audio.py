@@ -1,0 +1,154 @@
+"""The finishing step of a ragged s2 decode: the vocoder's rows resampled to the requested rate, converted to the requested
+sample format and packed into one device buffer by ONE launch (csrc/resample_poly.hip::evt_resample_pack_rows; include/evt.h
+has the operator's definition).  The int16 conversion and the silence interval are the reference's audio_postprocess
+(inference/tts.py:878-908); the resampler is resampy's kaiser_best filter as feature_extractor/normalize.py restates it for
+the ratio 1/2, written for any ratio: at 1/2 its taps are normalize._half_band_taps() and the operator is resample_half.
+The filter's constants are taken from there."""
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import List
+
+import numpy as np
+import torch
+
+from . import conv as _conv
+from . import lib as L
+from ..feature_extractor.normalize import _BETA, _ROLLOFF, _ZEROS
+
+PCM_F32, PCM_S16 = 0, 1
+FORMATS = {"float32": (PCM_F32, torch.float32), "int16": (PCM_S16, torch.int16)}
+TILE = 2048            # EVT_RESAMPLE_TILE: outputs of one row per block, counted from the row's output 0
+MAX_FACTOR = 1024      # largest reduced up / down served
+RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)     # the rates in everyday use from the model's 32 kHz
+
+
+def rate_ratio(in_rate, out_rate):
+    """(up, down) = out_rate / in_rate reduced; EvtError for a rate <= 0 or a factor above MAX_FACTOR"""
+    if int(in_rate) != in_rate or int(out_rate) != out_rate or in_rate <= 0 or out_rate <= 0:
+        raise L.EvtError(f"sample rates must be positive integers, got {in_rate} -> {out_rate}")
+    g = math.gcd(int(in_rate), int(out_rate))
+    up, down = int(out_rate) // g, int(in_rate) // g
+    if up > MAX_FACTOR or down > MAX_FACTOR:
+        raise L.EvtError(f"{in_rate} -> {out_rate} Hz reduces to {up}/{down}: factors above {MAX_FACTOR} are not served")
+    return up, down
+
+
+def out_len(n, up, down):
+    """outputs of a row of n samples"""
+    return (int(n) * up) // down
+
+
+def poly_taps(up, down):
+    """g[k], k = -(H - 1) .. H - 1 (float64, 2 H - 1 values, g[0] at index H - 1), H = Z * max(up, down):
+    g[k] = s * rho * sinc(rho * s * k / up) * I0(beta * sqrt(1 - (s k / (up Z))^2)) / I0(beta), s = min(1, up / down).
+    s k / up = k / max(up, down) and s k / (up Z) = k / H exactly, which is how they are evaluated."""
+    m = max(int(up), int(down))
+    h = _ZEROS * m
+    k = np.arange(-(h - 1), h, dtype=np.float64)
+    s = min(1.0, up / down)
+    taper = np.i0(_BETA * np.sqrt(1.0 - (k / h) ** 2.0)) / np.i0(float(_BETA))
+    return s * (_ROLLOFF * np.sinc(_ROLLOFF * k / m)) * taper
+
+
+def table_shape(up, down):
+    """(R, J): R = ceil(H / up) input samples on either side of an output's centre, J = 2 R + 1 taps per phase padded to a
+    multiple of 4"""
+    h = _ZEROS * max(int(up), int(down))
+    r = -(-h // int(up))
+    return r, (2 * r + 1 + 3) // 4 * 4
+
+
+def phase_rows(up, down):
+    """T[p][j] = g[p + (R - j) * up] (float64 [up, J]), zero where |p + (R - j) up| >= H and in the padding j > 2 R: output m
+    with m * down = q * up + p is sum_j T[p][j] * x[q - R + j]"""
+    g = poly_taps(up, down)
+    h = (len(g) + 1) // 2
+    r, j_pad = table_shape(up, down)
+    k = np.arange(up)[:, None] + (r - np.arange(j_pad)[None, :]) * up
+    live = (np.abs(k) < h) & (np.arange(j_pad)[None, :] <= 2 * r)
+    return np.where(live, g[np.clip(k + h - 1, 0, len(g) - 1)], 0.0)
+
+
+_TABLES = {}
+
+
+def phase_table(up, down, device):
+    """phase_rows rounded once to fp32, on the device; kept per (up, down, device)"""
+    device = torch.device(device)
+    key = (int(up), int(down), device.type, device.index)
+    t = _TABLES.get(key)
+    if t is None:
+        t = _TABLES[key] = torch.from_numpy(phase_rows(up, down).astype(np.float32)).to(device).contiguous()
+    return t
+
+
+@dataclass
+class PackedAudio:
+    """data: 1-D device tensor (int16 or float32) holding every row and `gap` zeros behind each; row b lies at
+    data[offsets[b] : offsets[b] + lengths[b]]"""
+    data: torch.Tensor
+    offsets: List[int]
+    lengths: List[int]
+    rate: int
+    gap: int = 0
+
+    def row(self, b, gap=False):
+        """a view of row b, without (or with) the silence behind it"""
+        return self.data[self.offsets[b]:self.offsets[b] + self.lengths[b] + (self.gap if gap else 0)]
+
+    def __len__(self):
+        return len(self.lengths)
+
+
+def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, interval=0.0, lens_dev=None, owner=None):
+    """x [nseq, L] (or [nseq, L, 1], or one row [L]) contiguous fp32 / bf16 / f16 on the GPU; row s has
+    n_s = min(lens[s] * mul, L) live samples.  lens: a sequence of ints (the host sizes the buffer from them); lens_dev:
+    the same values as an int32 tensor on x's device where the caller has one (decode_batch does), uploaded otherwise.
+    -> PackedAudio at out_rate in out_format ("int16" / "float32"): row s resampled to (n_s * up) // down samples (the
+    operator of include/evt.h; out_rate == in_rate passes the values through), gap = int(out_rate * interval) zeros behind
+    every row (the reference's zero_wav).  order: a permutation of the rows, the sequence in which they lie in the buffer
+    (default: 0, 1, ...); offsets are the host's prefix sum of To_s + gap in that sequence.  One launch writes every
+    element of the buffer: no memset in front of it."""
+    if out_format not in FORMATS:
+        raise L.EvtError(f"out_format must be one of {sorted(FORMATS)}, got {out_format!r}")
+    code, out_dtype = FORMATS[out_format]
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() == 3 and x.size(2) == 1:
+        x = x.squeeze(2)
+    if x.dim() != 2 or not x.is_contiguous() or x.size(0) < 1 or x.size(1) < 1:
+        raise L.EvtError(f"resample_pack takes contiguous rows [nseq, L], got {tuple(x.shape)}")
+    nseq, length = x.size(0), x.size(1)
+    lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    mul = int(mul)
+    if len(lens) != nseq or mul < 1 or min(lens) < 0:
+        raise L.EvtError(f"resample_pack: {nseq} lengths >= 0 and mul >= 1 expected, got {lens} and mul = {mul}")
+    if lens_dev is None:
+        lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+    _conv._check_lens(x, lens_dev, mul)
+    up, down = rate_ratio(in_rate, out_rate)
+    if interval < 0:
+        raise L.EvtError(f"interval = {interval} must be >= 0")
+    gap = int(out_rate * interval)
+    order = list(range(nseq)) if order is None else [int(b) for b in order]
+    if sorted(order) != list(range(nseq)):
+        raise L.EvtError(f"order must be a permutation of the {nseq} rows, got {order}")
+    lengths = [out_len(min(n * mul, length), up, down) for n in lens]
+    offsets, total = [0] * nseq, 0
+    for b in order:
+        offsets[b] = total
+        total += lengths[b] + gap
+    data = torch.empty(total, dtype=out_dtype, device=x.device)
+    if total == 0:
+        return PackedAudio(data, offsets, lengths, int(out_rate), gap)
+    off_dev = torch.tensor(offsets, dtype=torch.int64).to(x.device)
+    table, j_pad = (None, 0) if up == down == 1 else (phase_table(up, down, x.device), table_shape(up, down)[1])
+    e0 = _conv._t0()
+    L.check(L.lib().evt_resample_pack_rows(L.dt_of(x), L.ptr(x), L.ptr(lens_dev), mul, nseq, length, up, down, L.ptr(table),
+                                           j_pad, code, L.ptr(data), C.c_int64(total), L.ptr(off_dev), gap, L.stream_ptr()),
+            "evt_resample_pack_rows")
+    if e0 is not None:
+        _conv._t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
+    return PackedAudio(data, offsets, lengths, int(out_rate), gap)
+

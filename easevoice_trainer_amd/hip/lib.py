@@ -205,7 +205,8 @@ def lib():
         _lib.evt_resunit_bwd_ws_floats.restype = C.c_int64
         _lib.evt_debug_kernel_tags.restype = None
         # the ragged (inference) entry points of the vocoder: both builds export them, a library without them fails here
-        for name in ("evt_resunit_fwd_multi_lens", "evt_resunit_wide_fwd_lens", "evt_mask_tail", "evt_resample_rows"):
+        for name in ("evt_resunit_fwd_multi_lens", "evt_resunit_wide_fwd_lens", "evt_mask_tail", "evt_resample_rows",
+                     "evt_resample_pack_rows"):
             getattr(_lib, name).restype = C.c_int
     return _lib
 

@@ -1,6 +1,8 @@
 """The model-side core of TTS.run for one batch of text fragments (src/easevoice/inference/tts.py:756-817): semantic
 tokens from the s1 decoder, waveform fragments from the s2 decoder.  Everything around it in the reference -- text
-front-end, BERT / CN-HuBERT feature extraction, bucketing, audio post-processing -- is outside SURVEY §8."""
+front-end, BERT / CN-HuBERT feature extraction, bucketing -- is outside SURVEY §8.  The audio post-processing
+(TTS.audio_postprocess, tts.py:878-908: int16 with a silence interval behind every fragment) is synthesize_pcm, with any
+output rate; synthesize_stream hands out single fragments at a rate and in a format of the caller's choice."""
 import math
 
 import torch
@@ -69,16 +71,32 @@ def _poll_groups(stream, stats, per_waiting):
         yield group
 
 
-def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None):
+def _finish(voice, wav, out):
+    """one waveform of decode -> the caller's rate and format: resample_pack with nseq = 1, the launch a group's rows get
+    behind decode_batch (a row comes out of it bit for bit as it does alone).  out: {} (the waveform as it is), or the
+    out_rate / out_format that were set"""
+    if not out:
+        return wav
+    from ..hip.audio import resample_pack
+
+    rate = getattr(voice.model, "sampling_rate", 32000)
+    return resample_pack(wav, [wav.numel()], 1, rate, out.get("out_rate", rate), out.get("out_format", "float32")).row(0)
+
+
+def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None, out=None):
     """items: [(fragment index, y, idx)] of one poll, at most s2_batch of them -> their waveforms, through ONE decode_batch
     call (a single fragment: the decode call of the one-by-one path).  speeds: None, or one speed per fragment of the
-    whole request (fragment_speed); decode_batch gets the group's values only when one of them is not 1"""
+    whole request (fragment_speed); decode_batch gets the group's values only when one of them is not 1.  out: the
+    out_rate / out_format keywords that were set; decode_batch gets them only then, and its PackedAudio is handed out row
+    by row"""
+    out = out or {}
     with torch.no_grad():
         if len(items) == 1:
             r, y, idx = items[0]
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             one = 1.0 if speeds is None else speeds[r]
-            return [voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :]]
+            return [_finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :],
+                            out)]
         if speeds is not None and any(speeds[r] != 1.0 for r, _y, _idx in items):
             kw = dict(kw, speed=[speeds[r] for r, _y, _idx in items])
         sems = [y[-idx:] for _r, y, idx in items]
@@ -86,14 +104,15 @@ def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None):
         codes = torch.nn.utils.rnn.pad_sequence(sems, batch_first=True).unsqueeze(0)
         text = torch.nn.utils.rnn.pad_sequence(phones, batch_first=True)
         # one entry per row, all the same object: decode_batch encodes the shared reference(s) once
-        return voice.model.decode_batch(codes, [int(t.numel()) for t in sems], text, [int(t.numel()) for t in phones],
-                                        [refer] * len(items), **kw)
+        got = voice.model.decode_batch(codes, [int(t.numel()) for t in sems], text, [int(t.numel()) for t in phones],
+                                       [refer] * len(items), **kw, **out)
+        return [got.row(b) for b in range(len(items))] if out else got
 
 
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
-                      choose=None, wide=False, s2_batch=1, fragment_speed=None):
+                      choose=None, wide=False, s2_batch=1, fragment_speed=None, out_rate=None, out_format=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -123,8 +142,14 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     at fragment_speed[r].  With s2_batch > 1 the groups stay batched -- a group goes through one
     decode_batch(speed=[the group's speeds]) call, which resamples every row on its own lengths, and through the call
     without the keyword when all its speeds are 1 --; with s2_batch == 1, for a fragment that finishes alone and with
-    candidates > 1 outside the groups it is decode(speed=fragment_speed[r])."""
+    candidates > 1 outside the groups it is decode(speed=fragment_speed[r]).
+    out_rate / out_format (both None: the waveforms as the decoder gives them): every fragment is yielded as a 1-D device
+    tensor at out_rate Hz (None: the model's rate) in out_format "int16" or "float32" (None: "float32") -- the operator of
+    hip/audio.py.  A group's decode_batch call gets the keywords that were set (and no others) and finishes its rows with
+    one more launch; a fragment decoded alone goes through decode and then resample_pack with one row, which gives the
+    same bits."""
     model, dev = t2s.model, t2s.device
+    out = {k: v for k, v in (("out_rate", out_rate), ("out_format", out_format)) if v is not None}
     s2_batch = int(s2_batch)
     if s2_batch < 1:
         raise ValueError(f"s2_batch = {s2_batch} must be >= 1")
@@ -156,7 +181,8 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         with torch.no_grad():
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             one = speed_factor if fragment_speed is None else fragment_speed[r]
-            return voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :]
+            return _finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :],
+                           out)
 
     if candidates > 1 and int(slots) < candidates:
         raise ValueError(f"slots = {int(slots)} cannot hold the {candidates} candidates of one fragment")
@@ -208,7 +234,7 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                     take += 1
                 chunk, ready = ready[:take], ready[take:]
                 wavs = iter(_decode_group(voice, dev, batch_phones, refer, kw, [c for c in chunk if c[1] is not None],
-                                          fragment_speed))
+                                          fragment_speed, out))
                 for r, y, _idx in chunk:
                     yield r, (None if y is None else next(wavs))
         return
@@ -233,3 +259,29 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
             yield r, None
             continue
         yield r, audio(r, y, idx)
+
+
+def synthesize_pcm(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs, out_rate=None,
+                   fragment_interval=0.3, **stream_kwargs):
+    """The non-streaming end of TTS.run (tts.py:878-908, audio_postprocess): -> (rate, int16 tensor on the host) holding the
+    fragments in INPUT order, int(rate * fragment_interval) zeros behind each (the reference's zero_wav).  out_rate None:
+    the model's rate.  It drains synthesize_stream(out_rate=rate, out_format="int16", **stream_kwargs) -- s2_batch, slots,
+    fragment_speed, control ... as there --, so conversion and resampling happen on the device, one launch per group;
+    fragments that come back cancelled (or preempted) are left out together with their interval.  The pieces are joined
+    on the device and leave it in ONE device -> host copy."""
+    rate = int(getattr(voice.model, "sampling_rate", 32000) if out_rate is None else out_rate)
+    if fragment_interval < 0:
+        raise ValueError(f"fragment_interval = {fragment_interval} must be >= 0")
+    for k in ("out_rate", "out_format"):
+        if k in stream_kwargs:
+            raise ValueError(f"synthesize_pcm sets {k} itself")
+    got = {}
+    for r, wav in synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
+                                    out_rate=rate, out_format="int16", **stream_kwargs):
+        if wav is not None:
+            got[r] = wav
+    if not got:
+        return rate, torch.zeros(0, dtype=torch.int16)
+    silence = torch.zeros(int(rate * fragment_interval), dtype=torch.int16, device=next(iter(got.values())).device)
+    pieces = [t for r in sorted(got) for t in (got[r], silence)]
+    return rate, torch.cat(pieces).cpu()

@@ -31,6 +31,7 @@ class SoVITSVoice:
         del net.enc_q                      # not part of the export, not used by decode
         net.load_state_dict({k: v.float() for k, v in ck["weight"].items()}, strict=False)
         net.eval()
+        net.sampling_rate = self.sampling_rate
         self.rt = ModelRuntime(net, dtype=dtype, device=device)
         self.rt.prepare(force=True)
         self.model, self.device, self.dtype = net, torch.device(device), dtype
@@ -44,14 +45,17 @@ class SoVITSVoice:
                                  noise=None if noise is None else mv(noise))
 
     @torch.no_grad()
-    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1):
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1, out_rate=None,
+                     out_format=None, interval=0.0):
         """SynthesizerTrn.decode_batch: a ragged batch of fragments in one pass -> a list of B 1-D waveforms, row b what
-        decode gives for fragment b alone (at speed, or at speed[b] where a sequence of B speeds is given)"""
+        decode gives for fragment b alone (at speed, or at speed[b] where a sequence of B speeds is given); with out_rate /
+        out_format a hip.audio.PackedAudio: the rows at that rate and format in one device buffer"""
         L.set_half(self.dtype)
         mv = lambda t: t.to(self.device)
         mvr = lambda r: [mvr(e) for e in r] if isinstance(r, (list, tuple)) else mv(r)
         return self.model.decode_batch(mv(codes), code_lens, mv(text), text_lens, mvr(refer), noise_scale=noise_scale,
-                                       noise=None if noise is None else mv(noise), speed=speed)
+                                       noise=None if noise is None else mv(noise), speed=speed, out_rate=out_rate,
+                                       out_format=out_format, interval=interval)
 
     @torch.no_grad()
     def extract_latent(self, ssl):

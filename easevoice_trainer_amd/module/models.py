@@ -824,6 +824,7 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         self.spec_channels, self.segment_size, self.inter_channels = spec_channels, segment_size, inter_channels
         self.gin_channels, self.version = gin_channels, version
         self.upsample_rates = upsample_rates           # read by the reference's TTS.run (tts.py:798)
+        self.sampling_rate = 32000                     # of the waveforms (hps.data.sampling_rate; SoVITSVoice sets the export's)
         self.enc_p = TextEncoder(inter_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
                                  p_dropout, version=version)
         self.dec = Generator(inter_channels, resblock, resblock_kernel_sizes, resblock_dilation_sizes, upsample_rates,
@@ -917,7 +918,8 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         return torch.stack(ges, 0).mean(0)
 
     @torch.no_grad()
-    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1):
+    def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1, out_rate=None,
+                     out_format=None, interval=0.0):
         """decode for a RAGGED batch of fragments in one pass: codes [1, B, Tcmax] and text [B, Ttmax] right-padded,
         code_lens / text_lens [B] (tensors or sequences of ints).  refer: one reference spectrogram [1, spec, Tr] (or a
         list of them, averaged) shared by all rows, or a list of exactly B entries, one per row (a list of length B is
@@ -932,8 +934,22 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         there) -- the reference's per-sequence interpolation (models.py:246-248) on every row's own lengths, one
         evt_resample_rows launch --, n_b is the row's length from there on, waveform b has n_b * prod(upsample_rates)
         samples and is what decode(speed=speed[b]) gives for fragment b alone.  noise must then be [B, inter, >= max(n_b)]
-        (wider than Tmax for a speed below 1)."""
+        (wider than Tmax for a speed below 1).
+        out_rate / out_format (both None: the list above, launch for launch): one evt_resample_pack_rows launch behind
+        the vocoder takes its ragged rows to a hip.audio.PackedAudio -- one device buffer holding the rows in batch order at
+        out_rate Hz (None: self.sampling_rate) as out_format "int16" or "float32" (None: "float32"), int(out_rate * interval)
+        zeros behind each; row(b) is what hip.audio.resample_pack gives for waveform b alone, bit for bit."""
         dev = codes.device
+        if out_format is not None or out_rate is not None:
+            from ..hip import audio
+
+            out_rate = self.sampling_rate if out_rate is None else out_rate
+            out_format = "float32" if out_format is None else out_format
+            if out_format not in audio.FORMATS:
+                raise L.EvtError(f"decode_batch: out_format must be one of {sorted(audio.FORMATS)}, got {out_format!r}")
+            audio.rate_ratio(self.sampling_rate, out_rate)        # a rate that is not served fails before the pass
+        elif interval:
+            raise L.EvtError("decode_batch: interval goes with out_rate / out_format (the packed output)")
         if codes.dim() != 3 or codes.size(0) != 1 or text.dim() != 2 or text.size(0) != codes.size(1):
             raise L.EvtError(f"decode_batch takes codes [1, B, Tc] and text [B, Tt], got {tuple(codes.shape)} and {tuple(text.shape)}")
         B, Tc = codes.size(1), codes.size(2)
@@ -996,6 +1012,9 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
             z = self.flow(z_p, ym, g=ge, reverse=True, lens=lens32)
             o = self.dec(z * ym, g=ge, lens=lens32)                       # [B, T * up, 1], zero tails
         up = o.size(1) // T
+        if out_format is not None:
+            return audio.resample_pack(o, frames, up, self.sampling_rate, out_rate, out_format, interval=interval,
+                                       lens_dev=lens32, owner=self.dec)
         return [o[b, :frames[b] * up, 0] for b in range(B)]
 
     def forward(self, ssl, y, y_lengths, text, text_lengths, eps=None, ids_slice=None):

@@ -342,6 +342,42 @@ int evt_mask_tail(int32_t dtype, void* x, const int32_t* lens, int32_t mul, int3
 int evt_resample_rows(int32_t dtype, const void* x, const int32_t* in_lens, const int32_t* out_lens, int32_t nseq,
                       int32_t Lin, int32_t Lout, int32_t C, void* y, void* stream);
 
+/* The finishing launch of a ragged decode: every row of a batch of waveforms resampled from in_rate to out_rate
+ * (up / down = out_rate / in_rate, reduced), converted to the output format and packed into one buffer with `gap` zeros
+ * behind each row -- the int16 conversion and the silence interval of the reference's audio_postprocess
+ * (inference/tts.py:878-908) and a resampler in front of them, in one launch.
+ *
+ * The operator.  rho = 0.9475937167399596, beta = 14.769656459379492, Z = EVT_RESAMPLE_ZEROS (resampy's kaiser_best, the
+ * filter of feature_extractor/normalize.py::resample_half, which this is at up / down = 1 / 2); s = min(1, up / down),
+ * H = Z * max(up, down).  Prototype filter in float64, for integer |k| < H, zero outside:
+ *   g[k] = s * rho * sinc(rho * s * k / up) * I0(beta * sqrt(1 - (s * k / (up * Z))^2)) / I0(beta)   sinc(t) = sin(pi t) / (pi t)
+ * A row of n live samples gives To = (n * up) / down outputs (integer division, 64-bit):
+ *   y[m] = sum_{i = 0}^{n - 1} x[i] * g[m * down - i * up]        0 <= m < To,   x = 0 outside [0, n)
+ * Polyphase form: c = m * down, q = c / up, p = c % up, R = ceil(H / up);  y[m] = sum_j T[p][j] * x[q - R + j] with
+ * T[p][j] = g[p + (R - j) * up] for j = 0 .. 2 R and 0 for 2 R < j < J: the caller's `table` [up][J], built in float64 and
+ * rounded once to fp32, J a multiple of 4 in [2 R + 1, 2 R + 4], 16-byte aligned.  up == down == 1 is NOT this filter
+ * (g[0] = rho) but the identity, table may be NULL then and J is ignored.
+ * Arithmetic: x widened to fp32 (exact), products and sums in fp32 in a fixed order that depends on (m, up, down) only:
+ * four accumulators a0 .. a3 = 0; for j = 0, 4, 8, ... ascending a_e = fma(T[p][j + e], x[q - R + j + e], a_e), e = 0 .. 3;
+ * y[m] = (a0 + a1) + (a2 + a3).  A row therefore comes out bit for bit as it does with nseq = 1.
+ *
+ * x [nseq][L] of dtype; lens device int32 [nseq], row s has n_s = min(max(lens[s] * mul, 0), L) live samples and x is never
+ * read at or behind them.  Row s writes To_s samples at out[out_off[s] ..] and `gap` zeros directly behind them (out_off
+ * device int64 [nseq]; with the offsets a prefix sum of To_s + gap every element of `out` is written, no memset in front);
+ * an element that would fall outside [0, out_elems) is not stored.  out_format EVT_PCM_F32: the fp32 value v;
+ * EVT_PCM_S16: (int16) trunc(min(max(v * 32768, -32768), 32767)), NaN -> 0 (the reference's (audio * 32768).astype(int16),
+ * saturating where numpy wraps around).  Lengths are read on the device, no host synchronisation: legal in a captured
+ * graph.  A block takes EVT_RESAMPLE_TILE consecutive outputs of one row, counted from the row's output 0.
+ * EVT_EINVAL for a NULL pointer, a size <= 0, up or down <= 0, gap < 0, nseq > 65535, a pointer not aligned to its element
+ * (table: 16 bytes), a J outside the range above, an unknown format or a dtype the build does not serve. */
+#define EVT_RESAMPLE_ZEROS 64
+#define EVT_RESAMPLE_TILE 2048
+#define EVT_PCM_F32 0
+#define EVT_PCM_S16 1
+int evt_resample_pack_rows(int32_t dtype, const void* x, const int32_t* lens, int32_t mul, int32_t nseq, int32_t L,
+                           int32_t up, int32_t down, const float* table, int32_t J, int32_t out_format, void* out,
+                           int64_t out_elems, const int64_t* out_off, int32_t gap, void* stream);
+
 /* out = leaky_relu(x, slope).  The HiFi-GAN residual unit (modules.py:299-308) keeps an activated copy of its input
  * so that its convolutions and weight gradients take plain operands (LDS-DMA kernels).  16-byte aligned. */
 int evt_leaky_relu(int32_t dtype, const void* x, float slope, void* out, int64_t n, void* stream);

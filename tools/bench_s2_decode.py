@@ -16,9 +16,19 @@ same modes at those speeds: decode(speed=...) one at a time against decode_batch
 resampled on their own lengths (evt_resample_rows).  Such a run is kept under its own name ("speed_1.25", "mixed") in
 profiles/s2_decode_batch_speed.json, next to the runs the file already holds.
 
+--pcm times the way from finished fragments to PCM (profiles/s2_decode_pcm.json), in groups of 1 / 4 / 8 / 16, under these
+conditions: `device` -- waveforms on the device, as above; `host_int16` -- the same decode, then per fragment
+.float().cpu().numpy() * 32768, astype(int16) and one concatenate with the 0.3 s of zeros behind each: the way to the
+reference's int16 bytes without the finishing launch, and the BASELINE of this run; `pcm_<rate>` -- decode_batch(out_rate=rate,
+out_format="int16", interval=0.3): one more launch per group, a packed buffer on the device, at 32000 and at every
+--out-rate (default 16000 48000); `pcm_32000_host` -- that buffer copied to the host, one copy per group: the same bytes
+as the baseline.  A lone fragment (groups of 1) takes decode and then resample_pack with one row, as synthesize_stream does.
+The finishing launch alone is timed with device events on the rows of every group.
+
     python tools/bench_s2_decode.py [--reps 5] [--fragments 64] [--out profiles/s2_decode_batch.json]
     python tools/bench_s2_decode.py --speed 1.25
     python tools/bench_s2_decode.py --mixed-speeds
+    python tools/bench_s2_decode.py --pcm [--out-rate 16000 48000]
 """
 import argparse
 import json
@@ -60,6 +70,118 @@ def build_voice(dev, dtype):
     return SoVITSVoice({"weight": weight, "config": hps, "info": "bench"}, device=str(dev), dtype=dtype)
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def main_pcm(args):
+    """--pcm: see the module docstring"""
+    import numpy as np
+
+    from easevoice_trainer_amd.hip.audio import resample_pack
+
+    interval = 0.3
+    dev = torch.device("cuda:0")
+    voice = build_voice(dev, torch.bfloat16)
+    codes, texts, refer = workload(args.fragments)
+    codes, texts, refer = [c.to(dev) for c in codes], [t.to(dev) for t in texts], refer.to(dev)
+    audio_s = sum(2 * c.numel() for c in codes) / 50.0
+    pad = torch.nn.utils.rnn.pad_sequence
+    rates = [32000] + [r for r in args.out_rate if r != 32000]
+    ks = [1] + [k for k in args.batches if k != 1]
+
+    def groups(k, **kw):
+        """every group of k through the s2 decoder -> per group a list of waveforms, or a PackedAudio"""
+        for i in range(0, len(codes), k):
+            cs, ts = codes[i:i + k], texts[i:i + k]
+            if k == 1:
+                w = voice.decode(cs[0].view(1, 1, -1), ts[0].view(1, -1), refer)[0, 0]
+                yield (resample_pack(w, [w.numel()], 1, 32000, kw["out_rate"], kw["out_format"], interval=kw["interval"])
+                       if kw else [w])
+            else:
+                yield voice.decode_batch(pad(cs, batch_first=True).unsqueeze(0), [c.numel() for c in cs],
+                                         pad(ts, batch_first=True), [t.numel() for t in ts], refer, **kw)
+
+    def host_int16(k):
+        zero = np.zeros(int(32000 * interval), dtype=np.int16)
+        out = []
+        for ws in groups(k):
+            out.append(np.concatenate([a for w in ws for a in ((w.float().cpu().numpy() * 32768).astype(np.int16), zero)]))
+        return out
+
+    def pcm(k, rate, host=False):
+        out = []
+        for pa in groups(k, out_rate=rate, out_format="int16", interval=interval):
+            out.append(pa.data.cpu() if host else pa.data)
+        return out
+
+    modes = []
+    for k in ks:
+        modes.append((f"device/{k}", lambda k=k: [w for ws in groups(k) for w in ws]))
+        modes.append((f"host_int16/{k}", lambda k=k: host_int16(k)))
+        modes.append((f"pcm_32000_host/{k}", lambda k=k: pcm(k, 32000, True)))
+        modes += [(f"pcm_{r}/{k}", lambda k=k, r=r: pcm(k, r)) for r in rates]
+    for _name, fn in modes:                       # warm-up: every shape of every mode once
+        fn()
+        torch.cuda.synchronize()
+    # the bytes: the packed buffer at 32 kHz against the baseline's, first group of 4 under one prior noise.  They may differ
+    # only where |x| * 32768 reaches 32768 (numpy wraps around, the launch saturates)
+    noise = torch.randn(4, 192, 2 * max(c.numel() for c in codes[:4]) + 8, device=dev)
+    a4 = (pad(codes[:4], batch_first=True).unsqueeze(0), [c.numel() for c in codes[:4]], pad(texts[:4], batch_first=True),
+          [t.numel() for t in texts[:4]], refer)
+    ws = voice.decode_batch(*a4, noise=noise)
+    pa = voice.decode_batch(*a4, noise=noise, out_rate=32000, out_format="int16", interval=interval)
+    zero = np.zeros(int(32000 * interval), dtype=np.int16)
+    want = np.concatenate([a for w in ws for a in ((w.float().cpu().numpy() * 32768).astype(np.int16), zero)])
+    differing = int((pa.data.cpu().numpy() != want).sum())
+    times = {name: [] for name, _ in modes}
+    for _ in range(args.reps):
+        for name, fn in modes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / 1e3)
+    # the finishing launch alone, on the rows of every group (device events around the call, median over groups and reps)
+    finish = {}
+    for k in ks:
+        rows = []
+        for ws in groups(k):
+            rows.append((pad(list(ws), batch_first=True).contiguous(), [w.numel() for w in ws]))
+        for r in rates:
+            us = []
+            for _ in range(args.reps + 1):
+                for x, lens in rows:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    resample_pack(x, lens, 1, 32000, r, "int16", interval=interval)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us.append(e0.elapsed_time(e1) * 1e3)
+            finish[f"{r}/{k}"] = round(_median(us[len(rows):]), 1)
+    res = {"tool": "tools/bench_s2_decode.py --pcm", "device": torch.cuda.get_device_name(0), "dtype": "bf16",
+           "fragments": len(codes), "audio_seconds": round(audio_s, 2), "reps": args.reps, "interval_s": interval,
+           "baseline": "host_int16/<k> of this run: the same decode, then per fragment .float().cpu().numpy() * 32768, "
+                       "astype(int16), concatenated with the zeros behind each fragment",
+           "samples_differing_from_baseline_bytes_first_group": differing,
+           "finish_launch_us_median_per_group": finish, "modes": {}}
+    for name, _ in modes:
+        v = sorted(times[name])
+        med = _median(v)
+        res["modes"][name] = {"seconds_median": round(med, 4), "seconds_min": round(v[0], 4), "seconds_max": round(v[-1], 4),
+                              "fragments_per_s": round(len(codes) / med, 1)}
+    for name, m in res["modes"].items():
+        m["ratio_vs_host_int16"] = round(res["modes"]["host_int16/" + name.split("/")[1]]["seconds_median"] / m["seconds_median"], 3)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -67,8 +189,18 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[4, 8, 16])
     ap.add_argument("--speed", type=float, default=None, help="one speed for every fragment")
     ap.add_argument("--mixed-speeds", action="store_true", help="a seeded choice out of 0.8, 1.0, 1.25 per fragment")
+    ap.add_argument("--pcm", action="store_true", help="time the way to packed int16 PCM (profiles/s2_decode_pcm.json)")
+    ap.add_argument("--out-rate", type=int, nargs="+", default=[16000, 48000], help="with --pcm: output rates next to 32000")
     ap.add_argument("--out", default=None, help="default: profiles/s2_decode_batch.json, at a speed profiles/s2_decode_batch_speed.json")
     args = ap.parse_args()
+    if args.pcm:
+        if args.speed is not None or args.mixed_speeds:
+            raise SystemExit("--pcm is measured at speed 1")
+        if not torch.cuda.is_available():
+            raise RuntimeError("bench_s2_decode needs a GPU: nothing is measured without one")
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "s2_decode_pcm.json")
+        return main_pcm(args)
     if args.speed is not None and args.mixed_speeds:
         raise SystemExit("--speed and --mixed-speeds exclude each other")
     at_speed = args.speed is not None or args.mixed_speeds
