@@ -8,7 +8,12 @@
 //   * per-channel normalisation over time + GELU: HuBERT's first feature-extractor layer (GroupNorm with one channel per
 //     group, "feat_extract_norm": "group", then GELU) -- statistics per (item, channel) over all frames, two passes for
 //     the variance (a 10 s clip has 32 000 frames: E[x^2] - E[x]^2 in fp32 would lose the variance of a near-constant
-//     channel).
+//     channel);
+//   * the same layer for a RAGGED batch of clips with the convolution in front of it folded in (evt_hubert_front_rows:
+//     conv 1 -> 512, k 10, stride 5 recomputed in each of three passes instead of stored, per-row frame counts, partial
+//     sums per chunk of frames in a fixed order so that a row does not depend on the batch it is in);
+//   * the clip rescaling of the `ssl` step for a ragged batch (evt_clip_rescale_rows: peak, the float clip for HuBERT and
+//     the int16 clip for 5-wav32k, numpy's float32 arithmetic operation for operation).
 // Inference only: forward launches, no saved statistics.  HBM-bound streams: 16-byte accesses along the channel axis.
 #include "evt_common.h"
 #include "../../include/evt.h"
@@ -71,6 +76,213 @@ inline int ew_blocks(long n) {
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
 
+// ---- HuBERT's first layer on a ragged batch: conv(1 -> 512, k 10, s 5) + GroupNorm(512, 512) + GELU, the convolution
+// never stored.  A block owns kFChunk consecutive frames of ONE row, counted from the row's frame 0, for all 512 channels:
+// lane l of every wave holds the 80 weights of channels 8 l .. 8 l + 7 in registers (staged through LDS so that the 20 KB
+// are read from memory coalesced, once per block), the four waves take the chunk's frames v, v + 4, ..., and the samples
+// of the chunk (5 * frames + 5 floats) are read from LDS as wave-wide broadcasts.  Three passes over the same staged data
+// compute the same fma chain, so the value that is normalised is bit for bit the value the statistics were taken from.
+constexpr int kFC = 512, kFK = 10, kFS = 5;
+constexpr int kFChunk = EVT_HUBERT_FRONT_CHUNK;
+constexpr int kFSpan = kFChunk * kFS + (kFK - kFS);
+constexpr int kFWRow = kFC + 4;    // LDS row of one tap: 516 floats keep the rows 16-byte aligned and the staging stores
+                                   // (lane -> (channel, tap) = (i / 10, i % 10), bank 4 tap + channel) at most 2-way
+
+__device__ __forceinline__ int front_frames(int n) { return n < kFK ? 0 : (n - kFK) / kFS + 1; }
+
+enum { kFrontSum = 1, kFrontSq = 2, kFrontStore = 3 };
+
+template <typename T> __device__ __forceinline__ void store8(T* p, const float* v);
+template <> __device__ __forceinline__ void store8<float>(float* p, const float* v) {
+  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+}
+template <> __device__ __forceinline__ void store8<h16_t>(h16_t* p, const float* v) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(f2h_pack(v[0], v[1]), f2h_pack(v[2], v[3]), f2h_pack(v[4], v[5]),
+                                            f2h_pack(v[6], v[7]));
+}
+
+// grid (chunks of the longest possible row, nseq), 256 threads.  part [nseq][nchunk][512]: kFrontSum / kFrontSq write the
+// chunk's channel sums (of c / of (c - mean)^2) there; blocks behind a row's last frame write nothing (the statistics
+// kernel reads only the row's own chunks) and, in kFrontStore, store the zero tail.
+template <typename T, int PASS>
+__global__ __launch_bounds__(256, 3) void hubert_front_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lens,
+                                                           int N, int T1, int nchunk, const float* __restrict__ w,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           float* __restrict__ part, T* __restrict__ out) {
+  __shared__ __align__(16) float wl[kFK * kFWRow];
+  __shared__ float xs[kFSpan];
+  __shared__ float red[PASS == kFrontStore ? 1 : 4][PASS == kFrontStore ? 1 : kFC];
+  const int s = blockIdx.y, chunk = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c0 = lane * 8;
+  const int Ts = front_frames(min(max(lens[s], 0), N));
+  const int t0 = chunk * kFChunk;
+  const int tl = min(kFChunk, Ts - t0);              // live frames of this chunk (block-uniform; <= 0: none)
+  const int tw = min(kFChunk, T1 - t0);              // frames of this chunk that exist in `out`
+  T* ob = PASS == kFrontStore ? out + ((long)s * T1 + t0) * kFC + c0 : nullptr;
+  if (PASS == kFrontStore) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int f = max(tl, 0) + wave; f < tw; f += 4) store8<T>(ob + (long)f * kFC, z);
+  }
+  if (tl <= 0) return;
+  for (int i = threadIdx.x; i < kFC * kFK; i += 256) wl[(i % kFK) * kFWRow + i / kFK] = w[i];
+  // samples 5 t0 .. 5 (t0 + tl - 1) + 9 <= 5 (Ts - 1) + 9 < n_s: nothing at or behind the row's end is read
+  const float* xr = wav + (long)s * N + (long)t0 * kFS;
+  for (int i = threadIdx.x; i < tl * kFS + (kFK - kFS); i += 256) xs[i] = xr[i];
+  __syncthreads();
+  float wr[kFK][8];
+#pragma unroll
+  for (int j = 0; j < kFK; ++j) {
+    const float4 a = *reinterpret_cast<const float4*>(&wl[j * kFWRow + c0]);
+    const float4 b = *reinterpret_cast<const float4*>(&wl[j * kFWRow + c0 + 4]);
+    wr[j][0] = a.x, wr[j][1] = a.y, wr[j][2] = a.z, wr[j][3] = a.w;
+    wr[j][4] = b.x, wr[j][5] = b.y, wr[j][6] = b.z, wr[j][7] = b.w;
+  }
+  float m[8], r[8], g[8], bt[8], acc[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    acc[c] = 0.f;
+    m[c] = PASS != kFrontSum ? mean[(long)s * kFC + c0 + c] : 0.f;
+    r[c] = PASS == kFrontStore ? rstd[(long)s * kFC + c0 + c] : 0.f;
+    g[c] = PASS == kFrontStore ? gamma[c0 + c] : 0.f;
+    bt[c] = PASS == kFrontStore ? beta[c0 + c] : 0.f;
+  }
+  for (int f = wave; f < tl; f += 4) {
+    float xv[kFK], cv[8];
+#pragma unroll
+    for (int j = 0; j < kFK; ++j) xv[j] = xs[f * kFS + j];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      float a = 0.f;
+#pragma unroll
+      for (int j = 0; j < kFK; ++j) a = fmaf(wr[j][c], xv[j], a);
+      cv[c] = a;
+    }
+    if (PASS == kFrontSum) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) acc[c] += cv[c];
+    } else if (PASS == kFrontSq) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const float d = cv[c] - m[c];
+        acc[c] = fmaf(d, d, acc[c]);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        cv[c] = gelu_f((cv[c] - m[c]) * r[c] * g[c] + bt[c]);
+        // one erf at a time: interleaved, the eight polynomial evaluations take ~390 registers (one wave per SIMD)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      store8<T>(ob + (long)f * kFC, cv);
+    }
+  }
+  if (PASS != kFrontStore) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) red[wave][c0 + c] = acc[c];
+    __syncthreads();
+    float* pp = part + ((long)s * nchunk + chunk) * kFC;
+    for (int ch = threadIdx.x; ch < kFC; ch += 256) pp[ch] = (red[0][ch] + red[1][ch]) + (red[2][ch] + red[3][ch]);
+  }
+}
+
+// grid (2, nseq), 256 threads: thread = channel.  dst[s][ch] = sum of the row's chunk partials in ascending chunk order
+// over T_s (mode 0: the mean), or rsqrt(that + eps) (mode 1: from the squared deviations); 0 for a row without frames.
+__global__ __launch_bounds__(256) void hubert_front_stat_kernel(const float* __restrict__ part,
+                                                                const int32_t* __restrict__ lens, int N, int nchunk,
+                                                                float eps, int mode, float* __restrict__ dst) {
+  const int s = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
+  const int Ts = front_frames(min(max(lens[s], 0), N));
+  const int nc = (Ts + kFChunk - 1) / kFChunk;
+  const float* pp = part + (long)s * nchunk * kFC + ch;
+  float a = 0.f;
+  for (int k = 0; k < nc; ++k) a += pp[(long)k * kFC];
+  float v = 0.f;
+  if (Ts > 0) v = mode == 0 ? a / (float)Ts : rsqrtf(a / (float)Ts + eps);
+  dst[(long)s * kFC + ch] = v;
+}
+
+template <typename T>
+void launch_front(hipStream_t st, const float* wav, const int32_t* lens, int nseq, int N, int T1, int nchunk, const float* w,
+                  const float* gamma, const float* beta, float eps, T* out, float* ws) {
+  float* part = ws;
+  float* mean = ws + (long)nseq * nchunk * kFC;
+  float* rstd = mean + (long)nseq * kFC;
+  const dim3 grid(nchunk, nseq), sgrid(kFC / 256, nseq);
+  hipLaunchKernelGGL((hubert_front_kernel<T, kFrontSum>), grid, dim3(256), 0, st, wav, lens, N, T1, nchunk, w, gamma, beta,
+                     mean, rstd, part, out);
+  hipLaunchKernelGGL(hubert_front_stat_kernel, sgrid, dim3(256), 0, st, part, lens, N, nchunk, eps, 0, mean);
+  hipLaunchKernelGGL((hubert_front_kernel<T, kFrontSq>), grid, dim3(256), 0, st, wav, lens, N, T1, nchunk, w, gamma, beta,
+                     mean, rstd, part, out);
+  hipLaunchKernelGGL(hubert_front_stat_kernel, sgrid, dim3(256), 0, st, part, lens, N, nchunk, eps, 1, rstd);
+  hipLaunchKernelGGL((hubert_front_kernel<T, kFrontStore>), grid, dim3(256), 0, st, wav, lens, N, T1, nchunk, w, gamma, beta,
+                     mean, rstd, part, out);
+}
+
+// ---- normalize.py:148-153 on a ragged batch of clips
+// one block per row: the maximum is order-free; a NaN anywhere in the row makes the peak NaN (as np.abs(x).max())
+__global__ __launch_bounds__(1024) void clip_peak_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens, int N,
+                                                         float* __restrict__ peak) {
+  __shared__ float red[16];
+  __shared__ int bad[16];
+  const int s = blockIdx.x;
+  const int n = min(max(lens[s], 0), N);
+  const float* xr = x + (long)s * N;
+  float m = 0.f;
+  int nan = 0;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const float v = xr[i];
+    nan |= v != v;
+    m = fmaxf(m, fabsf(v));
+  }
+  m = wave_reduce_max(m);
+  nan = __any(nan);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = m, bad[wave] = nan;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 16; ++k) m = fmaxf(m, red[k]), nan |= bad[k];
+    peak[s] = nan ? __int_as_float(0x7fc00000) : m;
+  }
+}
+
+// (int16) trunc(v), saturating where the C cast is undefined; NaN -> 0
+__device__ __forceinline__ int16_t trunc_s16(float v) {
+  const float t = fminf(fmaxf(truncf(v), -32768.f), 32767.f);
+  return v != v ? (int16_t)0 : (int16_t)(int)t;
+}
+
+// every operation rounded to fp32 on its own: no fma may be formed from the product and the sum
+__device__ __forceinline__ float rescale_one(float v, float pk, float ca, float cb) {
+#pragma clang fp contract(off)
+  const float q = __fdiv_rn(v, pk);
+  const float a = __fmul_rn(q, ca);
+  const float b = __fmul_rn(cb, v);
+  return __fadd_rn(a, b);
+}
+
+__global__ __launch_bounds__(256) void clip_rescale_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens, int N,
+                                                           const float* __restrict__ peak, float c1, float c2, float c1b,
+                                                           float c2b, float* __restrict__ f, int16_t* __restrict__ q) {
+  const int s = blockIdx.y;
+  const int n = min(max(lens[s], 0), N);
+  const float pk = peak[s];
+  const long row = (long)s * N;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    float fv = 0.f;
+    int16_t qv = 0;
+    if (i < n) {
+      const float v = x[row + i];
+      fv = rescale_one(v, pk, c1b, c2b);
+      qv = trunc_s16(rescale_one(v, pk, c1, c2));
+    }
+    f[row + i] = fv;
+    q[row + i] = qv;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -102,6 +314,41 @@ int evt_channel_norm_gelu_fwd(int32_t dtype, const void* x, const float* gamma, 
     hipLaunchKernelGGL(channel_norm_gelu_kernel<float>, grid, dim3(256), 0, st, (const float*)x, gamma, beta, eps, (float*)out,
                        T, C, apply_gelu);
   else return EVT_ENOTSUP;
+  return evt_check_launch();
+}
+
+int64_t evt_hubert_front_ws_floats(int32_t nseq, int32_t N) {
+  if (nseq <= 0 || nseq > 65535 || N < kFK) return 0;
+  const int64_t T1 = (N - kFK) / kFS + 1;
+  return (int64_t)nseq * kFC * ((T1 + kFChunk - 1) / kFChunk + 2);
+}
+
+int evt_hubert_front_rows(int32_t dtype, const float* wav, const int32_t* lens, int32_t nseq, int32_t N, const float* w,
+                          const float* gamma, const float* beta, float eps, void* out, float* ws, int64_t ws_floats,
+                          void* stream) {
+  if (!wav || !lens || !w || !gamma || !beta || !out || !ws || nseq <= 0 || nseq > 65535 || N < kFK || !(eps >= 0.f))
+    return EVT_EINVAL;
+  if (((uintptr_t)out & 15) || ((uintptr_t)ws & 15) || ws_floats < evt_hubert_front_ws_floats(nseq, N)) return EVT_EINVAL;
+  if (dtype != EVT_DT_HALF && dtype != EVT_DT_F32) return EVT_ENOTSUP;
+  const int T1 = (N - kFK) / kFS + 1;
+  const int nchunk = (T1 + kFChunk - 1) / kFChunk;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == EVT_DT_HALF) launch_front<h16_t>(st, wav, lens, nseq, N, T1, nchunk, w, gamma, beta, eps, (h16_t*)out, ws);
+  else launch_front<float>(st, wav, lens, nseq, N, T1, nchunk, w, gamma, beta, eps, (float*)out, ws);
+  return evt_check_launch();
+}
+
+int evt_clip_rescale_rows(const float* x, const int32_t* lens, int32_t nseq, int32_t N, float* f, int16_t* q, float* peak,
+                          void* stream) {
+  if (!x || !lens || !f || !q || !peak || nseq <= 0 || nseq > 65535 || N <= 0) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  // normalize.py:61-62,151-153: maxx = 0.95, alpha = 0.5; the products in double as Python takes them, rounded once
+  const double maxx = 0.95, alpha = 0.5;
+  const float c1 = (float)(maxx * alpha * 32768), c2 = (float)((1 - alpha) * 32768);
+  const float c1b = (float)(maxx * alpha * 1145.14), c2b = (float)((1 - alpha) * 1145.14);
+  hipLaunchKernelGGL(clip_peak_kernel, dim3(nseq), dim3(1024), 0, st, x, lens, N, peak);
+  hipLaunchKernelGGL(clip_rescale_kernel, dim3((N + 1023) / 1024, nseq), dim3(256), 0, st, x, lens, N, peak, c1, c2, c1b, c2b,
+                     f, q);
   return evt_check_launch();
 }
 

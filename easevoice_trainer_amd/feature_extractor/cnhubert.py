@@ -16,6 +16,9 @@ state_dict loads as is (`load_hf_state_dict`); channels-last [B, T, C] rows; eve
   12 encoder layers   packed q | k | v projection + attention core (evt_mha_fwd through hip/enc.py::rel_self_attention,
                       window None), out projection, LayerNorm(x + attn), Linear 768 -> 3072, GELU, Linear 3072 -> 768,
                       LayerNorm(x + ffn)
+A RAGGED batch of clips goes through `HubertModel.forward_rows` (`CNHubert.last_hidden_state_batch` / `.batch`): the first
+convolution, its GroupNorm over each row's own frames and GELU in evt_hubert_front_rows, tails zeroed in front of the
+positional convolution, frame counts as key lengths -- row b is what the clip gives alone.
 Inference only (`torch.no_grad`); dropout / SpecAugment masking are training-time and absent, as in `model.eval()`.
 There is no torch fallback: a shape the kernels do not serve raises.
 """
@@ -23,15 +26,16 @@ import torch
 from torch import nn
 
 from ..hip import lib as L
-from ..hip.conv import EvtConv1d
+from ..hip.conv import EvtConv1d, mask_tail
 from ..hip.enc import new_site, rel_self_attention
-from ..hip.feat import add_layernorm, channel_norm_gelu, gelu_rows
+from ..hip.feat import add_layernorm, channel_norm_gelu, gelu_rows, hubert_front_rows
 from ..module.attentions import linear_rows
 from ..runtime import ModelRuntime
 
 CONV_DIM = (512, 512, 512, 512, 512, 512, 512)
 CONV_KERNEL = (10, 3, 3, 3, 3, 2, 2)
 CONV_STRIDE = (5, 2, 2, 2, 2, 2, 2)
+MIN_SAMPLES = 400                        # the shortest clip with a frame: the receptive field of the seven convolutions
 
 
 class _LN(nn.Module):
@@ -195,6 +199,51 @@ class HubertModel(nn.Module):
         lens = torch.full((x.size(0),), x.size(1), dtype=torch.int32, device=x.device)
         return self.encoder(x, lens)
 
+    @staticmethod
+    def layer_frames(n_samples):
+        """the frame count behind each of the seven convolutions (`frames`' recurrence, every step kept)"""
+        out = []
+        for k, s in zip(CONV_KERNEL, CONV_STRIDE):
+            n_samples = (n_samples - k) // s + 1
+            out.append(n_samples)
+        return out
+
+    @staticmethod
+    def check_clip_lengths(n_samples, width):
+        """a clip needs 400 samples for one frame (the receptive field of the seven convolutions) and must fit its row"""
+        n_samples = [int(n) for n in n_samples]
+        for b, n in enumerate(n_samples):
+            if n < MIN_SAMPLES:
+                raise ValueError(f"clip {b} has {n} samples: fewer than {MIN_SAMPLES}, HuBERT has no frame for it")
+            if n > width:
+                raise ValueError(f"clip {b} has {n} samples in rows of {width}")
+        return n_samples
+
+    def forward_rows(self, wav, n_samples):
+        """A RAGGED batch: wav [B, N] float32 (16 kHz), row b live on its first n_samples[b] samples (what lies behind them is
+        never read) -> (last_hidden_state [B, T, 768] with T = frames(N), frame counts [frames(n_b)]); row b's first
+        frames(n_b) frames are what `forward` gives for that clip alone, within rounding.  What keeps the rows apart:
+        the first layer's statistics run over the row's own frames (hip/feat.py::hubert_front_rows, which also replaces
+        the stored convolution); the six strided convolutions have no padding, so a live frame reads live frames only;
+        the tails are zeroed in front of the positional convolution, which then sees behind a row's end the zeros its own
+        padding gives a clip alone; attention takes the rows' frame counts as key lengths."""
+        if wav.dim() != 2 or len(n_samples) != wav.size(0):
+            raise ValueError(f"forward_rows takes rows [B, N] and B lengths, got {tuple(wav.shape)} and {len(n_samples)}")
+        n_samples = self.check_clip_lengths(n_samples, wav.size(1))
+        rt = self._rt
+        wav = wav.to(rt.device, torch.float32).contiguous()
+        lens = torch.tensor(n_samples, dtype=torch.int32).to(rt.device)
+        first = self.feature_extractor.conv_layers[0]
+        x = hubert_front_rows(wav, lens, first.conv.weight.data.view(CONV_DIM[0], CONV_KERNEL[0]), first.layer_norm.weight.data,
+                              first.layer_norm.bias.data, first.layer_norm.eps, rt.dtype)
+        for layer in self.feature_extractor.conv_layers[1:]:
+            x = layer(x)
+        x = self.feature_projection(x)
+        frame_lens = [self.layer_frames(n)[-1] for n in n_samples]
+        flens = torch.tensor(frame_lens, dtype=torch.int32).to(rt.device)
+        x = mask_tail(x.contiguous(), flens)
+        return self.encoder(x, flens), frame_lens
+
 
 class CNHubert:
     """src/easevoice/feature_extractor/cnhubert.py:16-32 on the GPU: `model(wav16k [n]) -> [1, 768, T]` float32 on the CPU,
@@ -224,6 +273,36 @@ class CNHubert:
     @torch.no_grad()
     def __call__(self, wav16k):
         return self.last_hidden_state(wav16k).transpose(1, 2).float().cpu()
+
+    @torch.no_grad()
+    def last_hidden_state_batch(self, wavs):
+        """wavs: a list of 1-D 16 kHz clips of any lengths, or (padded [B, N], lengths) -- the padding's content is never
+        read -> (last_hidden_state [B, Tmax, 768] on the GPU with zeros behind a row's frames, frame counts): ONE pass of
+        the model over the ragged batch (HubertModel.forward_rows); a clip below 400 samples raises ValueError"""
+        L.set_half(self.dtype)
+        if isinstance(wavs, tuple):
+            padded, lens = wavs
+            padded = torch.as_tensor(padded, dtype=torch.float32)
+            lens = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        else:
+            clips = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in wavs]
+            if not clips:
+                raise ValueError("last_hidden_state_batch: no clips")
+            lens = [c.numel() for c in clips]
+            HubertModel.check_clip_lengths(lens, max(lens))
+            padded = torch.zeros(len(clips), max(lens), dtype=torch.float32, device=clips[0].device)
+            for b, c in enumerate(clips):
+                padded[b, :lens[b]] = c
+        hs, frame_lens = self.model.forward_rows(padded, lens)
+        hs = hs[:, :max(frame_lens)].contiguous()
+        return mask_tail(hs, torch.tensor(frame_lens, dtype=torch.int32).to(hs.device)), frame_lens
+
+    @torch.no_grad()
+    def batch(self, wavs16k):
+        """what `__call__` returns for each clip -- [1, 768, T_b] float32 on the CPU -- from one ragged pass"""
+        hs, frame_lens = self.last_hidden_state_batch(wavs16k)
+        hs = hs.float().cpu()
+        return [hs[b:b + 1, :t].transpose(1, 2).clone(memory_format=torch.preserve_format) for b, t in enumerate(frame_lens)]
 
 
 def _read_state_dict(weights):

@@ -13,7 +13,10 @@ not under /root/reference: `resample_half` restates resampy's published algorith
 interpolation table is only ever read at every 256th entry and the interpolator degenerates to a symmetric 255-tap FIR
 (64 zero crossings, roll-off 0.9475937167399596, Kaiser beta 14.769656459379492, gain 1/2) followed by taking every second
 sample.  Parity of this one function is UNPINNED (no golden vector in the reference, package absent); it is checked against
-its own definition and against the ideal half-band behaviour (tests/test_feature_extractors_cpu.py)."""
+its own definition and against the ideal half-band behaviour (tests/test_feature_extractors_cpu.py).
+
+`FeatureWriter.ssl_batch` is `ssl` for a group of clips: peak, rescaling and resampling on the GPU (hip/feat.py::
+clip_rescale_rows, hip/audio.py::resample_pack at 1/2) and one ragged pass of the model (CNHubert.batch)."""
 import os
 
 import numpy as np
@@ -87,6 +90,68 @@ class FeatureWriter:
         wavfile.write(os.path.join(self.wav_dir, name), 32000, wav_int16)
         torch.save(ssl, path)
         return True
+
+    def _front_rows(self, clips):
+        """the device half of `ssl_batch` in front of the model: clips (1-D float32 arrays, 32 kHz) -> (peaks, the int16
+        clips for 5-wav32k, the 16 kHz clips as zero-filled rows [B, N16] on the GPU, their lengths).  One upload, one
+        hip/feat.py::clip_rescale_rows, one hip/audio.py::resample_pack (32000 -> 16000, float32, no gap: resample_half's
+        operator), peaks and int16 rows back in one copy each."""
+        from ..hip.audio import resample_pack
+        from ..hip.feat import clip_rescale_rows
+
+        device = self.hubert.device
+        lens = [len(c) for c in clips]
+        host = np.zeros((len(clips), max(lens)), dtype=np.float32)
+        for b, c in enumerate(clips):
+            host[b, :lens[b]] = c
+        x = torch.from_numpy(host).to(device)
+        lens_dev = torch.tensor(lens, dtype=torch.int32).to(device)
+        with torch.no_grad():
+            f, q, peak = clip_rescale_rows(x, lens_dev)
+            packed = resample_pack(f, lens, 1, 32000, 16000, "float32", interval=0.0, lens_dev=lens_dev)
+            rows16 = torch.zeros(len(clips), max(max(packed.lengths), 1), dtype=torch.float32, device=device)
+            for b in range(len(clips)):
+                rows16[b, :packed.lengths[b]] = packed.row(b)
+        q = q.cpu().numpy()
+        return peak.cpu().tolist(), [q[b, :lens[b]] for b in range(len(clips))], rows16, list(packed.lengths)
+
+    def ssl_batch(self, names, clips32k) -> list:
+        """`ssl` for several clips with ONE pass of the model over the ragged batch (hubert: feature_extractor.CNHubert, or
+        any object with its `device` and `batch((rows [B, N], lengths))`).  Per name what `ssl` returns: True for a name
+        whose feature file exists (skipped before anything is uploaded) and for a clip the reference skips (peak above
+        2.2, nothing written), False for a non-finite peak or non-finite features (nothing written), True after writing
+        4-cnhubert/<name>.pt and 5-wav32k/<name>.  The int16 file is byte for byte `ssl`'s; the features differ from
+        `ssl`'s within fp32 rounding (the resampler accumulates in fp32, resample_half in float64)."""
+        from scipy.io import wavfile
+
+        names = list(names)
+        if len(names) != len(clips32k):
+            raise ValueError(f"{len(names)} names for {len(clips32k)} clips")
+        done = [True] * len(names)
+        todo = [i for i, name in enumerate(names) if not os.path.exists(os.path.join(self.hubert_dir, name + ".pt"))]
+        if not todo:
+            return done
+        clips = [np.asarray(clips32k[i], dtype=np.float32).reshape(-1) for i in todo]
+        peaks, wav16, rows16, lens16 = self._front_rows(clips)
+        keep = []
+        for j, i in enumerate(todo):
+            if not np.isfinite(peaks[j]):
+                done[i] = False
+            elif not peaks[j] > 2.2:
+                keep.append(j)
+        if not keep:
+            return done
+        if len(keep) < len(todo):
+            rows16 = rows16[torch.tensor(keep, device=rows16.device)]
+        feats = self.hubert.batch((rows16, [lens16[j] for j in keep]))
+        for j, ssl in zip(keep, feats):
+            i = todo[j]
+            if not bool(torch.isfinite(ssl).all()):
+                done[i] = False
+                continue
+            wavfile.write(os.path.join(self.wav_dir, names[i]), 32000, wav16[j])
+            torch.save(ssl, os.path.join(self.hubert_dir, names[i] + ".pt"))
+        return done
 
     def text(self, name, phones, word2ph, norm_text, language="zh", input_ids=None):
         """normalize.py:_process_text: the BERT feature only for Chinese items that do not have one yet; always the text line"""

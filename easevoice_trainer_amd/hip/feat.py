@@ -30,6 +30,78 @@ def channel_norm_gelu(x, gamma, beta, eps, gelu=True):
     return out
 
 
+FRONT_CHANNELS, FRONT_K, FRONT_STRIDE = 512, 10, 5     # HuBERT's first convolution
+# the argument lists of include/evt.h, given to ctypes so that a call with another count or kind of argument is refused
+FRONT_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+RESCALE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _rows_entry(name, argtypes):
+    fn = getattr(L.lib(), name)          # AttributeError for a library without the entry: there is no fallback
+    if fn.argtypes is None:
+        fn.argtypes, fn.restype = argtypes, C.c_int
+    return fn
+
+
+def _check_rows(what, x, lens):
+    """the lens checks of hip/conv.py::_check_lens for the clip front end: fp32 rows [nseq, N] and int32 lengths on one GPU"""
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.size(0) < 1:
+        raise L.EvtError(f"{what}: contiguous float32 rows [nseq, N] expected")
+    if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
+            or lens.numel() != x.size(0) or not lens.is_contiguous()):
+        raise L.EvtError(f"{what}: lens must be a contiguous int32 [{x.size(0)}] tensor on {x.device}")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise L.EvtError(f"{what} is inference only: run it under torch.no_grad()")
+
+
+def front_frames(n):
+    """frames of HuBERT's first layer for a row of n samples (0 below 10)"""
+    return 0 if n < FRONT_K else (int(n) - FRONT_K) // FRONT_STRIDE + 1
+
+
+def hubert_front_rows(wav, lens, weight, gamma, beta, eps, dtype):
+    """wav [nseq, N] fp32, lens int32 [nseq] (samples) on the GPU; weight fp32 [512, 10] (or the convolution's [512, 1, 10]),
+    gamma / beta fp32 [512] -> [nseq, (N - 10) // 5 + 1, 512] of dtype: conv + GroupNorm(512, 512) + GELU per row over the
+    row's own frames, zeros behind them (evt_hubert_front_rows; include/evt.h has the definition).  wav is not read at or
+    behind a row's length, a row comes out bit for bit as it does alone."""
+    _check_rows("hubert_front_rows", wav, lens)
+    nseq, n = wav.shape
+    if n < FRONT_K:
+        raise L.EvtError(f"hubert_front_rows: rows of at least {FRONT_K} samples expected, got {n}")
+    for name, t, numel in (("weight", weight, FRONT_CHANNELS * FRONT_K), ("gamma", gamma, FRONT_CHANNELS),
+                           ("beta", beta, FRONT_CHANNELS)):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != wav.device or t.numel() != numel
+                or not t.is_contiguous()):
+            raise L.EvtError(f"hubert_front_rows: {name} must be contiguous float32 with {numel} elements on {wav.device}")
+    code = L.dt_code(dtype)
+    ws_floats = L.lib().evt_hubert_front_ws_floats(nseq, n)
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=wav.device)
+    out = torch.empty(nseq, front_frames(n), FRONT_CHANNELS, dtype=dtype, device=wav.device)
+    L.check(_rows_entry("evt_hubert_front_rows", FRONT_ARGTYPES)(
+        code, wav.data_ptr(), lens.data_ptr(), nseq, n, weight.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps),
+        out.data_ptr(), ws.data_ptr(), ws_floats, L.stream_ptr()), "evt_hubert_front_rows")
+    return out
+
+
+def clip_rescale_rows(x, lens):
+    """x [nseq, N] fp32 32 kHz clips, lens int32 [nseq] on the GPU -> (f fp32 [nseq, N], q int16 [nseq, N], peak fp32 [nseq]):
+    normalize.py:148-153 per row -- rescale_clip's float clip for HuBERT, its int16 clip for 5-wav32k and the row's peak --
+    bit for bit numpy's float32 arithmetic, zeros behind a row's length (evt_clip_rescale_rows).  The caller reads `peak`
+    to drop rows above 2.2; q saturates where numpy's cast is undefined."""
+    _check_rows("clip_rescale_rows", x, lens)
+    nseq, n = x.shape
+    if n < 1:
+        raise L.EvtError("clip_rescale_rows: empty rows")
+    f = torch.empty_like(x)
+    q = torch.empty(nseq, n, dtype=torch.int16, device=x.device)
+    peak = torch.empty(nseq, dtype=torch.float32, device=x.device)
+    L.check(_rows_entry("evt_clip_rescale_rows", RESCALE_ARGTYPES)(
+        x.data_ptr(), lens.data_ptr(), nseq, n, f.data_ptr(), q.data_ptr(), peak.data_ptr(), L.stream_ptr()),
+        "evt_clip_rescale_rows")
+    return f, q, peak
+
+
 def add_layernorm(x, r, gamma, beta, eps):
     """LayerNorm(x + r) over the last axis (r may be None): evt_add_layernorm_fwd, statistics discarded"""
     x = x.contiguous()

@@ -914,6 +914,48 @@ int evt_gelu_rows_fwd(int32_t dtype, const void* x, const float* bias, void* out
 int evt_channel_norm_gelu_fwd(int32_t dtype, const void* x, const float* gamma, const float* beta, float eps, void* out,
                               int32_t nseq, int32_t T, int32_t C, int32_t apply_gelu, void* stream);
 
+/* HuBERT's first feature-extractor layer (Conv1d(1, 512, k = 10, stride 5, no bias) -> GroupNorm(512, 512) -> GELU) for a
+ * RAGGED batch of clips, without materialising the convolution: the clip front end of CNHubert.batch.
+ *   wav [nseq][N] fp32; lens device int32 [nseq] in samples, row s has n_s = min(max(lens[s], 0), N) live samples and wav is
+ *   never read at or behind them; w fp32 [512][10]; gamma, beta fp32 [512].
+ *   out [nseq][T1][512] of dtype, T1 = (N - 10) / 5 + 1.  Row s has T_s = (n_s - 10) / 5 + 1 frames (0 when n_s < 10):
+ *     c[t][ch] = sum_{j < 10} w[ch][j] * wav[s][5 t + j]     (fp32 fma chain, j ascending from 0)
+ *     mean[ch] = sum_t c / T_s;  var[ch] = sum_t (c - mean)^2 / T_s  (biased; two passes, never E[x^2] - E[x]^2)
+ *     out[s][t][ch] = gelu_erf((c - mean) * rsqrt(var + eps) * gamma[ch] + beta[ch])   t < T_s, rounded once
+ *     out[s][t][:]  = 0                                                                T_s <= t < T1
+ *   Every element of out is written.
+ * Summation order: a block owns EVT_HUBERT_FRONT_CHUNK consecutive frames of one row counted from the row's frame 0; inside
+ * a chunk, frames t = v, v + 4, ... (v = 0 .. 3) are added in ascending order into four partial sums, combined as
+ * (p0 + p1) + (p2 + p3); the per-chunk sums go to the workspace and are added in ascending chunk order.  Neither nseq nor N
+ * enters: row s is bit for bit what the entry gives for that row alone (nseq = 1) with any N >= n_s.
+ * Five launches on `stream` (chunk sums, mean, chunk sums of squared deviations, rstd, normalise + GELU + store; the second
+ * and third pass recompute the convolution from the staged samples), no host synchronisation: legal in a captured graph.
+ * ws: fp32 workspace of at least evt_hubert_front_ws_floats(nseq, N) = nseq * 512 * (ceil(T1 / CHUNK) + 2) floats, 16-byte
+ * aligned, contents undefined afterwards.  EVT_EINVAL for a NULL pointer, nseq <= 0 or > 65535, N < 10, eps < 0 or NaN,
+ * ws_floats too small, out or ws not 16-byte aligned; EVT_ENOTSUP for a dtype the build does not serve.  The query returns
+ * 0 for arguments the entry refuses. */
+#define EVT_HUBERT_FRONT_CHUNK 64
+int64_t evt_hubert_front_ws_floats(int32_t nseq, int32_t N);
+int evt_hubert_front_rows(int32_t dtype, const float* wav, const int32_t* lens, int32_t nseq, int32_t N, const float* w,
+                          const float* gamma, const float* beta, float eps, void* out, float* ws, int64_t ws_floats,
+                          void* stream);
+
+/* The clip rescaling of the reference's `ssl` step (src/normalization/normalize.py:148-153, restated for one clip by
+ * feature_extractor/normalize.py::rescale_clip) for a ragged batch of 32 kHz clips.  x [nseq][N] fp32, lens device int32
+ * [nseq], n_s = min(max(lens[s], 0), N), x never read at or behind n_s.  Two launches, no host synchronisation:
+ *   peak[s] = max_{i < n_s} |x[s][i]|  (fp32 [nseq], an OUTPUT; NaN if the row holds a NaN, 0 for an empty row)
+ *   f[s][i] = fadd(fmul(fdiv(x, peak), c1b), fmul(c2b, x))         fp32 [nseq][N]: the clip that is resampled for HuBERT
+ *   q[s][i] = (int16) trunc(fadd(fmul(fdiv(x, peak), c1), fmul(c2, x)))  int16 [nseq][N]: the clip written to 5-wav32k
+ *   f = 0, q = 0 for n_s <= i < N
+ * every operation rounded to fp32 on its own (round to nearest even, no contraction into an fma), as numpy evaluates the
+ * float32 expression; c1 = (float)(0.95 * 0.5 * 32768), c2 = (float)(0.5 * 32768), c1b = (float)(0.95 * 0.5 * 1145.14),
+ * c2b = (float)(0.5 * 1145.14), the products taken in double.  For a clip whose peak is <= 1 the value under the cast is at
+ * most 31 948.8 in magnitude and q equals numpy's astype(int16) bit for bit.  Outside the int16 range, where numpy's cast is
+ * undefined, q SATURATES to [-32768, 32767], and a NaN (a NaN sample, or 0 / 0 in a silent clip) gives q = 0.
+ * EVT_EINVAL for a NULL pointer, nseq <= 0 or > 65535, N <= 0. */
+int evt_clip_rescale_rows(const float* x, const int32_t* lens, int32_t nseq, int32_t N, float* f, int16_t* q, float* peak,
+                          void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
