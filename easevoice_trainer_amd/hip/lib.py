@@ -23,6 +23,10 @@ class EvtError(RuntimeError):
     pass
 
 
+# return codes of the C ABI (csrc/evt_common.h): 0 is success
+EVT_OK, EVT_ELAUNCH, EVT_EINVAL, EVT_ENOTSUP = 0, 5, 22, 95
+
+
 class ConvParams(C.Structure):
     _fields_ = [
         ("dtype", C.c_int32), ("nseq", C.c_int32), ("lin", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
