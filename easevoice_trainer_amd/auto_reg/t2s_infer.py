@@ -22,7 +22,13 @@ Same token sequence as the reference for the same sampling noise; a different ex
     ("seed"); StreamControl.preempt(r) takes a running row out of its slot with the tokens it has, and the two keys
     continue it exactly, here or in another stream; score_stream forces whole sequences and returns their
     log-probabilities.
-The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token."""
+The reference reads two device scalars per token (the EOS tests of :846) and reallocates every cache tensor per token.
+
+How the module is laid out: _Session owns what every session has -- the buffers, the launch chain of a token step and the
+capture of its graph; DecodeSession (shared counters) and StreamSession (per-row counters) add their state, their attention
+and their end-of-step launch.  T2SInfer has ONE prompt pass (_prompt_pass: _decode runs it for all rows of a call, _admit
+for the slots of an admission) and ONE session cache (_held, behind session / stream_session).  A request of a stream is
+parsed once, by _RequestParser, into a Request record that _fits, _stream and _admit read by field name."""
 import collections
 import ctypes as C
 import math
@@ -65,14 +71,20 @@ class _Weights:
         return tuple(p._version for p in model.parameters()) + tuple(p.data_ptr() for p in model.parameters())
 
 
-class DecodeSession:
-    """static buffers + the captured step graph for one (batch, cache capacity, dtype)"""
+class _Session:
+    """what DecodeSession and StreamSession share: the static buffers of B rows, the launch chain of one token step and
+    the captured step graph.  A subclass adds its counters, names the library's linear-layer entry point (gemv_fn) and
+    supplies _attn(i) and _end_step(W, sp, noise, pe).  The chain looks _gemv, _attn and _end_step up on the session at
+    call time, so a function assigned onto a subclass (the CPU emulations of the tests) takes effect."""
+
+    gemv_fn = "evt_dec_gemm_rows"
+    fusable = False        # whether step_launches(fused_qkv=True) may put the in-projection into the attention launch
 
     def __init__(self, model, B, Lmax, ymax, dtype, device):
         self.model, self.B, self.Lmax, self.ymax, self.dtype, self.device = model, B, Lmax, ymax, dtype, device
         E, nl, V = model.model_dim, model.num_layers, model.vocab_size
         self.E, self.H, self.nl, self.V = E, model.num_head, nl, V
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
+        z = self._zeros
         self.kc = z(nl, B, Lmax, E, dt=dtype)
         self.vc = z(nl, B, Lmax, E, dt=dtype)
         self.xa, self.xb = z(B, E), z(B, E)
@@ -80,21 +92,75 @@ class DecodeSession:
         self.hid = z(B, 4 * E)
         self.logits = z(B, V)
         self.y = z(B, ymax, dt=torch.int64)
-        self.ctr = z(8, dt=torch.int32)
-        self.stop = torch.full((B,), -1, dtype=torch.int32, device=device)
-        self.x_lens, self.x_len = None, 0      # key-padding of a batch of texts (infer_panel_batch_infer); None = no padding
-        self.x_lens_buf = z(B, dt=torch.int32)
-        self.wide = B > T2SInfer.MAX_ROWS       # 5..32 rows: evt_dec_gemm_rows / evt_dec_sample_rows
-        self.row_seed = z(B, 2, dt=torch.int32)  # (seed, lane) per row of a wide session, written by T2SInfer._decode
+        self.row_seed = z(B, 2, dt=torch.int32)  # (seed, lane) of each row's built-in noise
         self.graph, self.graph_key = None, None
 
-    # ---- launches ----
+    def _zeros(self, *s, dt=torch.float32):
+        return torch.zeros(*s, dtype=dt, device=self.device)
+
     def _gemv(self, w, bias, a, r, g, b, eps, x_out, y, relu=0):
         N, K = w.shape
-        fn = "evt_dec_gemm_rows" if self.wide else "evt_dec_gemv"
+        fn = self.gemv_fn
         L.check(getattr(L.lib(), fn)(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
                                      C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu), L.stream_ptr()), fn)
 
+    def step_launches(self, W, sp, noise, pe, fused_qkv=False):
+        """one token: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + the end of the step (sampling
+        / embedding / counters: one launch, three in a DecodeSession of several rows) = 122 or 124 launches.  fused_qkv
+        puts the in-projection into the attention launch of a session that can (98 launches): 16 workgroups then stream
+        all of W_qkv, which is slower on the device (measured 696 vs 614 us per token under graph replay) but faster
+        when the HOST is the bottleneck (eager launches: 959 vs 1210 us).  In a StreamSession idle and stopped rows
+        ride along in the linear layers on stale inputs; the attention and the sampler skip them."""
+        prev = None
+        for i, w in enumerate(W.layers):
+            ln = (None, None, None, 0.0, None) if prev is None else (self.u, prev["g2"], prev["be2"], prev["eps2"], self.xa)
+            src = self.xa if prev is None else self.xb   # later blocks: LayerNorm2 of the previous one, stored to xa
+            if fused_qkv and self.fusable:
+                self._qkv_attn(i, w, src, *ln)
+            else:
+                self._gemv(w["wqkv"], w["bqkv"], src, *ln, self.qkv)
+                self._attn(i)
+            self._gemv(w["wo"], w["bo"], self.att, None, None, None, 0.0, None, self.t)
+            self._gemv(w["w1"], w["b1"], self.xa, self.t, w["g1"], w["be1"], w["eps1"], self.xb, self.hid, relu=1)
+            self._gemv(w["w2"], w["b2"], self.hid, None, None, None, 0.0, None, self.u)
+            prev = w
+        self._gemv(W.wpred, None, self.xb, self.u, prev["g2"], prev["be2"], prev["eps2"], None, self.logits)
+        self._end_step(W, sp, noise, pe)
+
+    def capture(self, gkey, W, sp, noise, pe, restore=()):
+        """the step graph under the key gkey: warm-up launches outside the capture on a side stream, then the capture.
+        Both move whatever counters are live, so the tensors of `restore` are put back afterwards (a stream session
+        captures with every slot idle and has nothing to restore)."""
+        dev = self.device
+        keep = [t.clone() for t in restore]
+        side = L.role_stream(dev, "decode_warm", ring=1)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self.step_launches(W, sp, noise, pe)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="relaxed"):
+            self.step_launches(W, sp, noise, pe)
+        for t, k in zip(restore, keep):
+            t.copy_(k)
+        self.graph, self.graph_key, self._keep = g, gkey, (sp, noise, pe, W)
+
+
+class DecodeSession(_Session):
+    """a session of rows that share one set of counters ctr (csrc/s1_decode.hip), one per (batch, cache capacity, dtype)"""
+
+    def __init__(self, model, B, Lmax, ymax, dtype, device):
+        super().__init__(model, B, Lmax, ymax, dtype, device)
+        self.ctr = self._zeros(8, dt=torch.int32)
+        self.stop = torch.full((B,), -1, dtype=torch.int32, device=device)
+        self.x_lens, self.x_len = None, 0      # key-padding of a batch of texts (infer_panel_batch_infer); None = no padding
+        self.x_lens_buf = self._zeros(B, dt=torch.int32)
+        # 5..32 rows: evt_dec_gemm_rows / evt_dec_sample_rows with the row_seed table that T2SInfer._decode writes, and
+        # never fused: every (row, head) workgroup would stream its head's rows of W_qkv again
+        self.wide = B > T2SInfer.MAX_ROWS
+        self.gemv_fn, self.fusable = ("evt_dec_gemm_rows", False) if self.wide else ("evt_dec_gemv", True)
+
+    # ---- launches ----
     def _sample_embed_advance(self, W, sp, noise, pe, dpos):
         """sampling, append, embedding of the new token and the counter update: one launch for one sequence, three for a
         batch (the counters may only move after every row's workgroup has read them)"""
@@ -117,36 +183,19 @@ class DecodeSession:
                                   self.B, self.E, self.ymax, pe.size(0), L.stream_ptr()), "evt_dec_embed")
         L.check(lib.evt_dec_advance(L.ptr(self.ctr), dpos, L.stream_ptr()), "evt_dec_advance")
 
+    def _end_step(self, W, sp, noise, pe):
+        self._sample_embed_advance(W, sp, noise, pe, 1)
+
+    def _attn(self, i):
+        L.check(L.lib().evt_dec_attn(L.dt_of(self.kc), L.ptr(self.qkv), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
+                                     L.ptr(self.ctr), L.ptr(self.att), self.B, self.H, self.E // self.H, self.Lmax,
+                                     L.ptr(self.x_lens), self.x_len, L.stream_ptr()), "evt_dec_attn")
+
     def _qkv_attn(self, i, w, a, r, g, b, eps, x_out):
         L.check(L.lib().evt_dec_qkv_attn(L.dt_of(self.kc), L.ptr(w["wqkv"]), L.ptr(w["bqkv"]), L.ptr(a), L.ptr(r), L.ptr(g),
                                          L.ptr(b), C.c_float(eps), L.ptr(x_out), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
                                          L.ptr(self.ctr), L.ptr(self.att), self.B, self.H, self.E // self.H, self.Lmax,
                                          L.ptr(self.x_lens), self.x_len, L.stream_ptr()), "evt_dec_qkv_attn")
-
-    def step_launches(self, W, sp, noise, pe, fused_qkv=False):
-        """one token: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + one launch for sampling /
-        embedding / counters = 122 launches.  fused_qkv puts the in-projection into the attention launch (98 launches):
-        16 workgroups then stream all of W_qkv, which is slower on the device (measured 696 vs 614 us per token under
-        graph replay) but faster when the HOST is the bottleneck (eager launches: 959 vs 1210 us).  A wide session never
-        fuses: every (row, head) workgroup would stream its head's rows of W_qkv again."""
-        fused_qkv = fused_qkv and not self.wide
-        prev = None
-        for i, w in enumerate(W.layers):
-            ln = (None, None, None, 0.0, None) if prev is None else (self.u, prev["g2"], prev["be2"], prev["eps2"], self.xa)
-            src = self.xa if prev is None else self.xb   # later blocks: LayerNorm2 of the previous one, stored to xa
-            if fused_qkv:
-                self._qkv_attn(i, w, src, *ln)
-            else:
-                self._gemv(w["wqkv"], w["bqkv"], src, *ln, self.qkv)
-                L.check(L.lib().evt_dec_attn(L.dt_of(self.kc), L.ptr(self.qkv), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
-                                             L.ptr(self.ctr), L.ptr(self.att), self.B, self.H, self.E // self.H, self.Lmax,
-                                             L.ptr(self.x_lens), self.x_len, L.stream_ptr()), "evt_dec_attn")
-            self._gemv(w["wo"], w["bo"], self.att, None, None, None, 0.0, None, self.t)
-            self._gemv(w["w1"], w["b1"], self.xa, self.t, w["g1"], w["be1"], w["eps1"], self.xb, self.hid, relu=1)
-            self._gemv(w["w2"], w["b2"], self.hid, None, None, None, 0.0, None, self.u)
-            prev = w
-        self._gemv(W.wpred, None, self.xb, self.u, prev["g2"], prev["be2"], prev["eps2"], None, self.logits)
-        self._sample_embed_advance(W, sp, noise, pe, 1)
 
 
 ROW_WORDS = 8             # include/evt.h EVT_ROW_*
@@ -178,7 +227,7 @@ class StreamControl:
         self.preempted.add(int(r))
 
 
-class StreamSession:
+class StreamSession(_Session):
     """static buffers + the captured step graph of a continuously batched session: B slots, each with its own counters
     rstate[b] (csrc/s1_decode_stream.hip).  Cache slab of a slot: [0, Xmax) the text, padded and masked by x_lens[b];
     [Xmax, Xmax + ylen[b] + steps) the audio.  All per-row state is device memory, so admitting a text into a free slot
@@ -186,41 +235,24 @@ class StreamSession:
     so the graph is captured once per (vocabulary-level parameters, noise table) and serves every parameter set."""
 
     def __init__(self, model, B, Xmax, Lmax, ymax, dtype, device):
-        self.model, self.B, self.Xmax, self.Lmax, self.ymax = model, B, Xmax, Lmax, ymax
-        self.dtype, self.device = dtype, device
-        E, nl, V = model.model_dim, model.num_layers, model.vocab_size
-        self.E, self.H, self.nl, self.V = E, model.num_head, nl, V
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
-        self.kc = z(nl, B, Lmax, E, dt=dtype)
-        self.vc = z(nl, B, Lmax, E, dt=dtype)
-        self.xa, self.xb = z(B, E), z(B, E)
-        self.qkv, self.att, self.t, self.u = z(B, 3 * E), z(B, E), z(B, E), z(B, E)
-        self.hid = z(B, 4 * E)
-        self.logits = z(B, V)
-        self.y = z(B, ymax, dt=torch.int64)
+        super().__init__(model, B, Lmax, ymax, dtype, device)
+        self.Xmax = Xmax
+        z = self._zeros
         self.state = z(B * (ROW_WORDS + 1), dt=torch.int32)      # rstate [B][8], then stop [B]: one read per poll
         self.rstate = self.state[:B * ROW_WORDS].view(B, ROW_WORDS)
         self.stop = self.state[B * ROW_WORDS:]
         self.x_lens = z(B, dt=torch.int32)
-        self.row_seed = z(B, 2, dt=torch.int32)
         self.row_sample = z(B, 4, dt=torch.int32)                 # evt_row_sample [B]: top_k, then the bits of 3 floats
         self.mask = z(B, dt=torch.int32)                          # rows of an admission's step 0
         self.logp, self.lp_on = None, False                       # [B][ymax][2] of a logprobs=True stream, made on demand
         self.force_on = False                                     # a stream with forced requests: the _f sampler launch
         self.noise_cands = 1                                      # C of an injected [steps][R][C][V] noise table
-        self.graph, self.graph_key = None, None
 
     def reset(self):
         self.state.zero_()                 # every slot idle
         self.stop.fill_(-1)
 
     # ---- launches ----
-    def _gemv(self, w, bias, a, r, g, b, eps, x_out, y, relu=0):
-        N, K = w.shape
-        L.check(L.lib().evt_dec_gemm_rows(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
-                                          C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu),
-                                          L.stream_ptr()), "evt_dec_gemm_rows")
-
     def _attn(self, i):
         L.check(L.lib().evt_dec_attn_rows(L.dt_of(self.kc), L.ptr(self.qkv), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
                                           L.ptr(self.rstate), L.ptr(self.att), self.B, self.H, self.E // self.H,
@@ -232,46 +264,137 @@ class StreamSession:
         temperature and repetition_penalty of a row come from row_sample[b]; `sp` carries the session-wide rest.  A
         stream with logprobs=True launches the variant that also fills logp[b][YCOUNT]; a stream with forced requests
         launches the one that takes the token of a row's forced steps from y (with or without logp)"""
-        if self.force_on:
-            L.check(L.lib().evt_dec_sample_embed_rows_f(
-                C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
-                L.ptr(self.stop), None,
-                L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
-                C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa),
-                L.ptr(self.logp) if self.lp_on else None, self.B, self.E, pe.size(0), dpos, L.stream_ptr()),
-                "evt_dec_sample_embed_rows_f")
-            return
-        if self.lp_on:
-            L.check(L.lib().evt_dec_sample_embed_rows_lp(
-                C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
-                L.ptr(self.stop), None,
-                L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
-                C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), L.ptr(self.logp), self.B, self.E,
-                pe.size(0), dpos, L.stream_ptr()), "evt_dec_sample_embed_rows_lp")
-            return
-        L.check(L.lib().evt_dec_sample_embed_rows_p(
+        fn = "evt_dec_sample_embed_rows_" + ("f" if self.force_on else "lp" if self.lp_on else "p")
+        logp = () if fn.endswith("_p") else (L.ptr(self.logp) if self.lp_on else None,)
+        L.check(getattr(L.lib(), fn)(
             C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
-            L.ptr(self.stop), None,
-            L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
-            C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), self.B, self.E, pe.size(0), dpos,
-            L.stream_ptr()), "evt_dec_sample_embed_rows_p")
+            L.ptr(self.stop), None, L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
+            C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), *logp, self.B, self.E, pe.size(0), dpos,
+            L.stream_ptr()), fn)
 
-    def step_launches(self, W, sp, noise, pe):
-        """one token for every running row: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + one
-        launch for sampling / embedding / counters = 122 launches (a wide DecodeSession: 124).  Idle and stopped rows
-        ride along in the linear layers on stale inputs; the attention and the sampler skip them."""
-        prev = None
-        for i, w in enumerate(W.layers):
-            ln = (None, None, None, 0.0, None) if prev is None else (self.u, prev["g2"], prev["be2"], prev["eps2"], self.xa)
-            src = self.xa if prev is None else self.xb
-            self._gemv(w["wqkv"], w["bqkv"], src, *ln, self.qkv)
-            self._attn(i)
-            self._gemv(w["wo"], w["bo"], self.att, None, None, None, 0.0, None, self.t)
-            self._gemv(w["w1"], w["b1"], self.xa, self.t, w["g1"], w["be1"], w["eps1"], self.xb, self.hid, relu=1)
-            self._gemv(w["w2"], w["b2"], self.hid, None, None, None, 0.0, None, self.u)
-            prev = w
-        self._gemv(W.wpred, None, self.xb, self.u, prev["g2"], prev["be2"], prev["eps2"], None, self.logits)
+    def _end_step(self, W, sp, noise, pe):
         self._sample_embed(W, sp, noise, pe, 1)
+
+
+# one request of a decode_stream as _RequestParser hands it to _fits, _stream and _admit: r its index in the stream,
+# limit its number of steps at most, sampling the four values of _sampling, n its candidates, force None or the tokens
+# of its forced steps (int64, CPU), seed None or its own (seed, lane)
+Request = collections.namedtuple("Request", "r x bert prompt limit sampling n force seed")
+# a running slot, and a slot that a poll found finished, cancelled or preempted (kind: "finish", "cancel", "preempt", the
+# name of its event)
+_Row = collections.namedtuple("_Row", "request ylen candidate")
+_Done = collections.namedtuple("_Done", "slot request y idx candidate logprobs kind")
+
+
+class _RequestParser:
+    """(r, request of decode_stream) -> Request, or an EvtError that names the request.  Built from the values of the
+    whole stream: `base` the session-wide sampling values by SAMPLE_KEYS, n, slots, early_stop_num, the injected noise
+    table or None, and whether the stream is lazy, was opened with forced=True, records log-probabilities."""
+
+    def __init__(self, model, base, n, slots, early_stop_num, noise, lazy, forced, logprobs):
+        self.slots, self.early_stop_num, self.lazy, self.forced, self.logprobs = slots, early_stop_num, lazy, forced, logprobs
+        self.V, self.eos = model.vocab_size, model.EOS
+        self.has_noise = noise is not None
+        self.nsteps = None if noise is None else int(noise.size(0))
+        self.ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
+        self.ncand = int(noise.size(2)) if noise is not None and noise.dim() == 4 else None
+        self.base_n = self.candidates(n, "decode_stream")
+        self.base = base
+        self.base_v = T2SInfer._sampling(*base.values(), "decode_stream")
+        # the step capacity of a lazy stream is known before its first request is drawn; a list's comes from its requests
+        self.cap_steps = self.limit(None) if lazy else None
+
+    def limit(self, early_stop_num):
+        lim = T2SInfer._limit(self.early_stop_num if early_stop_num is None else early_stop_num)
+        return lim if self.nsteps is None else min(lim, self.nsteps)      # an injected noise table also bounds the steps
+
+    def candidates(self, v, who):
+        try:
+            if isinstance(v, bool):
+                raise TypeError("a bool")
+            v = operator.index(v)
+        except TypeError:
+            raise L.EvtError(f"{who}: n = {v!r} is not an integer") from None
+        if not 1 <= v <= self.slots:
+            raise L.EvtError(f"{who}: n = {v} must be 1..slots = {self.slots}")
+        return v
+
+    def force_of(self, v, who, lim):
+        V, eos = self.V, self.eos
+        try:
+            t = torch.as_tensor(v).detach().cpu()
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise L.EvtError(f"{who}: force is no token vector ({e})") from None
+        if t.dim() != 1 or t.numel() < 1 or t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
+            raise L.EvtError(f"{who}: force must be a 1-D integer vector of at least one token")
+        t = t.long()
+        f = t.numel()
+        bad = ((t < 0) | (t >= V)).nonzero()
+        if bad.numel():
+            j = int(bad[0])
+            raise L.EvtError(f"{who}: force[{j}] = {int(t[j])} is outside [0, {V})")
+        at = (t == eos).nonzero().reshape(-1).tolist()
+        if at and at[0] == 0:
+            raise L.EvtError(f"{who}: force[0] is EOS ({eos}), but step 0 has no EOS column")
+        if at and at[0] != f - 1:
+            raise L.EvtError(f"{who}: force[{at[0]}] is EOS ({eos}) before the last position {f - 1}")
+        if f > lim:
+            raise L.EvtError(f"{who}: {f} forced tokens, but the request's step limit is {lim}")
+        if self.cap_steps is not None and f > self.cap_steps:
+            raise L.EvtError(f"{who}: {f} forced tokens, but the session's capacity is {self.cap_steps} steps")
+        return t
+
+    @staticmethod
+    def seed_of(v, who):
+        pair = v if isinstance(v, (tuple, list)) else (v, 0)
+        try:
+            if len(pair) != 2 or any(isinstance(e, bool) for e in pair):
+                raise TypeError("expected an int or a pair (seed, lane) of ints")
+            sd, lane = operator.index(pair[0]), operator.index(pair[1])
+        except TypeError as e:
+            raise L.EvtError(f"{who}: seed = {v!r} is not an integer or (integer, lane) ({e})") from None
+        if not 0 <= lane < T2SInfer.MAX_ROWS:
+            raise L.EvtError(f"{who}: seed lane = {lane} must be 0..{T2SInfer.MAX_ROWS - 1}")
+        return sd & 0x7FFFFFFF, lane
+
+    def __call__(self, r, req):
+        if len(req) not in (3, 4):
+            raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num or dict])")
+        x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
+        opt, samp, nr = req[3] if len(req) == 4 else None, self.base_v, self.base_n
+        force = own_seed = None
+        if isinstance(opt, dict):
+            unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num", "n", "force", "seed"})
+            if unknown:
+                raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)}, "
+                                 "early_stop_num, n, force and seed)")
+            if "n" in opt:
+                nr = self.candidates(opt["n"], f"request {r}")
+            force = opt.get("force")
+            if opt.get("seed") is not None:
+                own_seed = self.seed_of(opt["seed"], f"request {r}")
+            samp = T2SInfer._sampling(*({**self.base, **{k: v for k, v in opt.items() if k in SAMPLE_KEYS}}[k]
+                                        for k in SAMPLE_KEYS), f"request {r}")
+            opt = opt.get("early_stop_num")
+        lim = self.limit(opt)
+        if x.numel() < 1 or prompt.numel() < 1:
+            raise L.EvtError(f"request {r}: empty text or prompt")
+        if self.ncols is not None and r >= self.ncols:
+            raise L.EvtError(f"request {r}: the noise table has {self.ncols} columns")
+        if nr > 1 and self.has_noise and self.ncand is None:
+            raise L.EvtError(f"request {r}: n = {nr}, but the noise table has no candidate dimension "
+                             "([steps][R][C][V])")
+        if self.ncand is not None and nr > self.ncand:
+            raise L.EvtError(f"request {r}: n = {nr}, but the noise table has {self.ncand} candidates per request")
+        if self.lazy and nr > 1 and not (self.logprobs or self.base_n > 1):
+            raise L.EvtError(f"request {r}: n = {nr} in a lazy stream needs logprobs=True or a session-wide n > 1 "
+                             "(the form of the outputs is fixed when the stream is opened)")
+        if force is not None:
+            if self.lazy and not self.forced:
+                raise L.EvtError(f"request {r}: \"force\" in a lazy stream needs decode_stream(..., forced=True) "
+                                 "(the sampler launch is fixed when the stream is opened)")
+            force = self.force_of(force, f"request {r}", lim)
+        return Request(r, x, bert, prompt, lim, samp, nr, force, own_seed)
 
 
 class T2SInfer:
@@ -319,21 +442,31 @@ class T2SInfer:
 
         return run
 
-    def session(self, B, Lneed, yneed, dtype, device):
-        """sessions of <= MAX_ROWS rows are kept per shape; of the wide ones (up to 3.2 GB of bf16 cache at B = 32,
-        Lmax = 2048) only the WIDE_SESSIONS most recently used, a dropped one taking its captured graph with it"""
+    def _held(self, make, B, Lneed, yneed, dtype, device, *tag, lru=True, admit=None):
+        """the session cache: capacities rounded up to 512; a session under `lru` is one of the WIDE_SESSIONS most
+        recently used ones, a dropped one taking its cache and its captured graph with it.  admit(Lmax) may refuse a
+        session that has to be made -- after the least recently used one has made room, before anything is allocated or
+        recorded"""
         Lmax, ymax = -(-Lneed // 512) * 512, -(-yneed // 512) * 512
-        key = (B, Lmax, ymax, dtype, str(device))
-        if B > self.MAX_ROWS:
+        key = (B, Lmax, ymax, dtype, str(device), *tag)
+        if lru:
             if key in self._wide:
                 self._wide.remove(key)
             else:
                 while len(self._wide) >= self.WIDE_SESSIONS:
                     del self._sessions[self._wide.pop(0)]
+            if admit is not None and key not in self._sessions:
+                admit(Lmax)
             self._wide.append(key)
         if key not in self._sessions:
-            self._sessions[key] = DecodeSession(self.model, B, Lmax, ymax, dtype, device)
+            self._sessions[key] = make(Lmax, ymax)
         return self._sessions[key]
+
+    def session(self, B, Lneed, yneed, dtype, device):
+        """sessions of <= MAX_ROWS rows are kept per shape; of the wide ones (up to 3.2 GB of bf16 cache at B = 32,
+        Lmax = 2048) only the WIDE_SESSIONS most recently used"""
+        return self._held(lambda Lmax, ymax: DecodeSession(self.model, B, Lmax, ymax, dtype, device),
+                          B, Lneed, yneed, dtype, device, lru=B > self.MAX_ROWS)
 
     def stream_session(self, B, Xmax, Lneed, yneed, dtype, device):
         """the session cache of session(): capacities rounded to 512, stream sessions share the wide-session LRU.  A
@@ -342,14 +475,9 @@ class T2SInfer:
         of the free device memory: before anything is allocated, and with the figures in the message.  Free memory is
         what the device reports plus what torch's allocator holds unused, counted after the least recently used session
         has made room (a refused session therefore still costs that one; it is made again when asked for)"""
-        Lmax, ymax = -(-Lneed // 512) * 512, -(-yneed // 512) * 512
-        key = (B, Lmax, ymax, dtype, str(device), "stream", Xmax)
-        if key in self._wide:
-            self._wide.remove(key)
-        else:
-            while len(self._wide) >= self.WIDE_SESSIONS:
-                del self._sessions[self._wide.pop(0)]
-        if B > self.WIDE_ROWS and key not in self._sessions and torch.device(device).type == "cuda":
+        def admit(Lmax):
+            if B <= self.WIDE_ROWS or torch.device(device).type != "cuda":
+                return
             m = self.model
             need = 2 * m.num_layers * B * Lmax * m.model_dim * torch.empty((), dtype=dtype).element_size()
             free = (torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device)
@@ -357,15 +485,49 @@ class T2SInfer:
             if 2 * need > free:
                 raise L.EvtError(f"a stream session of {B} slots and {Lmax} cache positions needs {need} bytes of "
                                  f"key/value cache, more than half of the {free} bytes free on {device}")
-        self._wide.append(key)
-        if key not in self._sessions:
-            self._sessions[key] = StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device)
-        return self._sessions[key]
+
+        return self._held(lambda Lmax, ymax: StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device),
+                          B, Lneed, yneed, dtype, device, "stream", Xmax, admit=admit)
 
     MAX_ROWS = 4        # rows of a session on the kernels of csrc/s1_decode.hip (kMaxB); also the seed group of a row
     WIDE_ROWS = 32      # rows of a wide session (csrc/s1_decode_rows.hip); larger batches run in groups of 32
     WIDE_SESSIONS = 2   # wide sessions kept at once
     STREAM_ROWS = 128   # slots of a stream session opened with wide=True: four row groups of evt_dec_gemm_rows
+
+    def _prompt_pass(self, S, W, xs, berts, prompts, y_lens, x_len, rows, spread=lambda t: t):
+        """the prompt pass (t2s_model.py:575-660 / 775-825, T2SBlock.process_prompt) of k texts: xs k id vectors, berts
+        k x [1024, n], prompts [k, P] (padded to a common length, y_lens the true ones) or None; every text is padded to
+        x_len positions, masked as keys.  The keys/values of the k rows go into rows `rows` of S's cache, through
+        `spread` when one prompt row serves several cache rows.  Returns the activations after the last block
+        [k, x_len + P, E] and the two length vectors on the device."""
+        m = self.model
+        dev, cd = S.device, S.dtype
+        dense = self.dense(cd, dev)           # the library's GEMMs on prepared weight images (hip/linear.py), no vendor BLAS
+        embs = []
+        for x, bert in zip(xs, berts):
+            x, bert = x.to(dev), bert.to(dev)
+            xe = m.ar_text_embedding(x.unsqueeze(0))
+            xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
+            xe = m.ar_text_position(xe).squeeze(0)
+            embs.append(F.pad(xe, (0, 0, 0, x_len - xe.size(0))))
+        xy = torch.stack(embs, dim=0)
+        if prompts is not None:
+            xy = torch.cat([xy, m.ar_audio_position(m.ar_audio_embedding(prompts))], dim=1)
+        xy = xy.to(cd).contiguous()
+        src_len = xy.size(1)
+        xl = torch.tensor([int(x.numel()) for x in xs], dtype=torch.int32, device=dev)
+        yl = torch.tensor(y_lens, dtype=torch.int32, device=dev)
+        for i, lyr in enumerate(m.h.layers):
+            w = W.layers[i]
+            qkv = dense(xy, lyr.self_attn.in_proj_weight)
+            S.kc[i, rows, :src_len] = spread(qkv[..., S.E:2 * S.E])
+            S.vc[i, rows, :src_len] = spread(qkv[..., 2 * S.E:])
+            o = PrefixLMAttentionFn.apply(qkv, xl, yl, x_len, S.H, 0.0, 0)
+            sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
+            xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
+            ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
+            xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
+        return xy, xl, yl
 
     @torch.no_grad()
     def _decode(self, xs, berts, prompts, no_eos_steps, top_k, top_p, early_stop_num, temperature, repetition_penalty,
@@ -379,25 +541,11 @@ class T2SInfer:
         L.set_half(cd)                        # a 16-bit streaming dtype selects the build of the library that serves it
         B = len(xs)
         W = self.weights(cd)
-        # ---- prompt pass (t2s_model.py:575-660 / 775-825, T2SBlock.process_prompt) ----
         x_lens = [int(x.numel()) for x in xs]
         x_len = max(x_lens)
-        rows = []
-        dense = self.dense(cd, dev)           # the library's GEMMs on prepared weight images (hip/linear.py), no vendor BLAS
-        for x, bert in zip(xs, berts):
-            xe = m.ar_text_embedding(x.unsqueeze(0))
-            xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
-            xe = m.ar_text_position(xe).squeeze(0)
-            rows.append(F.pad(xe, (0, 0, 0, x_len - xe.size(0))))      # padded text positions: masked as keys below
-        xe = torch.stack(rows, dim=0)
-        if prompts is None:
-            y_len, xy = 0, xe
-        else:
-            y_len = prompts.size(1)
-            xy = torch.cat([xe, m.ar_audio_position(m.ar_audio_embedding(prompts))], dim=1)
-        xy = xy.to(cd).contiguous()
+        y_len = 0 if prompts is None else prompts.size(1)
         src_len = x_len + y_len
-        n_max = MAX_STEPS if early_stop_num == -1 else max(1, min(MAX_STEPS, int(early_stop_num) + 1))
+        n_max = self._limit(early_stop_num)
         noise_rows = 1
         if noise is not None:       # an injected noise table (parity runs) also bounds the number of steps
             noise = noise.to(dev, torch.float32).contiguous()
@@ -405,18 +553,7 @@ class T2SInfer:
             assert noise.size(-1) == m.vocab_size and noise_rows in (1, B)
             n_max = min(n_max, noise.size(0))
         S = self.session(B, src_len + n_max + 1, y_len + n_max + 1, cd, dev)
-        xl = torch.tensor(x_lens, dtype=torch.int32, device=dev)
-        yl = torch.full((B,), y_len, dtype=torch.int32, device=dev)
-        for i, lyr in enumerate(m.h.layers):
-            w = W.layers[i]
-            qkv = dense(xy, lyr.self_attn.in_proj_weight)
-            S.kc[i, :, :src_len].copy_(qkv[..., S.E:2 * S.E])
-            S.vc[i, :, :src_len].copy_(qkv[..., 2 * S.E:])
-            o = PrefixLMAttentionFn.apply(qkv, xl, yl, x_len, S.H, 0.0, 0)
-            sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
-            xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
-            ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
-            xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
+        xy, xl, _yl = self._prompt_pass(S, W, xs, berts, prompts, [y_len] * B, x_len, slice(None))
         # ---- state ----
         S.y.zero_()
         if prompts is not None:
@@ -448,18 +585,7 @@ class T2SInfer:
         use_graph = os.environ.get("EVT_DECODE_GRAPH", "1") != "0" and hip_graphs_safe()
         gkey = (bytes(sp), None if noise is None else noise.data_ptr(), pe.data_ptr(), id(W), padded, x_len)
         if use_graph and S.graph_key != gkey:
-            # warm-up launches outside the capture, on throw-away counters: restore the state afterwards
-            keep = (S.ctr.clone(), S.y.clone(), S.stop.clone(), S.xa.clone())
-            side = L.role_stream(dev, "decode_warm", ring=1)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                S.step_launches(W, sp, noise, pe)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="relaxed"):
-                S.step_launches(W, sp, noise, pe)
-            S.ctr.copy_(keep[0]); S.y.copy_(keep[1]); S.stop.copy_(keep[2]); S.xa.copy_(keep[3])
-            S.graph, S.graph_key, S._keep = g, gkey, (sp, noise, pe, W)
+            S.capture(gkey, W, sp, noise, pe, restore=(S.ctr, S.y, S.stop, S.xa))
         done = 1
         stop = S.stop.tolist() if n_max == 1 else [-1] * B
         while done < n_max and min(stop) < 0:
@@ -607,118 +733,20 @@ class T2SInfer:
         most = self.STREAM_ROWS if wide else self.WIDE_ROWS
         if not 1 <= int(slots) <= most:
             raise L.EvtError(f"slots must be 1..{most}, got {slots}")
-        slots, logprobs = int(slots), bool(logprobs)
-        nsteps = None if noise is None else int(noise.size(0))
-        ncols = None if noise is None or noise.dim() == 2 else int(noise.size(1))
-        ncand = int(noise.size(2)) if noise is not None and noise.dim() == 4 else None
-
-        def candidates(v, who):
-            try:
-                if isinstance(v, bool):
-                    raise TypeError("a bool")
-                v = operator.index(v)
-            except TypeError:
-                raise L.EvtError(f"{who}: n = {v!r} is not an integer") from None
-            if not 1 <= v <= slots:
-                raise L.EvtError(f"{who}: n = {v} must be 1..slots = {slots}")
-            return v
-
-        base_n = candidates(n, "decode_stream")
+        slots, logprobs, forced = int(slots), bool(logprobs), bool(forced)
         lazy = not isinstance(requests, (list, tuple))
-
-        base = dict(zip(SAMPLE_KEYS, (top_k, top_p, temperature, repetition_penalty)))
-        base_v = self._sampling(top_k, top_p, temperature, repetition_penalty, "decode_stream")
-        forced, V, eos = bool(forced), self.model.vocab_size, self.model.EOS
-        cap_steps = []          # the step capacity of a lazy stream, known before its first request is drawn
-
-        def force_of(v, who, lim):
-            try:
-                t = torch.as_tensor(v).detach().cpu()
-            except (TypeError, ValueError, RuntimeError) as e:
-                raise L.EvtError(f"{who}: force is no token vector ({e})") from None
-            if t.dim() != 1 or t.numel() < 1 or t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
-                raise L.EvtError(f"{who}: force must be a 1-D integer vector of at least one token")
-            t = t.long()
-            f = t.numel()
-            bad = ((t < 0) | (t >= V)).nonzero()
-            if bad.numel():
-                j = int(bad[0])
-                raise L.EvtError(f"{who}: force[{j}] = {int(t[j])} is outside [0, {V})")
-            at = (t == eos).nonzero().reshape(-1).tolist()
-            if at and at[0] == 0:
-                raise L.EvtError(f"{who}: force[0] is EOS ({eos}), but step 0 has no EOS column")
-            if at and at[0] != f - 1:
-                raise L.EvtError(f"{who}: force[{at[0]}] is EOS ({eos}) before the last position {f - 1}")
-            if f > lim:
-                raise L.EvtError(f"{who}: {f} forced tokens, but the request's step limit is {lim}")
-            if cap_steps and f > cap_steps[0]:
-                raise L.EvtError(f"{who}: {f} forced tokens, but the session's capacity is {cap_steps[0]} steps")
-            return t
-
-        def seed_of(v, who):
-            pair = v if isinstance(v, (tuple, list)) else (v, 0)
-            try:
-                if len(pair) != 2 or any(isinstance(e, bool) for e in pair):
-                    raise TypeError("expected an int or a pair (seed, lane) of ints")
-                sd, lane = operator.index(pair[0]), operator.index(pair[1])
-            except TypeError as e:
-                raise L.EvtError(f"{who}: seed = {v!r} is not an integer or (integer, lane) ({e})") from None
-            if not 0 <= lane < self.MAX_ROWS:
-                raise L.EvtError(f"{who}: seed lane = {lane} must be 0..{self.MAX_ROWS - 1}")
-            return sd & 0x7FFFFFFF, lane
-
-        def norm(r, req):
-            if len(req) not in (3, 4):
-                raise L.EvtError(f"request {r}: expected (x, bert, prompt[, early_stop_num or dict])")
-            x, bert, prompt = req[0].reshape(-1), req[1], req[2].reshape(-1)
-            opt, samp, nr = req[3] if len(req) == 4 else None, base_v, base_n
-            force = own_seed = None
-            if isinstance(opt, dict):
-                unknown = sorted(set(opt) - set(SAMPLE_KEYS) - {"early_stop_num", "n", "force", "seed"})
-                if unknown:
-                    raise L.EvtError(f"request {r}: unknown key(s) {unknown} (known: {list(SAMPLE_KEYS)}, "
-                                     "early_stop_num, n, force and seed)")
-                if "n" in opt:
-                    nr = candidates(opt["n"], f"request {r}")
-                force = opt.get("force")
-                if opt.get("seed") is not None:
-                    own_seed = seed_of(opt["seed"], f"request {r}")
-                samp = self._sampling(*({**base, **{k: v for k, v in opt.items() if k in SAMPLE_KEYS}}[k]
-                                        for k in SAMPLE_KEYS), f"request {r}")
-                opt = opt.get("early_stop_num")
-            lim = self._limit(early_stop_num if opt is None else opt)
-            if nsteps is not None:
-                lim = min(lim, nsteps)      # an injected noise table also bounds the number of steps
-            if x.numel() < 1 or prompt.numel() < 1:
-                raise L.EvtError(f"request {r}: empty text or prompt")
-            if ncols is not None and r >= ncols:
-                raise L.EvtError(f"request {r}: the noise table has {ncols} columns")
-            if nr > 1 and noise is not None and ncand is None:
-                raise L.EvtError(f"request {r}: n = {nr}, but the noise table has no candidate dimension "
-                                 "([steps][R][C][V])")
-            if ncand is not None and nr > ncand:
-                raise L.EvtError(f"request {r}: n = {nr}, but the noise table has {ncand} candidates per request")
-            if lazy and nr > 1 and not (logprobs or base_n > 1):
-                raise L.EvtError(f"request {r}: n = {nr} in a lazy stream needs logprobs=True or a session-wide n > 1 "
-                                 "(the form of the outputs is fixed when the stream is opened)")
-            if force is not None:
-                if lazy and not forced:
-                    raise L.EvtError(f"request {r}: \"force\" in a lazy stream needs decode_stream(..., forced=True) "
-                                     "(the sampler launch is fixed when the stream is opened)")
-                force = force_of(force, f"request {r}", lim)
-            return r, x, bert, prompt, lim, samp, nr, force, own_seed
-
-        rich = logprobs or base_n > 1
+        parse = _RequestParser(self.model, dict(zip(SAMPLE_KEYS, (top_k, top_p, temperature, repetition_penalty))), n,
+                               slots, early_stop_num, noise, lazy, forced, logprobs)
+        rich = logprobs or parse.base_n > 1
         if not lazy:
-            reqs = [norm(r, q) for r, q in enumerate(requests)]
+            reqs = [parse(r, q) for r, q in enumerate(requests)]
             if not reqs:
                 return iter(())
-            rich = rich or any(q[6] > 1 for q in reqs)
-            forced = forced or any(q[7] is not None for q in reqs)
-            Xmax = int(max_text_len) if max_text_len is not None else max(q[1].numel() for q in reqs)
-            Pmax = int(max_prompt_len) if max_prompt_len is not None else max(q[3].numel() for q in reqs)
-            n_max = max(q[4] for q in reqs)
-            cap = (Xmax, Pmax, n_max)
+            rich = rich or any(q.n > 1 for q in reqs)
+            forced = forced or any(q.force is not None for q in reqs)
+            Xmax = int(max_text_len) if max_text_len is not None else max(q.x.numel() for q in reqs)
+            Pmax = int(max_prompt_len) if max_prompt_len is not None else max(q.prompt.numel() for q in reqs)
+            cap = (Xmax, Pmax, max(q.limit for q in reqs))
             for q in reqs:
                 self._fits(q, cap)
             it = iter(reqs)
@@ -726,12 +754,8 @@ class T2SInfer:
             if max_text_len is None or max_prompt_len is None:
                 raise L.EvtError("a lazy iterable of requests needs max_text_len and max_prompt_len (the session's "
                                  "capacity is fixed when it is made)")
-            n_max = self._limit(early_stop_num)
-            if nsteps is not None:
-                n_max = min(n_max, nsteps)
-            cap = (int(max_text_len), int(max_prompt_len), n_max)
-            cap_steps.append(n_max)
-            it = (norm(r, q) for r, q in enumerate(requests))
+            cap = (int(max_text_len), int(max_prompt_len), parse.cap_steps)
+            it = (parse(r, q) for r, q in enumerate(requests))
         return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
                             max(1, int(poll)), control, logprobs, rich, forced)
 
@@ -765,9 +789,8 @@ class T2SInfer:
 
     @staticmethod
     def _fits(q, cap):
-        r, x, _bert, prompt, lim = q[:5]
-        if x.numel() > cap[0] or prompt.numel() > cap[1] or lim > cap[2]:
-            raise L.EvtError(f"request {r} (text {x.numel()}, prompt {prompt.numel()}, {lim} steps) does not fit the "
+        if q.x.numel() > cap[0] or q.prompt.numel() > cap[1] or q.limit > cap[2]:
+            raise L.EvtError(f"request {q.r} (text {q.x.numel()}, prompt {q.prompt.numel()}, {q.limit} steps) does not fit the "
                              f"session's capacity (text {cap[0]}, prompt {cap[1]}, {cap[2]} steps)")
 
     @torch.no_grad()
@@ -805,48 +828,24 @@ class T2SInfer:
             gkey = gkey + ("logprobs",)
         if S.force_on:   # likewise: the sampler launch with forced steps
             gkey = gkey + ("force",)
-        captured = False
-        if use_graph and S.graph_key != gkey:
+        captured = bool(use_graph and S.graph_key != gkey)
+        if captured:
             # every slot is idle here: the warm-up and the capture move no counter and write no cache line, so there is
             # no state to restore (the activations they leave are overwritten by each admission)
-            side = L.role_stream(dev, "decode_warm", ring=1)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                S.step_launches(W, sp, noise, pe)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="relaxed"):
-                S.step_launches(W, sp, noise, pe)
-            S.graph, S.graph_key, S._keep = g, gkey, (sp, noise, pe, W)
-            captured = True
+            S.capture(gkey, W, sp, noise, pe)
         return S, W, sp, pe, noise, use_graph, captured
 
     @torch.no_grad()
     def _admit(self, S, W, sp, pe, noise, batch, seeds):
-        """batch: [(slots, (r, x, bert, prompt, limit, sampling, n, force, seed))], `slots` the n slots of the request's
-        candidates in candidate order.  The prompt pass of _decode for these requests only, ONE row per request (texts padded to Xmax,
-        prompts to the longest of them); each row's keys/values go into the cache slabs of all its slots, then the row
-        state of every slot and step 0 for those slots: logits of the last prompt position and a masked sample."""
-        m = self.model
-        dev, cd = S.device, S.dtype
-        dense = self.dense(cd, dev)
+        """batch: [(slots, Request)], `slots` the n slots of the request's candidates in candidate order.  The prompt
+        pass for these requests only, ONE row per request (texts padded to Xmax, prompts to the longest of them); each
+        row's keys/values go into the cache slabs of all its slots, then the row state of every slot and step 0 for
+        those slots: logits of the last prompt position and a masked sample."""
+        dev = S.device
         Xmax, k = S.Xmax, len(batch)
-        y_lens = [int(q[3].numel()) for _s, q in batch]
-        x_lens = [int(q[1].numel()) for _s, q in batch]
+        y_lens = [int(q.prompt.numel()) for _s, q in batch]
         Pk = max(y_lens)
-        rows, prs = [], []
-        for _slots, (_r, x, bert, prompt, *_rest) in batch:
-            x, bert = x.to(dev), bert.to(dev)
-            xe = m.ar_text_embedding(x.unsqueeze(0))
-            xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
-            xe = m.ar_text_position(xe).squeeze(0)
-            rows.append(F.pad(xe, (0, 0, 0, Xmax - xe.size(0))))
-            prs.append(F.pad(prompt.to(dev).long(), (0, Pk - prompt.numel())))
-        pr = torch.stack(prs, dim=0)
-        xy = torch.cat([torch.stack(rows, dim=0), m.ar_audio_position(m.ar_audio_embedding(pr))], dim=1).to(cd).contiguous()
-        src_len = Xmax + Pk
-        xl = torch.tensor(x_lens, dtype=torch.int32, device=dev)
-        yl = torch.tensor(y_lens, dtype=torch.int32, device=dev)
+        pr = torch.stack([F.pad(q.prompt.to(dev).long(), (0, Pk - q.prompt.numel())) for _s, q in batch], dim=0)
         # per slot: (prompt row it copies from, candidate number, its request); one entry per request when every n is 1
         per = [(i, c, q) for i, (sl, q) in enumerate(batch) for c in range(len(sl))]
         slots_t = torch.tensor([s for sl, _q in batch for s in sl], dtype=torch.long, device=dev)
@@ -855,40 +854,32 @@ class T2SInfer:
         else:
             src_t = torch.tensor([i for i, _c, _q in per], dtype=torch.long, device=dev)
             spread = lambda t: t[src_t]
-        for i, lyr in enumerate(m.h.layers):
-            w = W.layers[i]
-            qkv = dense(xy, lyr.self_attn.in_proj_weight)
-            S.kc[i, slots_t, :src_len] = spread(qkv[..., S.E:2 * S.E])
-            S.vc[i, slots_t, :src_len] = spread(qkv[..., 2 * S.E:])
-            o = PrefixLMAttentionFn.apply(qkv, xl, yl, Xmax, S.H, 0.0, 0)
-            sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
-            xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
-            ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
-            xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
+        xy, xl, yl = self._prompt_pass(S, W, [q.x for _s, q in batch], [q.bert for _s, q in batch], pr, y_lens, Xmax,
+                                       slots_t, spread)
         # ---- row state ----
         # noise column: none for a [steps][V] table, the request's for [steps][R][V]; `noise` arrives with a candidate
         # dimension flattened ([steps][R * C][V], _stream_open), C = S.noise_cands: column r * C + c
         C_ = S.noise_cands
         ncol = (lambda r, c: 0) if noise is None or noise.dim() == 2 else (lambda r, c: r * C_ + c)
         # word 7: the row's forced steps; their tokens go behind the prompt in y, where the sampler launch finds them
-        rs = [[Xmax + y_lens[i], 0, y_lens[i], y_lens[i], q[4], ROW_RUNNING, ncol(q[0], c),
-               0 if q[7] is None else q[7].numel()] for i, c, q in per]
+        rs = [[Xmax + y_lens[i], 0, y_lens[i], y_lens[i], q.limit, ROW_RUNNING, ncol(q.r, c),
+               0 if q.force is None else q.force.numel()] for i, c, q in per]
         S.rstate[slots_t] = torch.tensor(rs, dtype=torch.int32).to(dev)
         S.stop[slots_t] = -1
         # candidate c draws lane r % 4 + 4c of the request's group seed (the hash folds the lane in as lane << 16): at
         # most 3 + 4 * 127 = 511 with n = STREAM_ROWS candidates, well inside the 16 bits the hash gives the lane
-        own = [q[8] if q[8] is not None else seeds(q[0]) for _i, _c, q in per]      # a request's own (seed, lane)
+        own = [q.seed if q.seed is not None else seeds(q.r) for _i, _c, q in per]      # a request's own (seed, lane)
         S.row_seed[slots_t] = torch.tensor([[sd, lane + self.MAX_ROWS * c] for (sd, lane), (_i, c, _q) in zip(own, per)],
                                            dtype=torch.int32).to(dev)
-        tab = torch.tensor([[0.0, *q[5][1:]] for _i, _c, q in per], dtype=torch.float32)
-        tab.view(torch.int32)[:, 0] = torch.tensor([q[5][0] for _i, _c, q in per], dtype=torch.int32)
+        tab = torch.tensor([[0.0, *q.sampling[1:]] for _i, _c, q in per], dtype=torch.float32)
+        tab.view(torch.int32)[:, 0] = torch.tensor([q.sampling[0] for _i, _c, q in per], dtype=torch.int32)
         S.row_sample[slots_t] = tab.view(torch.int32).to(dev)      # moved as integers: every bit pattern survives
         S.x_lens[slots_t] = spread(xl)
         S.y[slots_t] = 0
         S.y[slots_t, :Pk] = spread(pr)
         for (sl, q), P in zip(batch, y_lens):
-            if q[7] is not None:
-                S.y[torch.tensor(sl, device=dev), P:P + q[7].numel()] = q[7].to(dev)
+            if q.force is not None:
+                S.y[torch.tensor(sl, device=dev), P:P + q.force.numel()] = q.force.to(dev)
         S.mask.zero_()
         S.mask[slots_t] = 1
         # ---- step 0 of the admitted rows (the other rows' xb / logits are dead between two steps) ----
@@ -910,6 +901,7 @@ class T2SInfer:
         stats = self.stream_stats = dict(steps=0, admissions=0, admitted=[], prefill_rows=[], prefill_s=[], events=[],
                                          graph_captured=False)
         free, running, S, exhausted = list(range(slots)), {}, None, False
+        left = {}              # per running slot: graph replays until its row must have stopped
         cancelled = control.cancelled if control is not None else ()
         preempted = getattr(control, "preempted", ()) if control is not None else ()
         due = set()            # preempt() calls seen at a poll so far: a request still waiting then comes back as cancelled
@@ -926,18 +918,18 @@ class T2SInfer:
                         break
                     self._fits(head, cap)
                 q = head
-                if q[0] in cancelled or q[0] in due:     # withdrawn while it waited: no prompt pass, no slot
+                if q.r in cancelled or q.r in due:     # withdrawn while it waited: no prompt pass, no slot
                     head = None
-                    stats["events"].append(("cancel", stats["steps"], q[0], None))
-                    for c in range(q[6]):
-                        yield out(q[0], None, None, c, None)
+                    stats["events"].append(("cancel", stats["steps"], q.r, None))
+                    for c in range(q.n):
+                        yield out(q.r, None, None, c, None)
                     continue
-                if q[6] > len(free):             # FIFO: it waits for its n slots and nothing overtakes it
+                if q.n > len(free):             # FIFO: it waits for its n slots and nothing overtakes it
                     break
                 head = None
-                batch.append(([free.pop(0) for _ in range(q[6])], q))
+                batch.append(([free.pop(0) for _ in range(q.n)], q))
             if batch:
-                dev = batch[0][1][1].device
+                dev = batch[0][1].x.device
                 if S is None:
                     S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
                         cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced)
@@ -954,12 +946,11 @@ class T2SInfer:
                 stats["prefill_rows"].append(len(batch))
                 for sl, q in batch:
                     for c, slot in enumerate(sl):
-                        # request, prompt length, replays left at most, candidate
-                        running[slot] = [q[0], int(q[3].numel()), q[4] - 1, c]
-                        stats["events"].append(("admit", stats["steps"], q[0], slot))
+                        running[slot], left[slot] = _Row(q.r, int(q.prompt.numel()), c), q.limit - 1
+                        stats["events"].append(("admit", stats["steps"], q.r, slot))
             if not running:
                 return
-            n = min(poll, max(v[2] for v in running.values()))
+            n = min(poll, max(left.values()))
             for _ in range(n):
                 if use_graph:
                     S.graph.replay()
@@ -971,36 +962,36 @@ class T2SInfer:
             done = []
             due.update(preempted)
             for slot in sorted(running):
-                r, ylen, left, c = running[slot]
-                running[slot][2] = max(0, left - n)
+                r, ylen, c = running[slot]
+                left[slot] = max(0, left[slot] - n)
                 status = st[slot * ROW_WORDS + ROW_STATUS]
                 if status in (ROW_STOP_EOS, ROW_STOP_LIMIT):
                     last = st[S.B * ROW_WORDS + slot]
                     # one pair per step 0..last, written at the index the step's token went to: y[ylen + step]
                     lp = S.logp[slot, ylen:ylen + last + 1].clone() if logprobs else None
-                    done.append((slot, r, S.y[slot, :ylen + last].clone(), last - 1 if status == ROW_STOP_EOS else last,
-                                 c, lp, "finish"))
+                    done.append(_Done(slot, r, S.y[slot, :ylen + last].clone(),
+                                      last - 1 if status == ROW_STOP_EOS else last, c, lp, "finish"))
                 elif r in cancelled:
                     # an ordinary write on the stream of the replays: the row's workgroups see IDLE from the next
                     # replay on and return at once, whatever an admission later makes of the slot
                     S.rstate[slot, ROW_STATUS] = ROW_IDLE
-                    done.append((slot, r, None, None, c, None, "cancel"))
+                    done.append(_Done(slot, r, None, None, c, None, "cancel"))
                 elif r in due:
                     # idle as above; the row's tokens and log-probabilities up to the YCOUNT of this poll's state read
                     # are cloned on the stream of the replays, before an admission can write the slot
                     S.rstate[slot, ROW_STATUS] = ROW_IDLE
                     yc = st[slot * ROW_WORDS + ROW_YCOUNT]
                     lp = S.logp[slot, ylen:yc].clone() if logprobs else None
-                    done.append((slot, r, S.y[slot, :yc].clone(), None, c, lp, "preempt"))
+                    done.append(_Done(slot, r, S.y[slot, :yc].clone(), None, c, lp, "preempt"))
             if n == 0 and not done:
                 raise L.EvtError("stream session: a row is past its step limit but not stopped")
-            for slot, r, y, idx, c, lp, kind in done:
-                del running[slot]
-                free.append(slot)
-                stats["events"].append((kind, stats["steps"], r, slot))
+            for d in done:
+                del running[d.slot], left[d.slot]
+                free.append(d.slot)
+                stats["events"].append((d.kind, stats["steps"], d.request, d.slot))
             free.sort()
-            for slot, r, y, idx, c, lp, kind in done:
-                yield out(r, y, idx, c, lp)
+            for d in done:
+                yield out(d.request, d.y, d.idx, d.candidate, d.logprobs)
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
                                        early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,

@@ -334,6 +334,21 @@ static int launch_gemv(const void* W, const float* bias, const float* a, const f
   return evt_check_launch();
 }
 
+// The host side of evt_dec_sample, evt_dec_sample_rows and evt_dec_sample_embed around the one kernel dec_sample.  With
+// an embedding tail (ea.x set: evt_dec_sample_embed) the kernel moves the counters itself, which only a single workgroup
+// may do: the caller passes B = 1, and the one row reads column 0 of an injected noise table.
+static int launch_sample(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr,
+                         const float* noise, int32_t* stop_idx, float* probs_out, EmbedArgs ea, const int32_t* row_seed,
+                         int32_t B, void* stream) {
+  if (!p || !logits || !y || !ctr || !stop_idx || B <= 0) return EVT_EINVAL;
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1 || ea.x) sp.noise_rows = 1;
+  hipLaunchKernelGGL(dec_sample, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
+                     stop_idx, probs_out, ea, row_seed);
+  return evt_check_launch();
+}
+
 extern "C" {
 
 int evt_dec_gemv(int32_t wdtype, const void* W, const float* bias, const float* a, const float* r, const float* ln_g,
@@ -366,40 +381,22 @@ int evt_dec_attn(int32_t cdtype, const float* qkv, void* kcache, void* vcache, c
 
 int evt_dec_sample(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr, const float* noise,
                    int32_t* stop_idx, float* probs_out, int32_t B, void* stream) {
-  if (!p || !logits || !y || !ctr || !stop_idx || B <= 0) return EVT_EINVAL;
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
-  EmbedArgs none{};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
-                     (int*)stop_idx, probs_out, none, (const int*)nullptr);
-  return evt_check_launch();
+  return launch_sample(p, logits, y, ctr, noise, stop_idx, probs_out, EmbedArgs{}, nullptr, B, stream);
 }
 
 int evt_dec_sample_rows(const evt_sample_params* p, const float* logits, int64_t* y, const int32_t* ctr,
                         const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed, int32_t B,
                         void* stream) {
-  if (!p || !logits || !y || !ctr || !stop_idx || !row_seed || B <= 0) return EVT_EINVAL;
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
-  EmbedArgs none{};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
-                     (int*)stop_idx, probs_out, none, (const int*)row_seed);
-  return evt_check_launch();
+  if (!row_seed) return EVT_EINVAL;
+  return launch_sample(p, logits, y, ctr, noise, stop_idx, probs_out, EmbedArgs{}, row_seed, B, stream);
 }
 
 int evt_dec_sample_embed(const evt_sample_params* p, const float* logits, int64_t* y, int32_t* ctr, const float* noise,
                          int32_t* stop_idx, const float* emb, const float* pe, const float* alpha, float x_scale, float* x,
                          int32_t E, int32_t npos, int32_t dpos, void* stream) {
-  if (!p || !logits || !y || !ctr || !stop_idx || !emb || !pe || !alpha || !x || E <= 0 || npos <= 0) return EVT_EINVAL;
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
-  EmbedArgs ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
-  evt_sample_params sp = *p;
-  sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample, dim3(1), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y, (int*)ctr, noise,
-                     (int*)stop_idx, (float*)nullptr, ea, (const int*)nullptr);
-  return evt_check_launch();
+  if (!emb || !pe || !alpha || !x || E <= 0 || npos <= 0) return EVT_EINVAL;
+  return launch_sample(p, logits, y, ctr, noise, stop_idx, nullptr, EmbedArgs{emb, pe, alpha, x, x_scale, E, npos, dpos},
+                       nullptr, 1, stream);
 }
 
 int evt_dec_qkv_attn(int32_t dtype, const void* Wqkv, const float* bqkv, const float* a, const float* r,

@@ -240,6 +240,46 @@ __global__ __launch_bounds__(1024) void dec_sample_embed_rows_f(evt_sample_param
 
 }  // namespace
 
+// The host side of the four evt_dec_sample_embed_rows* entry points: the common validation, RowEmbed, the noise_rows
+// clamp and the choice of the kernel.  What differs per entry point: only kRows takes the four sampling values by value
+// and so refuses repetition_penalty <= 0 (the others read them from row_sample in device memory: the host that fills the
+// table validates them, t2s_infer.py); kRowsLp needs row_logp; kRowsF accepts NULL for it (the _p body) -- its forced
+// tokens live in y, device memory: the host that writes them validates them, the kernel clamps them.
+enum RowsEntry { kRows, kRowsP, kRowsLp, kRowsF };
+
+static int launch_sample_embed_rows(RowsEntry which, const evt_sample_params* p, const evt_row_sample* row_sample,
+                                    const float* logits, int64_t* y, int32_t* rstate, const float* noise,
+                                    int32_t* stop_idx, float* probs_out, const int32_t* row_seed, const int32_t* row_mask,
+                                    const float* emb, const float* pe, const float* alpha, float x_scale, float* x,
+                                    float* row_logp, int32_t B, int32_t E, int32_t npos, int32_t dpos, void* stream) {
+  if (!p || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 || E <= 0 ||
+      npos <= 0 || dpos < 0)
+    return EVT_EINVAL;
+  if ((which != kRows && !row_sample) || (which == kRowsLp && !row_logp)) return EVT_EINVAL;
+  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || (which == kRows && p->repetition_penalty <= 0.f)) return EVT_EINVAL;
+  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
+  evt_sample_params sp = *p;
+  if (sp.noise_rows < 1) sp.noise_rows = 1;
+  const dim3 grid(B), block(1024);
+  hipStream_t st = (hipStream_t)stream;
+  if (which == kRows)
+    hipLaunchKernelGGL(dec_sample_embed_rows, grid, block, 0, st, sp, logits, (long*)y, rstate, noise, stop_idx,
+                       probs_out, row_seed, row_mask, ea);
+  else if (which == kRowsP)
+    hipLaunchKernelGGL(dec_sample_embed_rows_p, grid, block, 0, st, sp, row_sample, logits, (long*)y, rstate, noise,
+                       stop_idx, probs_out, row_seed, row_mask, ea);
+  else if (which == kRowsLp)
+    hipLaunchKernelGGL(dec_sample_embed_rows_lp, grid, block, 0, st, sp, row_sample, logits, (long*)y, rstate, noise,
+                       stop_idx, probs_out, row_seed, row_mask, ea, row_logp);
+  else if (row_logp)
+    hipLaunchKernelGGL(dec_sample_embed_rows_f<true>, grid, block, 0, st, sp, row_sample, logits, (long*)y, rstate, noise,
+                       stop_idx, probs_out, row_seed, row_mask, ea, row_logp);
+  else
+    hipLaunchKernelGGL(dec_sample_embed_rows_f<false>, grid, block, 0, st, sp, row_sample, logits, (long*)y, rstate,
+                       noise, stop_idx, probs_out, row_seed, row_mask, ea, row_logp);
+  return evt_check_launch();
+}
+
 extern "C" {
 
 int evt_dec_attn_rows(int32_t cdtype, const float* qkv, void* kcache, void* vcache, const int32_t* rstate, float* out,
@@ -262,16 +302,8 @@ int evt_dec_sample_embed_rows(const evt_sample_params* p, const float* logits, i
                               const float* noise, int32_t* stop_idx, float* probs_out, const int32_t* row_seed,
                               const int32_t* row_mask, const float* emb, const float* pe, const float* alpha,
                               float x_scale, float* x, int32_t B, int32_t E, int32_t npos, int32_t dpos, void* stream) {
-  if (!p || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 || E <= 0 ||
-      npos <= 0 || dpos < 0)
-    return EVT_EINVAL;
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0 || p->repetition_penalty <= 0.f) return EVT_EINVAL;
-  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample_embed_rows, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, logits, (long*)y,
-                     (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed, (const int*)row_mask, ea);
-  return evt_check_launch();
+  return launch_sample_embed_rows(kRows, p, nullptr, logits, y, rstate, noise, stop_idx, probs_out, row_seed, row_mask,
+                                  emb, pe, alpha, x_scale, x, nullptr, B, E, npos, dpos, stream);
 }
 
 int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
@@ -279,18 +311,8 @@ int evt_dec_sample_embed_rows_p(const evt_sample_params* p, const evt_row_sample
                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                 const float* alpha, float x_scale, float* x, int32_t B, int32_t E, int32_t npos,
                                 int32_t dpos, void* stream) {
-  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 ||
-      E <= 0 || npos <= 0 || dpos < 0)
-    return EVT_EINVAL;
-  // the four per-row values live in device memory: the host that fills the table validates them (t2s_infer.py)
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
-  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample_embed_rows_p, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
-                     (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
-                     (const int*)row_mask, ea);
-  return evt_check_launch();
+  return launch_sample_embed_rows(kRowsP, p, row_sample, logits, y, rstate, noise, stop_idx, probs_out, row_seed,
+                                  row_mask, emb, pe, alpha, x_scale, x, nullptr, B, E, npos, dpos, stream);
 }
 
 int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
@@ -298,17 +320,8 @@ int evt_dec_sample_embed_rows_lp(const evt_sample_params* p, const evt_row_sampl
                                  const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                  const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
                                  int32_t npos, int32_t dpos, void* stream) {
-  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x ||
-      !row_logp || B <= 0 || E <= 0 || npos <= 0 || dpos < 0)
-    return EVT_EINVAL;
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
-  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  hipLaunchKernelGGL(dec_sample_embed_rows_lp, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample, logits,
-                     (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
-                     (const int*)row_mask, ea, row_logp);
-  return evt_check_launch();
+  return launch_sample_embed_rows(kRowsLp, p, row_sample, logits, y, rstate, noise, stop_idx, probs_out, row_seed,
+                                  row_mask, emb, pe, alpha, x_scale, x, row_logp, B, E, npos, dpos, stream);
 }
 
 int evt_dec_sample_embed_rows_f(const evt_sample_params* p, const evt_row_sample* row_sample, const float* logits,
@@ -316,23 +329,8 @@ int evt_dec_sample_embed_rows_f(const evt_sample_params* p, const evt_row_sample
                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                 const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
                                 int32_t npos, int32_t dpos, void* stream) {
-  if (!p || !row_sample || !logits || !y || !rstate || !stop_idx || !row_seed || !emb || !pe || !alpha || !x || B <= 0 ||
-      E <= 0 || npos <= 0 || dpos < 0)
-    return EVT_EINVAL;
-  // the forced tokens live in y, device memory: the host that writes them validates them, the kernel clamps them
-  if (p->V <= 1 || p->V > kSortN || p->ymax <= 0) return EVT_EINVAL;
-  RowEmbed ea{emb, pe, alpha, x, x_scale, E, npos, dpos};
-  evt_sample_params sp = *p;
-  if (sp.noise_rows < 1) sp.noise_rows = 1;
-  if (row_logp)
-    hipLaunchKernelGGL(dec_sample_embed_rows_f<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample,
-                       logits, (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
-                       (const int*)row_mask, ea, row_logp);
-  else
-    hipLaunchKernelGGL(dec_sample_embed_rows_f<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, sp, row_sample,
-                       logits, (long*)y, (int*)rstate, noise, (int*)stop_idx, probs_out, (const int*)row_seed,
-                       (const int*)row_mask, ea, row_logp);
-  return evt_check_launch();
+  return launch_sample_embed_rows(kRowsF, p, row_sample, logits, y, rstate, noise, stop_idx, probs_out, row_seed,
+                                  row_mask, emb, pe, alpha, x_scale, x, row_logp, B, E, npos, dpos, stream);
 }
 
 }  // extern "C"

@@ -1,13 +1,15 @@
 """Per-kernel register / scratch / occupancy table of one .hip source (hipcc -Rpass-analysis=kernel-resource-usage):
-what the compiler made of a kernel can be read without a GPU.  usage: python tools/kres.py csrc/file.hip [filter]"""
+what the compiler made of a kernel can be read without a GPU.
+usage: python tools/kres.py csrc/file.hip [filter] [-DEVT_HALF_F16 or other compiler flags]"""
 import re
 import subprocess
 import sys
 
 src = sys.argv[1]
-flt = sys.argv[2] if len(sys.argv) > 2 else ""
+rest = [a for a in sys.argv[2:] if not a.startswith("-")]
+flt = rest[0] if rest else ""
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
-       "-c", src, "-o", "/tmp/kres.o"]
+       *[a for a in sys.argv[2:] if a.startswith("-")], "-c", src, "-o", "/tmp/kres.o"]
 r = subprocess.run(cmd, capture_output=True, text=True)
 if r.returncode:
     print(r.stderr[-4000:])
@@ -31,5 +33,5 @@ for name, d in rows.items():
     dem = re.sub(r"\(.*\)$", "", dem)
     if flt and flt not in dem:
         continue
-    print(f"{dem:60s} vgpr {d.get('VGPRs','?'):>4} agpr {d.get('AGPRs','?'):>4} scratch {d.get('ScratchSize [bytes/lane]','?'):>5} "
+    print(f"{dem:60s} vgpr {d.get('VGPRs','?'):>4} agpr {d.get('AGPRs','?'):>4} sgpr {d.get('TotalSGPRs','?'):>4} lds {d.get('LDS Size [bytes/block]','?'):>6} scratch {d.get('ScratchSize [bytes/lane]','?'):>5} "
           f"occ {d.get('Occupancy [waves/SIMD]','?')} sgpr-spill {d.get('SGPRs Spill','?')} vgpr-spill {d.get('VGPRs Spill','?')}")
