@@ -283,9 +283,233 @@ __global__ __launch_bounds__(256) void clip_rescale_kernel(const float* __restri
   }
 }
 
+// ---- the two ends of Chinese-RoBERTa on a ragged batch of sentences
+// Output end: out item i = [C][n_i] at element C * item_off[i], column p of it = token row src[p] of h (or zeros).
+// A block owns kXP consecutive columns of ONE item and kXC channels.  Read side: a row's kXC channels are 16 bytes per
+// lane (16 lanes of 4 floats, 8 lanes of 8 halves), four (eight) rows per wave instruction.  LDS tile [kXC][kXS] fp32,
+// kXS = 65: a transposing ds_write_b32 of lane (row r, lane-in-row g) element k goes to bank (vec g + k + r) mod 32 --
+// vec g takes 8 (fp32) or 4 (16-bit) values, the 2 (4) rows of a 32-lane half shift them by r < vec: 2-way.  Store side:
+// wave w takes channels w, w + 4, ..., lane l column l: consecutive words of one LDS row (conflict-free) and
+// consecutive elements of one output row.
+constexpr int kXP = 64, kXC = 64, kXS = kXP + 1;
+
+template <typename T> struct Vec16;
+template <> struct Vec16<float> {
+  static constexpr int n = 4;
+  static __device__ __forceinline__ void load(const float* p, float* v) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+  }
+};
+template <> struct Vec16<h16_t> {
+  static constexpr int n = 8;
+  static __device__ __forceinline__ void load(const h16_t* p, float* v) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    v[0] = h2f_lo(a.x), v[1] = h2f_hi(a.x), v[2] = h2f_lo(a.y), v[3] = h2f_hi(a.y);
+    v[4] = h2f_lo(a.z), v[5] = h2f_hi(a.z), v[6] = h2f_lo(a.w), v[7] = h2f_hi(a.w);
+  }
+};
+
+// grid (upper bound of the column tiles, ceil(C / kXC)), 256 threads.  The block finds the item that owns its tile from
+// item_off itself (no host copy of it is needed): thread t counts the tiles of items [t chunk, (t + 1) chunk), the
+// counts are prefix-summed in LDS, the thread whose range holds tile blockIdx.x publishes (first column, end).  Every
+// offset is clamped into [previous end, total], so that no item_off can send a store outside out[0, C * total).
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void phone_expand_kernel(const TI* __restrict__ h, long n_rows, int C,
+                                                           const int32_t* __restrict__ src,
+                                                           const int32_t* __restrict__ item_off, int n_items, int total,
+                                                           TO* __restrict__ out) {
+  __shared__ float tile[kXC * kXS];
+  __shared__ int cnt[256];
+  __shared__ int sl[kXP];
+  __shared__ int found[3];           // first column of the tile, first and end column of its item
+  const int tid = threadIdx.x;
+  const int chunk = (n_items + 255) / 256;
+  const int i0 = min(tid * chunk, n_items), i1 = min(i0 + chunk, n_items);
+  auto bounds = [&](int i, int& lo, int& hi) {
+    lo = min(max(item_off[i], 0), total);
+    hi = min(max(item_off[i + 1], lo), total);
+  };
+  int mine = 0;
+  for (int i = i0; i < i1; ++i) {
+    int lo, hi;
+    bounds(i, lo, hi);
+    mine += (hi - lo + kXP - 1) / kXP;
+  }
+  cnt[tid] = mine;
+  if (tid == 0) found[0] = -1;
+  __syncthreads();
+  int before = 0;
+  for (int u = 0; u < tid; ++u) before += cnt[u];
+  const int want = blockIdx.x;
+  if (want >= before && want < before + mine) {
+    int k = before;
+    for (int i = i0; i < i1; ++i) {
+      int lo, hi;
+      bounds(i, lo, hi);
+      const int nt = (hi - lo + kXP - 1) / kXP;
+      if (want < k + nt) {
+        found[0] = lo + (want - k) * kXP, found[1] = lo, found[2] = hi;
+        break;
+      }
+      k += nt;
+    }
+  }
+  __syncthreads();
+  const int p0 = found[0];
+  if (p0 < 0) return;                                   // block-uniform: a tile behind the last one
+  const int lo = found[1], hi = found[2];
+  const int np = min(kXP, hi - p0);                     // live columns of this tile, >= 1
+  if (tid < kXP) {
+    int s = tid < np ? src[p0 + tid] : -1;
+    sl[tid] = (s < 0 || (long)s >= n_rows) ? -1 : s;
+  }
+  __syncthreads();
+  constexpr int V = Vec16<TI>::n, LPR = kXC / V, RPP = 256 / LPR;
+  const int g = tid % LPR, r = tid / LPR;
+  const int cb = blockIdx.y * kXC;
+  const bool chan = cb + g * V < C;                     // C % 8 == 0: a vector is live or dead as a whole
+#pragma unroll
+  for (int pass = 0; pass < kXP / RPP; ++pass) {
+    const int pl = pass * RPP + r;
+    if (pl < np) {
+      float v[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) v[k] = 0.f;
+      const int s = sl[pl];
+      if (s >= 0 && chan) Vec16<TI>::load(h + (long)s * C + cb + g * V, v);
+#pragma unroll
+      for (int k = 0; k < V; ++k) tile[(g * V + k) * kXS + pl] = v[k];
+    }
+  }
+  __syncthreads();
+  const int lane = tid & 63, wave = tid >> 6;
+  const int n = hi - lo;
+  TO* ob = out + (long)C * lo + (p0 - lo) + lane;
+  if (lane < np)
+    for (int c = wave; c < kXC && cb + c < C; c += 4) ob[(long)(cb + c) * n] = from_f<TO>(tile[c * kXS + lane]);
+}
+
+template <typename TI, typename TO>
+void launch_expand(hipStream_t st, const void* h, long n_rows, int C, const int32_t* src, const int32_t* item_off,
+                   int n_items, int total, void* out) {
+  const dim3 grid((total + kXP - 1) / kXP + n_items, (C + kXC - 1) / kXC);
+  hipLaunchKernelGGL((phone_expand_kernel<TI, TO>), grid, dim3(256), 0, st, (const TI*)h, n_rows, C, src, item_off, n_items,
+                     total, (TO*)out);
+}
+
+// Input end: one wave per token row, lane l channels 4 l + 256 i.  Three passes over the same three table rows (12 KB at
+// C = 1024, from L1 after the first), each forming the same fp32 sum (word + pos) + type: the sum, the squared deviations
+// from the mean, the normalised store.  Lane partial sums ascend in i, the wave sum is the xor butterfly: the order is a
+// function of C alone.
+template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d);
+template <> __device__ __forceinline__ void store4<float>(float* p, float a, float b, float c, float d) {
+  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+}
+template <> __device__ __forceinline__ void store4<h16_t>(h16_t* p, float a, float b, float c, float d) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(f2h_pack(a, b), f2h_pack(c, d));
+}
+
+__device__ __forceinline__ float4 embed_sum4(const float* w, const float* p, const float* t, int c) {
+#pragma clang fp contract(off)
+  const float4 a = *reinterpret_cast<const float4*>(w + c);
+  const float4 b = *reinterpret_cast<const float4*>(p + c);
+  const float4 d = *reinterpret_cast<const float4*>(t + c);
+  return make_float4((a.x + b.x) + d.x, (a.y + b.y) + d.y, (a.z + b.z) + d.z, (a.w + b.w) + d.w);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ tt,
+                                                            const int32_t* __restrict__ lens, int B, int Tn,
+                                                            const float* __restrict__ word, int vocab,
+                                                            const float* __restrict__ pos, const float* __restrict__ type,
+                                                            int types, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, int C,
+                                                            T* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+  if (row >= (long)B * Tn) return;                      // wave-uniform
+  const int b = (int)(row / Tn), t = (int)(row - (long)b * Tn);
+  T* o = out + row * C;
+  if (t >= min(max(lens[b], 0), Tn)) {
+    for (int c = lane * 4; c < C; c += 256) store4<T>(o + c, 0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const int id = min(max(ids[row], 0), vocab - 1);
+  const int ty = tt ? min(max(tt[row], 0), types - 1) : 0;
+  const float* w = word + (long)id * C;
+  const float* p = pos + (long)t * C;
+  const float* y = type + (long)ty * C;
+  float s = 0.f;
+  for (int c = lane * 4; c < C; c += 256) {
+    const float4 v = embed_sum4(w, p, y, c);
+    s += (v.x + v.y) + (v.z + v.w);
+  }
+  const float mean = wave_reduce_sum(s) / (float)C;
+  float q = 0.f;
+  for (int c = lane * 4; c < C; c += 256) {
+    const float4 v = embed_sum4(w, p, y, c);
+    const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
+    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+  }
+  const float rstd = 1.f / sqrtf(wave_reduce_sum(q) / (float)C + eps);
+  for (int c = lane * 4; c < C; c += 256) {
+    const float4 v = embed_sum4(w, p, y, c);
+    const float4 gm = *reinterpret_cast<const float4*>(gamma + c);
+    const float4 bt = *reinterpret_cast<const float4*>(beta + c);
+    store4<T>(o + c, (v.x - mean) * rstd * gm.x + bt.x, (v.y - mean) * rstd * gm.y + bt.y,
+              (v.z - mean) * rstd * gm.z + bt.z, (v.w - mean) * rstd * gm.w + bt.w);
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int evt_phone_expand_rows(int32_t dtype, const void* h, int32_t B, int32_t T, int32_t C, const int32_t* src,
+                          const int32_t* item_off, int32_t n_items, int32_t total, int32_t out_dtype, void* out,
+                          void* stream) {
+  if (!h || !item_off || B <= 0 || T <= 0 || C < 8 || C > 4096 || (C & 7) || n_items <= 0 || n_items > 65535 || total < 0)
+    return EVT_EINVAL;
+  if ((long)B * T > 0x7fffffffL || ((uintptr_t)h & 15)) return EVT_EINVAL;
+  if (dtype != EVT_DT_HALF && dtype != EVT_DT_F32) return EVT_ENOTSUP;
+  if (out_dtype != EVT_DT_HALF && out_dtype != EVT_DT_F32) return EVT_ENOTSUP;
+  if (total == 0) return EVT_OK;                        // nothing to write
+  if (!src || !out) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long n_rows = (long)B * T;
+  if (dtype == EVT_DT_F32 && out_dtype == EVT_DT_F32)
+    launch_expand<float, float>(st, h, n_rows, C, src, item_off, n_items, total, out);
+  else if (dtype == EVT_DT_F32)
+    launch_expand<float, h16_t>(st, h, n_rows, C, src, item_off, n_items, total, out);
+  else if (out_dtype == EVT_DT_F32)
+    launch_expand<h16_t, float>(st, h, n_rows, C, src, item_off, n_items, total, out);
+  else
+    launch_expand<h16_t, h16_t>(st, h, n_rows, C, src, item_off, n_items, total, out);
+  return evt_check_launch();
+}
+
+int evt_bert_embed_ln_rows(int32_t dtype, const int32_t* ids, const int32_t* tt, const int32_t* lens, int32_t B, int32_t T,
+                           const float* word, int32_t vocab, const float* pos, int32_t max_pos, const float* type,
+                           int32_t types, const float* gamma, const float* beta, float eps, int32_t C, void* out,
+                           void* stream) {
+  if (!ids || !lens || !word || !pos || !type || !gamma || !beta || !out || B <= 0 || T <= 0 || T > max_pos || vocab <= 0 ||
+      types <= 0 || C < 4 || C > 8192 || (C & 3) || !(eps >= 0.f))
+    return EVT_EINVAL;
+  if ((long)B * T > 0x7fffffffL) return EVT_EINVAL;
+  if (((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)
+    return EVT_EINVAL;
+  if (dtype != EVT_DT_HALF && dtype != EVT_DT_F32) return EVT_ENOTSUP;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(((long)B * T + 3) / 4));
+  if (dtype == EVT_DT_HALF)
+    hipLaunchKernelGGL(bert_embed_ln_kernel<h16_t>, grid, dim3(256), 0, st, ids, tt, lens, B, T, word, vocab, pos, type, types,
+                       gamma, beta, eps, C, (h16_t*)out);
+  else
+    hipLaunchKernelGGL(bert_embed_ln_kernel<float>, grid, dim3(256), 0, st, ids, tt, lens, B, T, word, vocab, pos, type, types,
+                       gamma, beta, eps, C, (float*)out);
+  return evt_check_launch();
+}
 
 int evt_gelu_rows_fwd(int32_t dtype, const void* x, const float* bias, void* out, int64_t nseq, int32_t t_in, int32_t t_out,
                       int32_t C, void* stream) {

@@ -62,7 +62,8 @@ def rescale_clip(audio32k: np.ndarray):
 class FeatureWriter:
     """writes the feature directory of one data set: `ssl(name, audio32k)` and `text(name, ...)` per item, `close()` writes
     2-name2text.txt.  hubert: feature_extractor.CNHubert (or any callable wav16k [n] -> [1, 768, T]); bert:
-    feature_extractor.BertFeatures (or any object with phone_level_feature(input_ids, word2ph))."""
+    feature_extractor.BertFeatures (or any object with phone_level_feature(input_ids, word2ph); `text_batch` takes a list of
+    items through its phone_level_features_batch(ids_list, word2ph_list, group=))."""
 
     def __init__(self, out_dir, hubert=None, bert=None):
         self.out_dir, self.hubert, self.bert = out_dir, hubert, bert
@@ -162,6 +163,29 @@ class FeatureWriter:
                 raise ValueError("bert_feature and phones not match")          # normalize.py:123-124
             torch.save(feat, path)
         self._text_lines.append("%s\t%s\t%s\t%s" % (name, " ".join(phones), word2ph, norm_text))
+
+    def text_batch(self, items, group=16) -> None:
+        """`text` for a list of (name, phones, word2ph, norm_text, language, input_ids): the items that `text` would send
+        through BERT -- Chinese ones without a 3-bert/<name>.pt -- go through bert.phone_level_features_batch in groups
+        of at most `group` (everything else is dropped before anything is uploaded; nothing is launched when none is left),
+        every feature is checked against its item's phones and written as `text` writes it (float32 [1024, n] on the CPU),
+        and the text lines of ALL items are appended in input order."""
+        items = [tuple(it) for it in items]
+        todo, seen = [], set()
+        for i, (name, _phones, _word2ph, _norm_text, language, _ids) in enumerate(items):
+            if language == "zh" and name not in seen and not os.path.exists(os.path.join(self.bert_dir, name + ".pt")):
+                todo.append(i)
+                seen.add(name)             # a name given twice is written once, as by two calls of `text`
+        if todo:
+            ids = [torch.as_tensor(items[i][5]).reshape(-1) for i in todo]
+            feats = self.bert.phone_level_features_batch(ids, [list(items[i][2]) for i in todo], group=group)
+            for i, feat in zip(todo, feats):
+                if feat.shape[-1] != len(items[i][1]):
+                    raise ValueError(f"bert_feature and phones not match (item {i}: {items[i][0]})")
+            for i, feat in zip(todo, feats):
+                torch.save(feat.float().clone(), os.path.join(self.bert_dir, items[i][0] + ".pt"))
+        for name, phones, word2ph, norm_text, _language, _ids in items:
+            self._text_lines.append("%s\t%s\t%s\t%s" % (name, " ".join(phones), word2ph, norm_text))
 
     def close(self):
         with open(os.path.join(self.out_dir, "2-name2text.txt"), "w", encoding="utf8") as f:

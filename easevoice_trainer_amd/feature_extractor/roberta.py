@@ -11,7 +11,13 @@ The encoder is restated module for module with the checkpoint's parameter names 
 layers above the one that is read are not built.  Rows are [B, T, C]; per layer: three 1x1-convolution projections + the
 attention core (hip/enc.py::rel_self_attention, window None, key padding by lengths), the output projection,
 LayerNorm(x + attn) (evt_add_layernorm_fwd), Linear -> GELU (evt_gelu_rows_fwd) -> Linear, LayerNorm(x + ffn).  The
-embedding sum (word + position + token type) is a gather and its LayerNorm one launch.  Inference only."""
+embedding sum (word + position + token type) is a gather and its LayerNorm one launch.  Inference only.
+
+Ragged groups of sentences (`BertFeatures.hidden_rows`, `phone_level_features_batch`) run the same layers on right-padded
+ids with the lengths as key lengths; both ends of a group are one launch each: hip/feat.py::bert_embed_ln_rows in front
+(the embedding sum and its LayerNorm, zeros behind a sentence's length) and phone_expand_rows behind (the [1:-1] slice, the
+repetition by word2ph, the transpose and the cast for all sentences of the group, from the host-built `column_map`)."""
+import numpy as np
 import torch
 from torch import nn
 
@@ -149,10 +155,74 @@ class BertEncoderStack(nn.Module):
         return x
 
 
+MAX_TOKENS = 512        # the checkpoint's position table
+
+
+def column_map(items):
+    """The column map of hip/feat.py::phone_expand_rows, on the host.  items: per output item a list of segments,
+    ("rows", first, counts) -- token rows first, first + 1, ... of the flattened hidden rows, row i repeated counts[i] times
+    (0 allowed) -- or ("zero", n) -- n columns of zeros.  -> (src int32 [total], item_off int32 [len(items) + 1])"""
+    parts, item_off = [], [0]
+    for segments in items:
+        n = 0
+        for seg in segments:
+            if seg[0] == "rows":
+                counts = np.asarray(seg[2], dtype=np.int64).reshape(-1)
+                if counts.size and counts.min() < 0:
+                    raise ValueError("negative repeat count")
+                part = np.repeat(int(seg[1]) + np.arange(counts.size, dtype=np.int64), counts)
+            elif seg[0] == "zero":
+                if int(seg[1]) < 0:
+                    raise ValueError("negative column count")
+                part = np.full(int(seg[1]), -1, dtype=np.int64)
+            else:
+                raise ValueError(f"unknown segment kind {seg[0]!r}")
+            parts.append(part)
+            n += part.size
+        item_off.append(item_off[-1] + n)
+    if item_off[-1] >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 columns in one call")
+    src = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    return src.astype(np.int32), np.asarray(item_off, dtype=np.int32)
+
+
+def check_sentences(ids_list, word2ph_list=None):
+    """the host checks of the batch methods, made for every sentence before anything is uploaded: -> the id vectors as 1-D
+    int32 arrays.  ValueError for a sentence outside 2 .. 512 tokens, and the reference's "text and word2ph not match"
+    (normalize.py:96-97) with the sentence's index."""
+    out = []
+    for b, ids in enumerate(ids_list):
+        a = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).astype(np.int32)
+        if a.ndim != 1 or not 2 <= a.size <= MAX_TOKENS:
+            raise ValueError(f"sentence {b}: a 1-D vector of 2 .. {MAX_TOKENS} ids ([CLS] chars [SEP]) expected, got shape "
+                             f"{tuple(a.shape)}")
+        out.append(a)
+    if word2ph_list is not None:
+        if len(word2ph_list) != len(out):
+            raise ValueError(f"{len(word2ph_list)} word2ph lists for {len(out)} sentences")
+        for b, (a, w) in enumerate(zip(out, word2ph_list)):
+            if len(w) != a.size - 2:
+                raise ValueError(f"text and word2ph not match (sentence {b}: {a.size - 2} characters, {len(w)} counts)")
+            if len(w) and min(w) < 0:
+                raise ValueError(f"sentence {b}: negative word2ph count")
+    return out
+
+
+def length_groups(lengths, group):
+    """indices sorted by length (stable) and cut into groups of at most `group`"""
+    group = int(group)
+    if group < 1:
+        raise ValueError("group must be at least 1")
+    order = sorted(range(len(lengths)), key=lambda i: lengths[i])
+    return [order[k:k + group] for k in range(0, len(order), group)]
+
+
 class BertFeatures:
     """`_get_bert_feature` (normalize.py:88-106) on the GPU.  `weights`: a BertForMaskedLM / BertModel state_dict (keys
     `bert.*`), or a directory / file holding one; None keeps the random initialisation (tests); `config`: overrides of the
-    BERT-large dimensions."""
+    BERT-large dimensions.  `phone_level_feature` takes one sentence; `hidden_rows` / `phone_level_features_batch` take a
+    ragged group through the encoder at once, with both ends of it on the device (hip/feat.py::bert_embed_ln_rows,
+    phone_expand_rows)."""
 
     def __init__(self, weights=None, device="cuda:0", dtype=torch.float32, **config):
         from .cnhubert import _read_state_dict
@@ -166,6 +236,10 @@ class BertFeatures:
         self.rt.bank.weight_grads = False
         self.rt.prepare(force=True)
         self.model, self.device, self.dtype = net, torch.device(device), dtype
+
+    @property
+    def hidden_size(self):
+        return self.model.bert.embeddings.word_embeddings.weight.size(1)
 
     @torch.no_grad()
     def hidden(self, input_ids, attention_mask=None, token_type_ids=None):
@@ -182,3 +256,63 @@ class BertFeatures:
             raise ValueError("text and word2ph not match")         # the reference's failure message, normalize.py:96-97
         rep = torch.as_tensor(list(word2ph), device=res.device)
         return torch.repeat_interleave(res, rep, dim=0).T.contiguous().cpu()
+
+    @torch.no_grad()
+    def hidden_rows(self, ids_list):
+        """a ragged group of sentences, each a 1-D id vector [CLS] chars [SEP] of 2 .. 512 tokens (ValueError otherwise) ->
+        (hidden_states[read_layer] [B, Tmax, hidden] on the GPU, the token counts): the ids right-padded to the group's
+        longest sentence and uploaded with the lengths in one copy, the embeddings in one launch
+        (hip/feat.py::bert_embed_ln_rows), the encoder layers with the lengths as key lengths.  Row b's live tokens are what
+        the sentence gives alone; rows behind a sentence's length hold nothing of use."""
+        from ..hip.feat import bert_embed_ln_rows
+
+        arrays = check_sentences(ids_list)
+        if not arrays:
+            raise ValueError("no sentence")
+        L.set_half(self.dtype)
+        lens = [a.size for a in arrays]
+        B, T = len(arrays), max(lens)
+        host = np.zeros(B * T + B, dtype=np.int32)
+        for b, a in enumerate(arrays):
+            host[b * T:b * T + a.size] = a
+        host[B * T:] = lens
+        dev = torch.from_numpy(host).to(self.device)
+        ids, lens_dev = dev[:B * T].view(B, T), dev[B * T:]
+        emb = self.model.bert.embeddings
+        x = bert_embed_ln_rows(ids, lens_dev, emb.word_embeddings.weight, emb.position_embeddings.weight,
+                               emb.token_type_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps,
+                               self.dtype)
+        for layer in self.model.bert.encoder.layer:
+            x = layer(x, lens_dev)
+        return x, lens
+
+    @staticmethod
+    def _expand(h, src, item_off, out_dtype):
+        """(src, item_off) of column_map, on the host -> the packed buffer on h's device: one upload, one launch"""
+        from ..hip.feat import phone_expand_rows
+
+        n_items, total = item_off.size - 1, int(item_off[-1])
+        both = torch.from_numpy(np.concatenate([item_off, src])).to(h.device)
+        return phone_expand_rows(h, both[n_items + 1:], both[:n_items + 1], n_items, total, out_dtype)
+
+    @torch.no_grad()
+    def phone_level_features_batch(self, ids_list, word2ph_list, group=16, out_dtype=torch.float32, device_out=False):
+        """`phone_level_feature` for many sentences: ids_list 1-D id vectors ([CLS] chars [SEP]), word2ph_list the counts per
+        character (0 allowed) -> the [hidden, sum(word2ph)] tensors of out_dtype in INPUT order, on the CPU (on the GPU with
+        device_out).  The sentences are sorted by length and cut into groups of at most `group`; a group costs one upload of
+        ids and lengths, one pass of the encoder, one upload of the column map (built with numpy), one
+        hip/feat.py::phone_expand_rows and one device -> host copy of its packed buffer, of which the results are views.
+        ValueError("text and word2ph not match ...") naming the sentence, before anything is uploaded."""
+        arrays = check_sentences(ids_list, word2ph_list)
+        out = [None] * len(arrays)
+        for members in length_groups([a.size for a in arrays], group):
+            h, lens = self.hidden_rows([arrays[i] for i in members])
+            T, Cc = h.size(1), h.size(2)
+            src, item_off = column_map([[("rows", j * T + 1, word2ph_list[i])] for j, i in enumerate(members)])
+            packed = self._expand(h, src, item_off, out_dtype)
+            if not device_out:
+                packed = packed.cpu()
+            for j, i in enumerate(members):
+                lo, hi = int(item_off[j]), int(item_off[j + 1])
+                out[i] = packed[Cc * lo:Cc * hi].view(Cc, hi - lo)
+        return out

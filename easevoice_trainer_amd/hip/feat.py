@@ -102,6 +102,69 @@ def clip_rescale_rows(x, lens):
     return f, q, peak
 
 
+EXPAND_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                   C.c_int32, C.c_void_p, C.c_void_p]
+EMBED_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                  C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]
+
+
+def _check_i32(what, name, t, numel, device):
+    if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.device != device or t.numel() != numel
+            or not t.is_contiguous()):
+        raise L.EvtError(f"{what}: {name} must be a contiguous int32 tensor of {numel} elements on {device}")
+
+
+def phone_expand_rows(h, src, item_off, n_items, total, out_dtype=torch.float32):
+    """h [B, T, C] hidden rows (fp32 or the build's 16-bit type) -> the packed phone-level features of `n_items` items, a
+    1-D tensor of C * total elements of out_dtype: item i is the [C, n_i] block at C * item_off[i], its column p - item_off[i]
+    the token row src[p] of h.reshape(-1, C) (zeros for src[p] = -1 or outside the rows).  src int32 [total], item_off int32
+    [n_items + 1] on h's device.  One launch (evt_phone_expand_rows; include/evt.h has the definition), no
+    synchronisation; rows that no column names are not read."""
+    if not torch.is_tensor(h) or h.dim() != 3 or not h.is_contiguous() or not h.is_cuda:
+        raise L.EvtError("phone_expand_rows: contiguous [B, T, C] rows on the GPU expected")
+    B, T, Cc = h.shape
+    n_items, total = int(n_items), int(total)
+    if Cc % 8 or not 8 <= Cc <= 4096 or B < 1 or T < 1 or not 1 <= n_items <= 65535 or total < 0:
+        raise L.EvtError(f"phone_expand_rows: rows {tuple(h.shape)}, {n_items} items, {total} columns are not served")
+    _check_i32("phone_expand_rows", "src", src, total, h.device)
+    _check_i32("phone_expand_rows", "item_off", item_off, n_items + 1, h.device)
+    if torch.is_grad_enabled() and h.requires_grad:
+        raise L.EvtError("phone_expand_rows is inference only: run it under torch.no_grad()")
+    out = torch.empty(Cc * total, dtype=out_dtype, device=h.device)
+    L.check(_rows_entry("evt_phone_expand_rows", EXPAND_ARGTYPES)(
+        L.dt_of(h), h.data_ptr(), B, T, Cc, src.data_ptr(), item_off.data_ptr(), n_items, total, L.dt_code(out_dtype),
+        out.data_ptr(), L.stream_ptr()), "evt_phone_expand_rows")
+    return out
+
+
+def bert_embed_ln_rows(ids, lens, word, pos, type_emb, gamma, beta, eps, dtype, token_type_ids=None):
+    """ids int32 [B, T] (right-padded), lens int32 [B] on the GPU; word [vocab, C], pos [max_pos, C], type_emb [types, C],
+    gamma / beta [C] fp32 -> LayerNorm(word[ids] + pos[t] + type[tt]) as [B, T, C] of dtype, zeros at and behind lens[b]:
+    BERT's embeddings in one launch (evt_bert_embed_ln_rows).  Ids outside the table are clamped on the device; a row is
+    bit for bit the same in any batch and with any padding."""
+    if not torch.is_tensor(ids) or ids.dim() != 2 or not ids.is_cuda:
+        raise L.EvtError("bert_embed_ln_rows: ids [B, T] on the GPU expected")
+    B, T = ids.shape
+    _check_i32("bert_embed_ln_rows", "ids", ids, B * T, ids.device)
+    _check_i32("bert_embed_ln_rows", "lens", lens, B, ids.device)
+    if token_type_ids is not None:
+        _check_i32("bert_embed_ln_rows", "token_type_ids", token_type_ids, B * T, ids.device)
+    Cc = word.size(-1)
+    for name, t, rows in (("word", word, None), ("pos", pos, None), ("type_emb", type_emb, None), ("gamma", gamma, 1),
+                          ("beta", beta, 1)):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != ids.device or not t.is_contiguous()
+                or t.size(-1) != Cc or t.dim() != (1 if rows else 2) or t.data_ptr() % 16):
+            raise L.EvtError(f"bert_embed_ln_rows: {name} must be contiguous, 16-byte aligned float32 [.., {Cc}] on {ids.device}")
+    if B < 1 or T < 1 or T > pos.size(0) or Cc % 4 or not 4 <= Cc <= 8192:
+        raise L.EvtError(f"bert_embed_ln_rows: ids {tuple(ids.shape)} with tables of {pos.size(0)} positions x {Cc} are not served")
+    out = torch.empty(B, T, Cc, dtype=dtype, device=ids.device)
+    L.check(_rows_entry("evt_bert_embed_ln_rows", EMBED_ARGTYPES)(
+        L.dt_code(dtype), ids.data_ptr(), None if token_type_ids is None else token_type_ids.data_ptr(), lens.data_ptr(), B, T,
+        word.data_ptr(), word.size(0), pos.data_ptr(), pos.size(0), type_emb.data_ptr(), type_emb.size(0), gamma.data_ptr(),
+        beta.data_ptr(), float(eps), Cc, out.data_ptr(), L.stream_ptr()), "evt_bert_embed_ln_rows")
+    return out
+
+
 def add_layernorm(x, r, gamma, beta, eps):
     """LayerNorm(x + r) over the last axis (r may be None): evt_add_layernorm_fwd, statistics discarded"""
     x = x.contiguous()

@@ -208,9 +208,11 @@ def lib():
         _lib.evt_last_kernel_tag.restype = C.c_char_p
         _lib.evt_resunit_bwd_ws_floats.restype = C.c_int64
         _lib.evt_debug_kernel_tags.restype = None
-        # the ragged (inference) entry points of the vocoder and of the clip front end: both builds export them, a library without them fails here
+        # the ragged (inference) entry points of the vocoder, of the clip front end and of the two ends of BERT: both builds
+        # export them, a library without them fails here
         for name in ("evt_resunit_fwd_multi_lens", "evt_resunit_wide_fwd_lens", "evt_mask_tail", "evt_resample_rows",
-                     "evt_resample_pack_rows", "evt_hubert_front_rows", "evt_clip_rescale_rows"):
+                     "evt_resample_pack_rows", "evt_hubert_front_rows", "evt_clip_rescale_rows", "evt_phone_expand_rows",
+                     "evt_bert_embed_ln_rows"):
             getattr(_lib, name).restype = C.c_int
         _lib.evt_hubert_front_ws_floats.restype = C.c_int64
     return _lib

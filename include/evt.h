@@ -956,6 +956,45 @@ int evt_hubert_front_rows(int32_t dtype, const float* wav, const int32_t* lens, 
 int evt_clip_rescale_rows(const float* x, const int32_t* lens, int32_t nseq, int32_t N, float* f, int16_t* q, float* peak,
                           void* stream);
 
+/* The output end of Chinese-RoBERTa's phone-level features for a group of sentences: a transposing gather, one launch.
+ *   h [B][T][C] of dtype, 16-byte aligned; src device int32 [total]: for every output column the flat token row b * T + t
+ *   it copies, or -1 for a column of zeros (a value outside [-1, B * T) is taken as -1 on the device, never read);
+ *   item_off device int32 [n_items + 1]: item i owns columns item_off[i] .. item_off[i + 1] - 1, n_i of them (0 is legal).
+ *   out, packed, of out_dtype (fp32 or the build's 16-bit type, rounded to nearest even): item i is a contiguous [C][n_i]
+ *   block at element C * item_off[i],
+ *     out[C * item_off[i] + c * n_i + (p - item_off[i])] = h[src[p]][c], or 0.
+ *   Every element of out[0, C * total) that belongs to an item is written once, nothing else is; token rows that no
+ *   column names are never read.  item_off is expected ascending from 0 to total; every entry is clamped into
+ *   [previous end, total] on the device, so a wrong one cannot send a store outside out.
+ * A block owns 64 consecutive columns of one item (a tile never crosses an item) and 64 channels: 16-byte reads along c,
+ * an LDS tile of 65-word rows (both sides at most 2-way conflicted), stores of 64 consecutive columns per wave.  Plain
+ * vector stores, no atomics, no host synchronisation: legal in a captured graph.
+ * EVT_EINVAL (nothing launched) for a NULL h / item_off (src / out when total > 0), B, T or n_items <= 0, n_items > 65535,
+ * B * T >= 2^31, C outside 8 .. 4096 or not a multiple of 8, total < 0, h not 16-byte aligned; EVT_ENOTSUP for a dtype the
+ * build does not serve.  total == 0 is EVT_OK without a launch. */
+int evt_phone_expand_rows(int32_t dtype, const void* h, int32_t B, int32_t T, int32_t C, const int32_t* src,
+                          const int32_t* item_off, int32_t n_items, int32_t total, int32_t out_dtype, void* out,
+                          void* stream);
+
+/* The input end: BERT's embedding sum and its LayerNorm for a right-padded group of sentences, one launch.
+ *   ids int32 [B][T]; tt int32 [B][T] token types or NULL (all 0); lens device int32 [B], row b has
+ *   min(max(lens[b], 0), T) live tokens; word fp32 [vocab][C], pos fp32 [max_pos][C], type fp32 [types][C], gamma, beta
+ *   fp32 [C], all 16-byte aligned.
+ *     v[c]         = (word[id][c] + pos[t][c]) + type[ty][c]          fp32; id, ty clamped into their tables on the device
+ *     mean         = sum_c v / C;  var = sum_c (v - mean)^2 / C       two passes
+ *     out[b][t][c] = (v - mean) / sqrt(var + eps) * gamma[c] + beta[c]   t <  lens[b], rounded once to dtype
+ *     out[b][t][:] = 0                                                   t >= lens[b]  (ids there are not read)
+ * One wave per token row; lane l adds channels 4 l + 256 i in ascending i, four at a time as (a + b) + (c + d), the wave sum
+ * is the xor butterfly 32, 16, .., 1: the order depends on C alone, so a row is bit for bit the same for any B and any
+ * T >= lens[b].  No host synchronisation.
+ * EVT_EINVAL (nothing launched) for a NULL pointer other than tt, B, T, vocab or types <= 0, T > max_pos, B * T >= 2^31, C
+ * outside 4 .. 8192 or not a multiple of 4, eps < 0 or NaN, a table or out not 16-byte aligned; EVT_ENOTSUP for a dtype the
+ * build does not serve. */
+int evt_bert_embed_ln_rows(int32_t dtype, const int32_t* ids, const int32_t* tt, const int32_t* lens, int32_t B, int32_t T,
+                           const float* word, int32_t vocab, const float* pos, int32_t max_pos, const float* type,
+                           int32_t types, const float* gamma, const float* beta, float eps, int32_t C, void* out,
+                           void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
