@@ -396,6 +396,64 @@ __global__ void glu_dropout_res_bwd(const T* h, const TR* dy, float p, const uns
   }
 }
 
+// ---- the style encoder on a RAGGED batch of references (inference, no dropout): the two chains above with the dead tail of
+// every row written as exact zeros, and the mean over a row's live frames.  The reference's module convolves over a tensor
+// that ends at the clip's end, so whatever has a footprint over time must see zeros behind lens[s].
+// x [nseq][L][C]; element i lives iff its frame (i / C) % L < lens[s].  The live value is the p = 0 form of mish_dropout_fwd.
+template <typename T, typename TY>
+__global__ void mish_rows_fwd(const T* x, const int* lens, int L, int C, TY* y, long n) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / C;
+    const long s = row / L;
+    const bool live = (int)(row - s * L) < lens[s];
+    y[i] = live ? from_f<TY>(mish_f(to_f<T>(x[i]))) : from_f<TY>(0.f);
+  }
+}
+// the p = 0 form of glu_dropout_res_fwd.  p, seed_dev and site stay run-time arguments (0, NULL, 0 from the entry) and the live
+// value is that kernel's expression word for word, so that the compiler contracts product and sum here as it does there:
+// the two have to agree bit for bit (tests/test_style_rows_gpu.py).  h and res are not read in a dead frame.
+template <typename T, typename TR>
+__global__ void glu_res_rows_fwd(const T* h, const TR* res, float p, const unsigned* seed_dev, unsigned site, const int* lens,
+                                 int L, TR* y, long rows, int C) {
+  const DropCfg dc = drop_cfg(p, seed_dev, site);
+  const long n = rows * C;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / C;
+    const int c = (int)(i - row * C);
+    const long s = row / L;
+    if ((int)(row - s * L) < lens[s]) {
+      const float sg = 1.f / (1.f + __expf(-to_f<T>(h[row * 2 * C + C + c])));
+      y[i] = from_f<TR>(to_f<TR>(res[i]) + to_f<T>(h[row * 2 * C + c]) * sg * drop_mult(dc, (unsigned long)i));
+    } else {
+      y[i] = from_f<TR>(0.f);
+    }
+  }
+}
+// out[s][c] = sum_{t < n_s} x[s][t][c] / n_s.  Grid (ceil(C / 64), nseq), 4 waves: lane = channel, wave v adds the frames
+// 64 k + v, 64 k + v + 4, ... of chunk k in ascending order; the four partials meet in LDS as (p0 + p1) + (p2 + p3) and the
+// chunk sums are added in ascending k.  Nothing but n_s enters the order.
+template <typename T>
+__global__ __launch_bounds__(256) void mean_rows_kernel(const T* __restrict__ x, const int* __restrict__ lens, int L, int C,
+                                                        float* __restrict__ out) {
+  __shared__ float part[4][64];
+  const int s = blockIdx.y, lane = threadIdx.x & 63, v = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const int n = min(max(lens[s], 0), L);
+  const T* xr = x + (long)s * L * C;
+  float acc = 0.f;
+  for (int t0 = 0; t0 < n; t0 += 64) {
+    const int t1 = min(t0 + 64, n);
+    float p = 0.f;
+    if (c < C)
+      for (int t = t0 + v; t < t1; t += 4) p += to_f<T>(xr[(long)t * C + c]);
+    part[v][lane] = p;
+    __syncthreads();
+    if (v == 0) acc += (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    __syncthreads();
+  }
+  if (v == 0 && c < C) out[(long)s * C + c] = n > 0 ? acc / (float)n : 0.f;
+}
+
 // ---- posterior encoder tail (src/easevoice/module/models.py:352-358):  stats = proj(h) * mask;  m, logs = split(stats);
 //      z = (m + eps * exp(logs)) * mask  -- mask, cast, split, exp, multiply, add, mask as one launch (and one backward) ----
 template <typename T>
@@ -626,6 +684,42 @@ int evt_glu_dropout_res_bwd(int32_t dtype, int32_t wide_dtype, const void* h, co
     hipLaunchKernelGGL((glu_dropout_res_bwd<T, TR>), ew_grid(rows * C), dim3(256), 0, st, (const T*)h, (const TR*)dy, p,
                        seed_dev, site, (T*)dh, (long)rows, C);
   });
+}
+
+int evt_mish_rows_fwd(int32_t dtype, int32_t wide_dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t L,
+                      int32_t C, void* y, void* stream) {
+  if (!x || !lens || !y || nseq <= 0 || L <= 0 || C <= 0) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long n = (long)nseq * L * C;
+  return mixed_dispatch(dtype, wide_dtype, [&](auto* t, auto* tr) {
+    EVT_TT(t, tr);
+    hipLaunchKernelGGL((mish_rows_fwd<T, TR>), ew_grid(n), dim3(256), 0, st, (const T*)x, lens, L, C, (TR*)y, n);
+  });
+}
+
+int evt_glu_res_rows_fwd(int32_t dtype, int32_t wide_dtype, const void* h, const void* res, const int32_t* lens,
+                         int32_t nseq, int32_t L, int32_t C, void* y, void* stream) {
+  if (!h || !res || !lens || !y || nseq <= 0 || L <= 0 || C <= 0) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long rows = (long)nseq * L;
+  return mixed_dispatch(dtype, wide_dtype, [&](auto* t, auto* tr) {
+    EVT_TT(t, tr);
+    hipLaunchKernelGGL((glu_res_rows_fwd<T, TR>), ew_grid(rows * C), dim3(256), 0, st, (const T*)h, (const TR*)res, 0.f,
+                       (const unsigned*)nullptr, 0u, lens, L, (TR*)y, rows, C);
+  });
+}
+
+int evt_mean_rows(int32_t dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t L, int32_t C, float* out,
+                  void* stream) {
+  if (!x || !lens || !out || nseq <= 0 || nseq > 65535 || L <= 0 || C <= 0) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((C + 63) / 64, nseq);
+  if (dtype == EVT_DT_HALF)
+    hipLaunchKernelGGL(mean_rows_kernel<h16_t>, grid, dim3(256), 0, st, (const h16_t*)x, lens, L, C, out);
+  else if (dtype == EVT_DT_F32)
+    hipLaunchKernelGGL(mean_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)x, lens, L, C, out);
+  else return EVT_EINVAL;
+  return evt_check_launch();
 }
 
 int evt_coupling_flip_fwd(int32_t dtype, const float* x, const void* stats, const int32_t* lens, int32_t rows_per_seq,

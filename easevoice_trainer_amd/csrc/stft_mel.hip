@@ -176,9 +176,101 @@ __global__ __launch_bounds__(256) void mel_bwd_kernel(const float* dmel, const f
   }
 }
 
+// ---- reference clips of a ragged batch -> linear spectrograms (the reference's _get_ref_spec, inference/tts.py:390-409)
+// one block per row: the maximum is order-free; a NaN anywhere in the live part makes the peak NaN (as torch's abs().max())
+__global__ __launch_bounds__(1024) void ref_peak_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens, int N,
+                                                        float* __restrict__ peak) {
+  __shared__ float red[16];
+  __shared__ int bad[16];
+  const int s = blockIdx.x;
+  const int n = min(max(lens[s], 0), N);
+  const float* xr = x + (long)s * N;
+  float m = 0.f;
+  int nan = 0;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const float v = xr[i];
+    nan |= v != v;
+    m = fmaxf(m, fabsf(v));
+  }
+  m = wave_reduce_max(m);
+  nan = __any(nan);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = m, bad[wave] = nan;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 16; ++k) m = fmaxf(m, red[k]), nan |= bad[k];
+    peak[s] = nan ? __int_as_float(0x7fc00000) : m;
+  }
+}
+
+// frames of a clip of n samples: 0 where the reflect padding (pad < n) or the first frame does not fit
+__host__ __device__ __forceinline__ int ref_frames(int n, int pad, int hop) {
+  return (n > pad && n + 2 * pad >= NFFT) ? (n + 2 * pad - NFFT) / hop + 1 : 0;
+}
+
+// grid (Fmax, nseq): block (f, s) is frame f of row s, channels-last out[s][f][0 .. bins).  The magnitudes go through LDS so
+// that a frame leaves as consecutive 16-byte stores (bins % 4 == 0: every frame's base is 16-byte aligned), 4-byte ones
+// otherwise; a frame behind the row's end is stored as zeros the same way.
+__global__ __launch_bounds__(256) void ref_spec_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens,
+                                                       const float* __restrict__ peak, const float* __restrict__ window,
+                                                       float* __restrict__ out, int N, int hop, int bins) {
+  __shared__ cplx tw[NFFT / 2];
+  __shared__ cplx ex[NFFT];
+  __shared__ __attribute__((aligned(16))) float mag[NBIN + 3];
+  const int t = threadIdx.x;
+  const int f = blockIdx.x, seq = blockIdx.y;
+  const int pad = (NFFT - hop) / 2;
+  const int n = min(max(lens[seq], 0), N);
+  float* o = out + ((long)seq * gridDim.x + f) * bins;
+  const bool live = f < ref_frames(n, pad, hop);      // block-uniform
+  if (live) {
+    build_twiddles(tw, t);
+    const float pk = peak[seq];
+    const bool scale = pk > 1.f;                       // false for a NaN peak
+    const float den = fminf(2.f, pk);
+    const float* xr = x + (long)seq * N;
+    float* xs = reinterpret_cast<float*>(ex);
+    for (int i = t; i < NFFT; i += 256) {
+      float v = xr[reflect_index(f * hop + i, pad, n)];
+      if (scale) v = __fdiv_rn(v, den);                // audio /= min(2, maxx): a division rounded on its own
+      xs[i] = v * window[i];
+    }
+    __syncthreads();
+    cplx v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = {xs[__brev((unsigned)(c * 256 + t)) >> 21], 0.f};
+    fft2048(v, tw, ex, t);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      const int e = c * 256 + t;
+      if (e < NBIN) mag[e] = sqrtf(v[c].x * v[c].x + v[c].y * v[c].y + 1e-6f);
+    }
+    __syncthreads();
+  }
+  if ((bins & 3) == 0) {
+    for (int e = 4 * t; e < bins; e += 1024)
+      *reinterpret_cast<float4*>(o + e) = live ? *reinterpret_cast<const float4*>(mag + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    for (int e = t; e < bins; e += 256) o[e] = live ? mag[e] : 0.f;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int evt_ref_spec_rows(const float* x, const int32_t* lens, int32_t nseq, int32_t N, const float* window, int32_t n_fft,
+                      int32_t hop, int32_t bins, float* out, float* peak, void* stream) {
+  if (!x || !lens || !window || !out || !peak || nseq <= 0 || nseq > 65535 || N <= 0) return EVT_EINVAL;
+  if (n_fft != NFFT || hop <= 0 || hop > n_fft || bins < 1 || bins > NBIN) return EVT_EINVAL;
+  if ((uintptr_t)out & 15) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ref_peak_kernel, dim3(nseq), dim3(1024), 0, st, x, lens, N, peak);
+  const int fmax = ref_frames(N, (n_fft - hop) / 2, hop);
+  if (fmax > 0)
+    hipLaunchKernelGGL(ref_spec_kernel, dim3(fmax, nseq), dim3(256), 0, st, x, lens, peak, window, out, N, hop, bins);
+  return evt_check_launch();
+}
 
 int64_t evt_mel_workspace_floats(int32_t nseq, int32_t wav_len, int32_t n_fft, int32_t hop, int32_t n_mels) {
   if (hop <= 0) return 0;  // no frames to hold: evt_mel_fwd / evt_mel_bwd refuse this geometry

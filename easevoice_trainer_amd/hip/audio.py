@@ -152,3 +152,50 @@ def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, inter
         _conv._t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
     return PackedAudio(data, offsets, lengths, int(out_rate), gap)
 
+
+REF_NFFT = 2048        # the transform of csrc/stft_mel.hip
+
+
+def ref_frames(n, hop=640):
+    """frames of a clip of n samples (include/evt.h): n // 640 at hop 640, 0 for a clip the reflect padding refuses"""
+    pad = (REF_NFFT - hop) // 2
+    return (n + 2 * pad - REF_NFFT) // hop + 1 if n > pad and n + 2 * pad >= REF_NFFT else 0
+
+
+def ref_spec_rows(x, lens, hop=640, bins=704, lens_dev=None):
+    """The reference's _get_ref_spec (inference/tts.py:390-409) for a ragged batch of reference clips, two launches and no
+    host synchronisation (csrc/stft_mel.hip::evt_ref_spec_rows; include/evt.h has the operator's definition).  x [nseq, N]
+    contiguous fp32 on the GPU (or one clip [N]), row s with lens[s] live samples, never read behind them; lens: a sequence
+    of ints, uploaded unless lens_dev (the same values as an int32 tensor on x's device) is given.
+    -> (spec fp32 [nseq, Fmax, bins] channels-last -- the first `bins` bins of sqrt(re^2 + im^2 + 1e-6) of the clip divided
+    by min(2, peak) where its peak exceeds 1, exact zeros behind a row's frames --, frames: list of F_s, peak fp32 [nseq]).
+    A row of at most pad = (2048 - hop) // 2 samples is an EvtError, as torch's reflect padding refuses it."""
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.size(0) < 1 or x.size(1) < 1:
+        raise L.EvtError(f"ref_spec_rows takes contiguous fp32 rows [nseq, N] on the GPU, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    nseq, n = x.size(0), x.size(1)
+    lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    hop, bins = int(hop), int(bins)
+    if hop <= 0 or hop > REF_NFFT or not 1 <= bins <= REF_NFFT // 2 + 1:
+        raise L.EvtError(f"ref_spec_rows: hop in [1, {REF_NFFT}] and bins in [1, {REF_NFFT // 2 + 1}] expected, got {hop} and {bins}")
+    if len(lens) != nseq or max(lens) > n:
+        raise L.EvtError(f"ref_spec_rows: {nseq} lengths of at most {n} samples expected, got {lens}")
+    frames = [ref_frames(v, hop) for v in lens]
+    if min(frames) < 1:
+        raise L.EvtError(f"ref_spec_rows: clip {frames.index(min(frames))} has {lens[frames.index(min(frames))]} samples, "
+                         f"too few for the reflect padding of {(REF_NFFT - hop) // 2} and one frame")
+    if lens_dev is None:
+        lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+    _conv._check_lens(x, lens_dev, 1)
+    from ..module.mel_processing import _window
+
+    window = _window(REF_NFFT, x.device)              # the tensor spectrogram_torch hands its kernel
+    spec = torch.empty((nseq, ref_frames(n, hop), bins), dtype=torch.float32, device=x.device)
+    peak = torch.empty(nseq, dtype=torch.float32, device=x.device)
+    e0 = _conv._t0()
+    L.check(L.lib().evt_ref_spec_rows(L.ptr(x), L.ptr(lens_dev), nseq, n, L.ptr(window), REF_NFFT, hop, bins,
+                                      L.ptr(spec), L.ptr(peak), L.stream_ptr()), "evt_ref_spec_rows")
+    if e0 is not None:
+        _conv._t1_elt(e0, "ref_spec_kernel", (x.numel() + spec.numel()) * 4, None)
+    return spec, frames, peak

@@ -437,6 +437,54 @@ def glu_dropout_res(h, res, p, site):
     return GluDropoutResFn.apply(h, res, float(p), int(site))
 
 
+def _rows_lens(x, lens):
+    if (x.dim() != 3 or not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
+            or lens.numel() != x.size(0) or not lens.is_contiguous()):
+        raise L.EvtError(f"ragged style encoder: rows [B, T, C] and a contiguous int32 [B] lens on {x.device} expected, got "
+                         f"{tuple(x.shape)} and {lens.dtype if torch.is_tensor(lens) else type(lens)}")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise L.EvtError("the ragged (lens) forms of the style encoder are inference only: run them under torch.no_grad()")
+
+
+def mish_rows(x, lens, out_dtype=None):
+    """mish_dropout at p = 0 on a ragged batch x [B, T, C]: frames t >= lens[b] come out as exact zeros (one launch,
+    evt_mish_rows_fwd); no grad"""
+    x = x.contiguous()
+    _rows_lens(x, lens)
+    y = torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
+    L.check(L.lib().evt_mish_rows_fwd(L.dt_of(x), L.dt_of(y), L.ptr(x), L.ptr(lens), x.size(0), x.size(1), x.size(2),
+                                      L.ptr(y), L.stream_ptr()), "evt_mish_rows_fwd")
+    return y
+
+
+def glu_res_rows(h, res, lens):
+    """glu_dropout_res at p = 0 on a ragged batch h [B, T, 2C], res [B, T, C]: frames t >= lens[b] come out as exact zeros
+    (one launch, evt_glu_res_rows_fwd); no grad"""
+    h = h.contiguous()
+    if res.dtype not in (h.dtype, torch.float32):
+        res = res.to(h.dtype)
+    res = res.contiguous()
+    _rows_lens(h, lens)
+    Cc = h.size(-1) // 2
+    if tuple(res.shape) != (h.size(0), h.size(1), Cc):
+        raise L.EvtError(f"glu_res_rows: res {tuple(res.shape)} does not go with h {tuple(h.shape)}")
+    y = torch.empty_like(res)
+    L.check(L.lib().evt_glu_res_rows_fwd(L.dt_of(h), L.dt_of(res), L.ptr(h), L.ptr(res), L.ptr(lens), h.size(0), h.size(1),
+                                         Cc, L.ptr(y), L.stream_ptr()), "evt_glu_res_rows_fwd")
+    return y
+
+
+def mean_rows(x, lens):
+    """x [B, T, C] (fp32 or the library's 16-bit type), lens int32 [B] -> fp32 [B, C]: the mean over every row's live frames
+    in fp32, in an order that depends on the row's length alone (evt_mean_rows); a row of length 0 gives zeros"""
+    x = x.contiguous()
+    _rows_lens(x, lens)
+    out = torch.empty((x.size(0), x.size(2)), dtype=torch.float32, device=x.device)
+    L.check(L.lib().evt_mean_rows(L.dt_of(x), L.ptr(x), L.ptr(lens), x.size(0), x.size(1), x.size(2), L.ptr(out),
+                                  L.stream_ptr()), "evt_mean_rows")
+    return out
+
+
 class ReparamFn(torch.autograd.Function):
     """posterior encoder tail (models.py:352-358): stats [B, T, 2C] (the projection's output, compute dtype), eps [B, T, C]
     fp32, lens -> z, m, logs fp32 (masked) in one launch; one launch back"""

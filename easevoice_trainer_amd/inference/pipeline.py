@@ -83,18 +83,22 @@ def _finish(voice, wav, out):
     return resample_pack(wav, [wav.numel()], 1, rate, out.get("out_rate", rate), out.get("out_format", "float32")).row(0)
 
 
-def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None, out=None):
+def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None, out=None, styles=None):
     """items: [(fragment index, y, idx)] of one poll, at most s2_batch of them -> their waveforms, through ONE decode_batch
     call (a single fragment: the decode call of the one-by-one path).  speeds: None, or one speed per fragment of the
     whole request (fragment_speed); decode_batch gets the group's values only when one of them is not 1.  out: the
     out_rate / out_format keywords that were set; decode_batch gets them only then, and its PackedAudio is handed out row
-    by row"""
+    by row.  styles: None, or one [1, gin] style vector per fragment of the whole request (fragment_style): the group then
+    goes through decode_batch(refer=None, style=<its rows stacked, in order>), a single fragment through decode(style=...)"""
     out = out or {}
     with torch.no_grad():
         if len(items) == 1:
             r, y, idx = items[0]
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             one = 1.0 if speeds is None else speeds[r]
+            if styles is not None:
+                return [_finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), None, speed=one,
+                                                          style=styles[r], **kw)[0, 0, :], out)]
             return [_finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :],
                             out)]
         if speeds is not None and any(speeds[r] != 1.0 for r, _y, _idx in items):
@@ -103,6 +107,10 @@ def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None, out=N
         phones = [batch_phones[r].to(dev) for r, _y, _idx in items]
         codes = torch.nn.utils.rnn.pad_sequence(sems, batch_first=True).unsqueeze(0)
         text = torch.nn.utils.rnn.pad_sequence(phones, batch_first=True)
+        if styles is not None:
+            got = voice.model.decode_batch(codes, [int(t.numel()) for t in sems], text, [int(t.numel()) for t in phones],
+                                           None, style=torch.cat([styles[r] for r, _y, _idx in items], 0), **kw, **out)
+            return [got.row(b) for b in range(len(items))] if out else got
         # one entry per row, all the same object: decode_batch encodes the shared reference(s) once
         got = voice.model.decode_batch(codes, [int(t.numel()) for t in sems], text, [int(t.numel()) for t in phones],
                                        [refer] * len(items), **kw, **out)
@@ -112,7 +120,8 @@ def _decode_group(voice, dev, batch_phones, refer, kw, items, speeds=None, out=N
 def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
-                      choose=None, wide=False, s2_batch=1, fragment_speed=None, out_rate=None, out_format=None):
+                      choose=None, wide=False, s2_batch=1, fragment_speed=None, out_rate=None, out_format=None,
+                      fragment_style=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -147,7 +156,12 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     tensor at out_rate Hz (None: the model's rate) in out_format "int16" or "float32" (None: "float32") -- the operator of
     hip/audio.py.  A group's decode_batch call gets the keywords that were set (and no others) and finishes its rows with
     one more launch; a fragment decoded alone goes through decode and then resample_pack with one row, which gives the
-    same bits."""
+    same bits.
+    fragment_style: None (every fragment speaks with the shared refer_specs: the calls above, unchanged), or a list with one
+    precomputed voice per fragment -- a [1, gin] style vector (SynthesizerTrn.style_rows / _style) or an
+    inference/voice.py::EnrolledVoice --, the companion of a per-fragment prompt_semantic: fragment r is decoded with voice
+    r.  refer_specs may then be empty; a group goes through decode_batch(refer=None, style=<the group's rows stacked>),
+    whose rows may all differ, a fragment decoded alone through decode(refer=None, style=...)."""
     model, dev = t2s.model, t2s.device
     out = {k: v for k, v in (("out_rate", out_rate), ("out_format", out_format)) if v is not None}
     s2_batch = int(s2_batch)
@@ -171,6 +185,10 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         if len(fragment_speed) != n:
             raise ValueError(f"fragment_speed has {len(fragment_speed)} entries for {n} fragments")
         fragment_speed = [float(v) for v in fragment_speed]
+    if fragment_style is not None:
+        if len(fragment_style) != n:
+            raise ValueError(f"fragment_style has {len(fragment_style)} entries for {n} fragments")
+        fragment_style = [getattr(v, "style", v).to(dev).reshape(1, -1) for v in fragment_style]
     reqs = [(p.to(dev), b.to(dev), pr) for p, b, pr in zip(all_phoneme_ids, all_bert_features, prompts)]
     if fragment_sampling is not None:
         reqs = [q if fs is None else (*q, dict(fs)) for q, fs in zip(reqs, fragment_sampling)]
@@ -181,6 +199,9 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
         with torch.no_grad():
             sem = y[-idx:].unsqueeze(0).unsqueeze(0)
             one = speed_factor if fragment_speed is None else fragment_speed[r]
+            if fragment_style is not None:
+                return _finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), None, speed=one,
+                                                         style=fragment_style[r], **kw)[0, 0, :], out)
             return _finish(voice, voice.model.decode(sem, batch_phones[r].to(dev).unsqueeze(0), refer, speed=one, **kw)[0, 0, :],
                            out)
 
@@ -234,7 +255,7 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                     take += 1
                 chunk, ready = ready[:take], ready[take:]
                 wavs = iter(_decode_group(voice, dev, batch_phones, refer, kw, [c for c in chunk if c[1] is not None],
-                                          fragment_speed, out))
+                                          fragment_speed, out, fragment_style))
                 for r, y, _idx in chunk:
                     yield r, (None if y is None else next(wavs))
         return
@@ -268,7 +289,8 @@ def synthesize_pcm(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features,
     the model's rate.  It drains synthesize_stream(out_rate=rate, out_format="int16", **stream_kwargs) -- s2_batch, slots,
     fragment_speed, control ... as there --, so conversion and resampling happen on the device, one launch per group;
     fragments that come back cancelled (or preempted) are left out together with their interval.  The pieces are joined
-    on the device and leave it in ONE device -> host copy."""
+    on the device and leave it in ONE device -> host copy.  fragment_style (one voice per fragment, refer_specs may be
+    empty) goes through as the other stream keywords do."""
     rate = int(getattr(voice.model, "sampling_rate", 32000) if out_rate is None else out_rate)
     if fragment_interval < 0:
         raise ValueError(f"fragment_interval = {fragment_interval} must be >= 0")

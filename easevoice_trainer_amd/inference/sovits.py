@@ -37,25 +37,40 @@ class SoVITSVoice:
         self.model, self.device, self.dtype = net, torch.device(device), dtype
 
     @torch.no_grad()
-    def decode(self, codes, text, refer, noise_scale=0.5, speed=1, noise=None):
+    def decode(self, codes, text, refer, noise_scale=0.5, speed=1, noise=None, style=None):
+        """style: a precomputed voice [1, gin] (style_rows, inference/voice.py::enroll_voices) in place of refer (then None)"""
         L.set_half(self.dtype)
         mv = lambda t: t.to(self.device)
+        if style is not None:
+            return self.model.decode(mv(codes), mv(text), refer, noise_scale=noise_scale, speed=speed,
+                                     noise=None if noise is None else mv(noise), style=style)
         refer = [mv(r) for r in refer] if isinstance(refer, (list, tuple)) else mv(refer)
         return self.model.decode(mv(codes), mv(text), refer, noise_scale=noise_scale, speed=speed,
                                  noise=None if noise is None else mv(noise))
 
     @torch.no_grad()
     def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1, out_rate=None,
-                     out_format=None, interval=0.0):
+                     out_format=None, interval=0.0, style=None):
         """SynthesizerTrn.decode_batch: a ragged batch of fragments in one pass -> a list of B 1-D waveforms, row b what
         decode gives for fragment b alone (at speed, or at speed[b] where a sequence of B speeds is given); with out_rate /
-        out_format a hip.audio.PackedAudio: the rows at that rate and format in one device buffer"""
+        out_format a hip.audio.PackedAudio: the rows at that rate and format in one device buffer.  style: precomputed
+        voices [1, gin] or [B, gin] on the device in place of refer (then None)"""
         L.set_half(self.dtype)
         mv = lambda t: t.to(self.device)
-        mvr = lambda r: [mvr(e) for e in r] if isinstance(r, (list, tuple)) else mv(r)
+        mvr = lambda r: None if r is None else [mvr(e) for e in r] if isinstance(r, (list, tuple)) else mv(r)
+        if style is not None:
+            return self.model.decode_batch(mv(codes), code_lens, mv(text), text_lens, mvr(refer), noise_scale=noise_scale,
+                                           noise=None if noise is None else mv(noise), speed=speed, out_rate=out_rate,
+                                           out_format=out_format, interval=interval, style=style)
         return self.model.decode_batch(mv(codes), code_lens, mv(text), text_lens, mvr(refer), noise_scale=noise_scale,
                                        noise=None if noise is None else mv(noise), speed=speed, out_rate=out_rate,
                                        out_format=out_format, interval=interval)
+
+    @torch.no_grad()
+    def style_rows(self, spec_cl, lens):
+        """SynthesizerTrn.style_rows: a ragged batch of channels-last reference spectrograms -> [B, gin] in one pass"""
+        L.set_half(self.dtype)
+        return self.model.style_rows(spec_cl.to(self.device), lens)
 
     @torch.no_grad()
     def extract_latent(self, ssl):

@@ -342,6 +342,13 @@ class Conv1dGLU(nn.Module, _ComputeDtype):
         x1, x2 = torch.split(h, self.out_channels, dim=-1)
         return residual + self.dropout(x1 * torch.sigmoid(x2))
 
+    def forward_rows(self, x, lens):
+        """forward for a ragged batch in eval mode: x [B, T, C] with zeros behind lens[b] -> the same with zeros behind
+        lens[b] (the convolution saw the row end where the reference's unpadded tensor ends; hip/enc.py::glu_res_rows)"""
+        from ..hip.enc import glu_res_rows
+
+        return glu_res_rows(self.conv1(x.to(self.cd).contiguous()), x, lens)
+
 
 class StyleAttention(nn.Module):
     """modules.py:605-682 (MultiHeadAttention + ScaledDotProductAttention of the style encoder)."""
@@ -424,6 +431,42 @@ class MelStyleEncoder(nn.Module):
         x = self.fc(x)
         n = (~pad).sum(dim=1, keepdim=True)
         return x.masked_fill(pad.unsqueeze(-1), 0).sum(dim=1) / n
+
+    @torch.no_grad()
+    def forward_rows(self, x, lens):
+        """A ragged batch of references in one pass, eval mode only: x [B, Tmax, n_mel], lens int32 [B] on x's device (every
+        length in 1 .. Tmax) -> fp32 [B, style_vector_dim]; row b is what forward(x[b:b+1, :lens[b]], ones) computes for the
+        reference alone.  The reference's module convolves over an unmasked tensor that ends at the clip's end, so each of
+        the two k = 5 convolutions and the attention is handed zeros behind lens[b]: the activations in front of them write
+        the dead tail themselves (hip/enc.py::mish_rows / glu_res_rows), the attention masks the keys by lens as it does in
+        forward, and the mean is taken over the live frames in fp32 in a fixed order (hip/enc.py::mean_rows).
+        In a 16-bit bank the convolution dispatcher would pick its kernel by the batch's shape (from 32 tiles of 64 x 64 on
+        conv_ring<2, 2, 4> of csrc/conv_deep.hip takes the k = 5 convolutions and fc, below that the generic implicit GEMM
+        of csrc/conv1d.hip does; up to 16 rows a 1 x 1 layer goes to rows16_gemm), and a voice's vector would depend on
+        which clips it was enrolled with.  The pass therefore pins the bank to the generic implicit GEMM (EVT_IMPL_IGEMM, an
+        existing kernel) for its own layers and puts the bank's setting back."""
+        if self.training:
+            raise L.EvtError("MelStyleEncoder.forward_rows is the inference form: call eval() first")
+        if not x.is_cuda:
+            raise L.EvtError("MelStyleEncoder.forward_rows runs on the library's kernels: the input must be on the GPU")
+        from ..hip.enc import mean_rows, mish_rows
+
+        sp = self.spectral
+        slot = self.fc.fc._slot
+        bank = slot.bank if slot is not None else None
+        pin = bank is not None and L.is_half(bank.dtype) and bank.impl == L.IMPL_AUTO
+        if pin:
+            bank.impl = L.IMPL_IGEMM
+        try:
+            x = mish_rows(sp[0](x), lens)                          # feeds a projection: its dtype
+            x = mish_rows(sp[3](x), lens, torch.float32)           # the fp32 residual stream of `temporal`
+            for glu in self.temporal:
+                x = glu.forward_rows(x, lens)
+            x = self.slf_attn(x, lens)
+            return mean_rows(self.fc(x), lens)
+        finally:
+            if pin:
+                bank.impl = L.IMPL_AUTO
 
 
 # --------------------------------------------------------------------------------------------------
@@ -871,19 +914,21 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         return codes.transpose(0, 1)
 
     @torch.no_grad()
-    def decode(self, codes, text, refer, noise_scale=0.5, speed=1, noise=None):
+    def decode(self, codes, text, refer, noise_scale=0.5, speed=1, noise=None, style=None):
         """Inference: semantic codes [1, B, Tc] + phoneme ids [B, Tt] + reference spectrogram(s) [B, spec, Tr] (a list
         averages the style vectors) -> waveform [B, 1, T*hop] (models.py:974-1013): prior from the text/ssl encoder,
         z_p = m_p + noise*exp(logs_p)*noise_scale, the flow run in reverse, the HiFi-GAN generator over the whole
-        sequence.  `noise` ([B, inter, >=T]) injects the prior draw for deterministic parity runs."""
+        sequence.  `noise` ([B, inter, >=T]) injects the prior draw for deterministic parity runs.
+        style: a precomputed style vector [1, gin] (or [B, gin]) -- _style / style_rows -- used as ge in place of the style
+        pass; refer is then None (both given: EvtError)."""
         amp = self.cd in (torch.bfloat16, torch.float16)
         with torch.autocast("cuda", dtype=self.cd if amp else torch.bfloat16, enabled=amp):
             ges = []
-            for r in (refer if isinstance(refer, (list, tuple)) else [refer]):
+            for r in ([] if style is not None else refer if isinstance(refer, (list, tuple)) else [refer]):
                 r_cl = r.transpose(1, 2)
                 r_cl = r_cl if self.version == "v1" else r_cl[..., :704]
                 ges.append(self.ref_enc(r_cl, torch.ones(r_cl.size(0), r_cl.size(1), 1, device=r.device)))
-            ge = torch.stack(ges, 0).mean(0)
+            ge = torch.stack(ges, 0).mean(0) if style is None else self._given_style(style, refer, codes.size(1), codes.device)
             B, Tc = codes.size(1), codes.size(2)
             T = Tc * 2 if self.semantic_frame_rate == "25hz" else Tc
             y_lengths = torch.full((B,), T, dtype=torch.long, device=codes.device)
@@ -918,8 +963,42 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         return torch.stack(ges, 0).mean(0)
 
     @torch.no_grad()
+    def style_rows(self, spec_cl, lens):
+        """Style vectors of a ragged batch of reference spectrograms in ONE pass of the style encoder: spec_cl fp32
+        [B, Tmax, >= 704] channels-last (hip/audio.py::ref_spec_rows; v1: all spec_channels bins), lens: the rows' frame
+        counts (a sequence of ints, or an int32 tensor on spec_cl's device) -> [B, gin] in the dtype _style returns (fp32: the
+        sum of forward runs in fp32 under autocast too), row b what _style gives for reference b alone up to the order of
+        the mean's sum and, in 16-bit, to the convolution kernels the dispatcher picks for the batch's shape
+        (MelStyleEncoder.forward_rows).  The result
+        goes to decode / decode_batch as `style`."""
+        if spec_cl.dim() != 3 or spec_cl.dtype != torch.float32:
+            raise L.EvtError(f"style_rows takes fp32 spectrograms [B, Tmax, bins] (channels-last), got {spec_cl.dtype} {tuple(spec_cl.shape)}")
+        bins = spec_cl.size(2) if self.version == "v1" else 704
+        if spec_cl.size(2) < bins or (self.version == "v1" and bins != self.spec_channels):
+            raise L.EvtError(f"style_rows: the style encoder takes {bins} bins, the spectrograms have {spec_cl.size(2)}")
+        if not torch.is_tensor(lens):
+            lens = torch.tensor([int(v) for v in lens], dtype=torch.int32).to(spec_cl.device)
+        lens = lens.to(torch.int32).contiguous()
+        x = spec_cl if spec_cl.size(2) == bins else spec_cl[..., :bins].contiguous()
+        amp = self.cd in (torch.bfloat16, torch.float16)
+        with torch.autocast("cuda", dtype=self.cd if amp else torch.bfloat16, enabled=amp):
+            return self.ref_enc.forward_rows(x, lens)
+
+    def _given_style(self, style, refer, B, dev):
+        """the `style` keyword of decode / decode_batch -> ge [B, gin] on dev in the dtype _style returns"""
+        if refer is not None:
+            raise L.EvtError("decode: give either the reference spectrogram(s) `refer` or a precomputed `style`, not both")
+        if not torch.is_tensor(style) or style.dim() != 2 or style.size(1) != self.gin_channels or style.size(0) not in (1, B):
+            raise L.EvtError(f"decode: style must be [1, {self.gin_channels}] (shared) or [{B}, {self.gin_channels}] (one per "
+                             f"row), got {tuple(style.shape) if torch.is_tensor(style) else type(style)}")
+        if style.device != dev:
+            raise L.EvtError(f"decode: style lives on {style.device}, the batch on {dev}")
+        ge = style.to(torch.float32)                  # _style's dtype: the pooled mean leaves the style encoder in fp32
+        return ge.contiguous() if ge.size(0) == B else ge.expand(B, -1).contiguous()
+
+    @torch.no_grad()
     def decode_batch(self, codes, code_lens, text, text_lens, refer, noise_scale=0.5, noise=None, speed=1, out_rate=None,
-                     out_format=None, interval=0.0):
+                     out_format=None, interval=0.0, style=None):
         """decode for a RAGGED batch of fragments in one pass: codes [1, B, Tcmax] and text [B, Ttmax] right-padded,
         code_lens / text_lens [B] (tensors or sequences of ints).  refer: one reference spectrogram [1, spec, Tr] (or a
         list of them, averaged) shared by all rows, or a list of exactly B entries, one per row (a list of length B is
@@ -938,7 +1017,10 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         out_rate / out_format (both None: the list above, launch for launch): one evt_resample_pack_rows launch behind
         the vocoder takes its ragged rows to a hip.audio.PackedAudio -- one device buffer holding the rows in batch order at
         out_rate Hz (None: self.sampling_rate) as out_format "int16" or "float32" (None: "float32"), int(out_rate * interval)
-        zeros behind each; row(b) is what hip.audio.resample_pack gives for waveform b alone, bit for bit."""
+        zeros behind each; row(b) is what hip.audio.resample_pack gives for waveform b alone, bit for bit.
+        style (None: the pass above, launch for launch): precomputed style vectors [1, gin] (shared) or [B, gin] (one voice
+        per row) on the batch's device -- _style / style_rows -- used as ge in place of the style passes; refer is then
+        None.  Both given, a wrong shape or a wrong device: EvtError."""
         dev = codes.device
         if out_format is not None or out_rate is not None:
             from ..hip import audio
@@ -977,7 +1059,9 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         amp = self.cd in (torch.bfloat16, torch.float16)
         with torch.autocast("cuda", dtype=self.cd if amp else torch.bfloat16, enabled=amp):
             per_row = isinstance(refer, (list, tuple)) and len(refer) == B
-            if per_row:
+            if style is not None:
+                ge = self._given_style(style, refer, B, dev)
+            elif per_row:
                 seen = {}        # rows that name the same reference object share one pass of the style encoder
                 for r in refer:
                     if id(r) not in seen:

@@ -413,6 +413,27 @@ int evt_mel_bwd(const float* dmel, const float* window, const float* mel_basis, 
 /* workspace floats needed by evt_mel_fwd/bwd; 0 for hop <= 0 (which they refuse) */
 int64_t evt_mel_workspace_floats(int32_t nseq, int32_t wav_len, int32_t n_fft, int32_t hop, int32_t n_mels);
 
+/* Linear spectrograms of a RAGGED batch of reference clips: the reference's _get_ref_spec (inference/tts.py:390-409: peak,
+ * audio /= min(2, peak) where the peak exceeds 1, spectrogram_torch) for nseq clips at once, the FFT arithmetic of evt_mel_fwd.
+ *   x fp32 [nseq][N]; lens device int32 [nseq], row s has n_s = min(max(lens[s], 0), N) live samples and x is never read at or
+ *   behind them; window fp32 [n_fft]; n_fft = 2048; pad = (n_fft - hop) / 2.
+ *   Row s has F_s = (n_s + 2 pad - n_fft) / hop + 1 frames when n_s > pad and n_s + 2 pad >= n_fft, else 0 (n_s / 640 at hop
+ *   640); Fmax is the same count for n_s = N.
+ * Two launches on `stream`, no host synchronisation: legal in a captured graph.
+ *   peak[s] = max_{i < n_s} |x[s][i]|   (fp32 [nseq], an OUTPUT; NaN if the live part holds a NaN, 0 for an empty row)
+ *   v[i]    = peak[s] > 1 ? fdiv(x[s][i], min(2, peak[s])) : x[s][i]      the division rounded to fp32 on its own
+ *   frame f < F_s, sample j < n_fft:  q = f * hop + j - pad;  i = |q| for q < n_s, 2 (n_s - 1) - q from there on: the reflect
+ *   padding at the ROW's own ends;  X = DFT_2048(v[i] * window[j]);  out[s][f][k] = sqrt(re_k^2 + im_k^2 + 1e-6), k < bins
+ *   out[s][f][:] = 0  for F_s <= f < Fmax
+ * out fp32 channels-LAST [nseq][Fmax][bins], 1 <= bins <= n_fft / 2 + 1: only the first `bins` bins are stored (the style
+ * encoder takes 704).  Every element of out is written, no memset in front; 16-byte stores where bins is a multiple of 4.
+ * One block per (row, frame): neither nseq nor N enters the arithmetic, a row is bit for bit what nseq = 1 gives with any
+ * N >= n_s.  N so short that Fmax = 0: peak is written, out has no element.
+ * EVT_EINVAL (nothing launched) for a NULL pointer, nseq <= 0 or > 65535, N <= 0, n_fft != 2048, hop <= 0 or > n_fft, bins
+ * outside the range above, out not 16-byte aligned. */
+int evt_ref_spec_rows(const float* x, const int32_t* lens, int32_t nseq, int32_t N, const float* window, int32_t n_fft,
+                      int32_t hop, int32_t bins, float* out, float* peak, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Input front-end of the s2 step (no gradients).
  * ------------------------------------------------------------------------------------- */
@@ -656,6 +677,28 @@ int evt_glu_dropout_res_fwd(int32_t dtype, int32_t wide_dtype, const void* h, co
                             const uint32_t* seed_dev, uint32_t site, void* y, int64_t rows, int32_t C, void* stream);
 int evt_glu_dropout_res_bwd(int32_t dtype, int32_t wide_dtype, const void* h, const void* dy, float p,
                             const uint32_t* seed_dev, uint32_t site, void* dh, int64_t rows, int32_t C, void* stream);
+/* The style encoder on a RAGGED batch of references (inference: p = 0, forward only).  The reference's module convolves over
+ * a tensor that ends at the clip's end, so every consumer with a footprint over time has to see zeros behind a row's length.
+ * x / h / res / y [nseq][L][.], lens device int32 [nseq]; frame t of row s is live iff t < lens[s].
+ *   evt_mish_rows_fwd:    y[s][t][c] = mish(x[s][t][c])                            live,  0 otherwise;  x, y [nseq][L][C]
+ *   evt_glu_res_rows_fwd: y[s][t][c] = res[s][t][c] + h[s][t][c] * sigmoid(h[s][t][C + c])  live,  0 otherwise;  h [nseq][L][2C]
+ * A live element is bit for bit what evt_mish_dropout_fwd / evt_glu_dropout_res_fwd give at p = 0, a dead one an exact zero
+ * whatever x / h / res hold there (they are not read): one launch where that entry and evt_mask_tail were two.  dtype /
+ * wide_dtype as above.  EVT_EINVAL for a NULL pointer, a size <= 0 or a pair of dtypes that is not served.
+ *   evt_mean_rows: out[s][c] = (sum_{t < n_s} x[s][t][c]) / (float)n_s, n_s = min(max(lens[s], 0), L); x [nseq][L][C] of dtype,
+ *   out fp32 [nseq][C], zeros for n_s = 0.  fp32 throughout.  Summation order: EVT_MEAN_ROWS_CHUNK = 64 consecutive frames
+ *   counted from the row's frame 0 form a chunk; inside chunk k the frames 64 k + v, 64 k + v + 4, ... (v = 0 .. 3) are added
+ *   in ascending order into four partial sums starting from 0, combined as (p0 + p1) + (p2 + p3); the chunk sums are added in
+ *   ascending k, starting from 0 (the scheme of evt_hubert_front_rows, without a workspace).  Nothing but n_s enters: row s is
+ *   bit for bit what nseq = 1 gives with any L >= n_s.  EVT_EINVAL for a NULL pointer, nseq <= 0 or > 65535, L or C <= 0, a
+ *   dtype the build does not serve. */
+#define EVT_MEAN_ROWS_CHUNK 64
+int evt_mish_rows_fwd(int32_t dtype, int32_t wide_dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t L,
+                      int32_t C, void* y, void* stream);
+int evt_glu_res_rows_fwd(int32_t dtype, int32_t wide_dtype, const void* h, const void* res, const int32_t* lens,
+                         int32_t nseq, int32_t L, int32_t C, void* y, void* stream);
+int evt_mean_rows(int32_t dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t L, int32_t C, float* out,
+                  void* stream);
 /* Tail of the posterior encoder (src/easevoice/module/models.py:352-358): with stats [rows][2C] the projection's output,
  *   m = stats[:, :C] * mask, logs = stats[:, C:] * mask, z = (m + eps * exp(logs)) * mask     (fp32 [rows][C] each)
  * and its backward: dstats from dz / dm / dlogs (each may be NULL), eps and the saved logs. */
