@@ -1391,12 +1391,12 @@ int evt_conv1d_bwd_weight(const evt_conv1d_params* c, const void* x, const void*
   return evt_conv1d_bwd_weight_parts(c, x, dy, y, dw, dbias, nullptr, stream);
 }
 
-int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
-                                float* dbias, evt_wgrad_parts* sp, void* stream) {
+// argument checks of a weight-gradient call (sp->used is cleared on the way)
+static int wg_check_args(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
+                         evt_wgrad_parts* sp) {
   int rc = valid(c);
   if (rc) return rc;
   if (!x || !dy || !dw) return EVT_EINVAL;
-  int used_host = 0;
   if (sp) {
     sp->used = 0;
     if (sp->parts < 1 || !sp->used_dev || sp->prev_used < 0 || sp->prev_used > sp->parts) return EVT_EINVAL;
@@ -1404,14 +1404,28 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
     if (sp->ws && sp->ws_floats <= 0) return EVT_EINVAL;
   }
   if (c->out_act != EVT_ACT_NONE && !y) return EVT_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int lout = evt_conv1d_lout(c);
-  const void* ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
+  return 0;
+}
+
+// Where a weight gradient goes: the descriptor of the MFMA kernels and the family that takes it.  ONE function for the
+// single entry point and for the grouped one: a member of a group runs the kernel it would run alone.
+struct WgRoute {
+  WgP p;
+  int lout;
+  const void* ysv;
+  bool grouped, igemm_path, gemm_w, halo_w, deep_w, ring_w;
+};
+
+static WgRoute wg_route(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
+                        const evt_wgrad_parts* sp, int* used_host) {
+  WgRoute r{};
+  const int lout = r.lout = evt_conv1d_lout(c);
+  const void* ysv = r.ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
   evt_wlayout l; evt_conv1d_layout(c, &l);
-  const bool grouped = c->impl != EVT_IMPL_NAIVE && evt_grouped_supported(c);
-  const bool igemm_path = !grouped && c->impl != EVT_IMPL_NAIVE && igemm_ok(c) && l.reg_kp <= 64;
+  const bool grouped = r.grouped = c->impl != EVT_IMPL_NAIVE && evt_grouped_supported(c);
+  const bool igemm_path = r.igemm_path = !grouped && c->impl != EVT_IMPL_NAIVE && igemm_ok(c) && l.reg_kp <= 64;
   // descriptor of the MFMA weight-gradient kernels
-  WgP p{};
+  WgP& p = r.p;
   p.dw = dw; p.nseq = c->nseq; p.KH = c->k; p.KHp = l.reg_kp; p.s = c->stride; p.dil = c->dil; p.off = -c->pad;
   if (!c->transposed) {
     // dW[co][.][t][ci] += dy_eff[q][co] * lrelu(x)[q*s + t*dil - pad][ci]
@@ -1427,16 +1441,36 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
   p.dbias = nullptr;
   if (sp) {
     p.dw_extra = sp->dw_extra; p.part_stride = sp->part_stride; p.parts = sp->parts; p.prev_used = sp->prev_used;
-    p.db_part = sp->db_part; p.used = sp->used_dev; p.used_host = &used_host; p.dirty0 = sp->dirty0 || sp->prev_used > 0;
+    p.db_part = sp->db_part; p.used = sp->used_dev; p.used_host = used_host; p.dirty0 = sp->dirty0 || sp->prev_used > 0;
   }
   // wide layers with plain operands: LDS-DMA GEMM kernel (conv_deep.hip); its dbias comes from the column-sum kernel
   // dense layers (k = 1, long reductions): the 128 x 128 weight-gradient GEMM tile
-  const bool gemm_w = igemm_path && c->impl == EVT_IMPL_AUTO && !c->transposed && evt_conv::wgrad_gemm_eligible(p, c->dtype);
+  const bool gemm_w = r.gemm_w = igemm_path && c->impl == EVT_IMPL_AUTO && !c->transposed && evt_conv::wgrad_gemm_eligible(p, c->dtype);
   // stride-1 layers with 3..11 taps and long sequences: one staged window of x serves all taps (wgrad_halo.hip)
-  const bool halo_w = !gemm_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_halo_eligible(p, c->dtype);
-  const bool deep_w = !gemm_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_deep_eligible(p, c->dtype);
+  const bool halo_w = r.halo_w = !gemm_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_halo_eligible(p, c->dtype);
+  const bool deep_w = r.deep_w = !gemm_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_deep_eligible(p, c->dtype);
   // latency-bound mid-size layers: ring-pipelined LDS-DMA kernel (fuses dbias when A is dy)
-  const bool ring_w = !deep_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_ring_eligible(p, c->dtype);
+  r.ring_w = !deep_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_ring_eligible(p, c->dtype);
+  return r;
+}
+
+// dbias is fused into the 16-bit MFMA weight-gradient kernels when their A operand is dy (plain Conv1d)
+static bool wg_fuses_bias_igemm(const evt_conv1d_params* c, const WgRoute& r, const float* dbias) {
+  return dbias && r.igemm_path && c->dtype == EVT_DT_HALF && !c->transposed;
+}
+
+int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
+                                float* dbias, evt_wgrad_parts* sp, void* stream) {
+  int rc = wg_check_args(c, x, dy, y, dw, sp);
+  if (rc) return rc;
+  int used_host = 0;
+  hipStream_t st = (hipStream_t)stream;
+  WgRoute route = wg_route(c, x, dy, y, dw, sp, &used_host);
+  WgP& p = route.p;
+  const int lout = route.lout;
+  const void* ysv = route.ysv;
+  const bool grouped = route.grouped, igemm_path = route.igemm_path, gemm_w = route.gemm_w, halo_w = route.halo_w,
+             deep_w = route.deep_w, ring_w = route.ring_w;
   // dbias is fused into the bf16 MFMA weight-gradient kernel when its A operand is dy (plain Conv1d)
   const bool cin1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 2;   // fuses dbias as well
   const bool cout1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 1;  // and so does the dot-product conv
@@ -1534,6 +1568,102 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
   }
   p.dbias = nullptr;
   return launch_wgrad(c->dtype, p, st);
+}
+
+int evt_wgrad_group_plan(evt_wgrad_plan* m, int32_t n, int64_t target) {
+  if (!m || n < 0 || target < 1) return EVT_EINVAL;
+  for (int i0 = 0; i0 < n; i0 += EVT_WGRAD_GROUP_MAX) {
+    const int cnt = n - i0 < EVT_WGRAD_GROUP_MAX ? n - i0 : EVT_WGRAD_GROUP_MAX;
+    long tiles[EVT_WGRAD_GROUP_MAX];
+    int stages[EVT_WGRAD_GROUP_MAX], mins[EVT_WGRAD_GROUP_MAX], parts[EVT_WGRAD_GROUP_MAX], nsplit[EVT_WGRAD_GROUP_MAX],
+        per[EVT_WGRAD_GROUP_MAX];
+    for (int i = 0; i < cnt; ++i) {
+      const evt_wgrad_plan& e = m[i0 + i];
+      if (e.tiles < 1 || e.stages < 1) return EVT_EINVAL;
+      tiles[i] = (long)e.tiles; stages[i] = e.stages; mins[i] = e.min_stages; parts[i] = e.parts;
+    }
+    evt_conv::wgrad_group_plan(tiles, stages, mins, parts, cnt, (long)target, nsplit, per);
+    for (int i = 0; i < cnt; ++i) {
+      m[i0 + i].launch = i0 / EVT_WGRAD_GROUP_MAX;
+      m[i0 + i].nsplit = nsplit[i];
+      m[i0 + i].per = per[i];
+    }
+  }
+  return 0;
+}
+
+namespace {
+// members of a group that met in one instantiation of wgrad_ring and wait for their launch
+struct WgBucket {
+  int MA, KT, s, n;
+  WgP ps[EVT_WGRAD_GROUP_MAX];
+  int used_host[EVT_WGRAD_GROUP_MAX];
+  evt_wgrad_parts* sp[EVT_WGRAD_GROUP_MAX];
+};
+
+int wg_bucket_launch(WgBucket& b, hipStream_t st) {
+  if (b.n == 0) return 0;
+  // one member left over: the single launcher, with the parameters it always had
+  const int rc = b.n == 1 ? evt_conv::launch_wgrad_ring(b.ps[0], st) : evt_conv::launch_wgrad_ring_group(b.ps, b.n, st);
+  for (int i = 0; i < b.n; ++i)
+    if (b.sp[i]) b.sp[i]->used = b.used_host[i];
+  b.n = 0;
+  return rc;
+}
+}  // namespace
+
+int evt_conv1d_bwd_weight_group(const evt_wgrad_member* members, int32_t n, void* stream) {
+  if (n < 0 || (n > 0 && !members)) return EVT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < n; ++i) {
+    const evt_wgrad_member& m = members[i];
+    if (!m.p) return EVT_EINVAL;
+    const int rc = wg_check_args(m.p, m.x, m.dy, m.y, m.dw, m.sp);
+    if (rc) return rc;
+    for (int j = 0; j < i; ++j)
+      if (members[j].dw == m.dw) return EVT_EINVAL;
+  }
+  constexpr int NB = 6;                                     // (MA, KT) pairs of wgrad_ring
+  static thread_local WgBucket buckets[NB];
+  int nb = 0;
+  for (int i = 0; i < n; ++i) {
+    const evt_wgrad_member& m = members[i];
+    int used_host = 0;
+    WgRoute r = wg_route(m.p, m.x, m.dy, m.y, m.dw, m.sp, &used_host);
+    // a bias gradient that the kernel does not fuse takes a launch of its own: the single path knows how
+    const bool together = r.ring_w && (!m.dbias || wg_fuses_bias_igemm(m.p, r, m.dbias));
+    WgBucket* b = nullptr;
+    if (together) {
+      const evt_conv::WgRingShape sh = evt_conv::wgrad_ring_shape(r.p);
+      for (int k = 0; k < nb && !b; ++k)
+        if (buckets[k].MA == sh.MA && buckets[k].KT == sh.KT && buckets[k].s == r.p.s) b = &buckets[k];
+      if (!b && nb < NB) {
+        b = &buckets[nb++];
+        b->MA = sh.MA; b->KT = sh.KT; b->s = r.p.s; b->n = 0;
+      }
+    }
+    if (!b) {
+      const int rc = evt_conv1d_bwd_weight_parts(m.p, m.x, m.dy, m.y, m.dw, m.dbias, m.sp, stream);
+      if (rc) return rc;
+      continue;
+    }
+    const int k = b->n++;
+    b->ps[k] = r.p;
+    b->ps[k].dbias = m.dbias;
+    if (!m.dbias) b->ps[k].db_part = nullptr;
+    b->used_host[k] = 0;
+    b->ps[k].used_host = m.sp ? &b->used_host[k] : nullptr;
+    b->sp[k] = m.sp;
+    if (b->n == EVT_WGRAD_GROUP_MAX) {
+      const int rc = wg_bucket_launch(*b, st);
+      if (rc) return rc;
+    }
+  }
+  for (int k = 0; k < nb; ++k) {
+    const int rc = wg_bucket_launch(buckets[k], st);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -632,7 +632,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_deep(WgP p, int stages_per_split
   }
   if (do_bias) wg_finish_bias_mma<4>(p, bacc, a0, wr, wc, g8, j16, blockIdx.y);
   // lane holds A channels g8*4..+3 (rows) x B channel j16 (column) of each tile
-  wg_finish<4, WKT>(p, smem, acc, ntap, a0, ch, t0, wr, wc, g8, j16, blockIdx.y);
+  wg_finish<4, WKT>(p, smem, acc, ntap, a0, ch, t0, wr, wc, g8, j16, blockIdx.y, blockIdx.x == 0 && blockIdx.y == 0);
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1156,8 +1156,10 @@ template <int MA> __device__ __forceinline__ int a_swz(int row) {
   return MA == 4 ? 2 * ((row & 3) | (((row >> 3) & 1) << 2)) : 2 * (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
 }
 
+// The block's work as a function of (descriptor, stages per split, tile index, split index): the single launch passes its
+// block indices, the grouped launch (wgrad_ring_group below) what it decoded for one member of its table.
 template <int MA, int KT, int NS>
-__global__ __launch_bounds__(256) void wgrad_ring(WgP p, int stages_per_split) {
+__device__ __forceinline__ void wgrad_ring_block(const WgP& p, int stages_per_split, int tile, int split) {
   constexpr int AROW = 64 * MA;                     // bytes per A-tile row (32*MA channels)
   constexpr int ABYTES = WPOS * AROW;
   constexpr int STAGE = ABYTES + KT * WB_BYTES;
@@ -1170,8 +1172,7 @@ __global__ __launch_bounds__(256) void wgrad_ring(WgP p, int stages_per_split) {
   const int wr = wave >> 1, wc = wave & 1;
 
   // plain grid: an XCD-aware decode as in wgrad_deep cut the fetched bytes but made the launch slower (see launch_wgrad_ring)
-  int bx = blockIdx.x;
-  const int split = blockIdx.y;
+  int bx = tile;
   const int ch = bx % p.nchunk; bx /= p.nchunk;
   const int tgi = bx % p.ntapgrp;
   const int atile = bx / p.ntapgrp;
@@ -1272,7 +1273,34 @@ __global__ __launch_bounds__(256) void wgrad_ring(WgP p, int stages_per_split) {
     asm volatile("" ::: "memory");
   }
   if (do_bias) wg_finish_bias_mma<MA>(p, bacc, a0, wr, wc, g8, j16, split);
-  wg_finish<MA, KT>(p, smem, acc, ntap, a0, ch, t0, wr, wc, g8, j16, split);
+  wg_finish<MA, KT>(p, smem, acc, ntap, a0, ch, t0, wr, wc, g8, j16, split, tile == 0 && split == 0);
+}
+
+template <int MA, int KT, int NS>
+__global__ __launch_bounds__(256) void wgrad_ring(WgP p, int stages_per_split) {
+  wgrad_ring_block<MA, KT, NS>(p, stages_per_split, blockIdx.x, blockIdx.y);
+}
+
+// the descriptor of member `r` of a grouped launch (block-uniform: scalar loads from the kernel arguments)
+__device__ __forceinline__ WgP wg_member_desc(const WgP& base, const WgMember& r) {
+  WgP p = base;
+  p.A = r.A; p.B = r.B; p.dw = r.dw; p.dw_extra = r.dw_extra; p.db_part = r.db_part; p.dbias = r.dbias; p.used = r.used;
+  p.part_stride = r.part_stride;
+  p.nseq = r.nseq; p.LA = r.LA; p.LB = r.LB; p.CA = r.CA; p.CB = r.CB; p.KH = r.KH; p.KHp = r.KHp; p.dil = r.dil;
+  p.off = r.off; p.Q = r.Q; p.nchunk = r.nchunk; p.ntapgrp = r.ntapgrp;
+  p.parts = r.parts; p.prev_used = r.prev_used; p.now_used = r.now_used; p.dirty0 = r.dirty0; p.nsplit = r.nsplit;
+  return p;
+}
+
+// Grouped launch: grid plane z is one member (one convolution); x / y are its tile and split as in the single launch, sized
+// for the largest member -- a block outside its member's own ranges returns at once.  Tile 0 of split 0 of a member is the
+// one block that records that member's slab counts.
+template <int MA, int KT, int NS>
+__global__ __launch_bounds__(256) void wgrad_ring_group(WgGroup g) {
+  const WgMember& r = g.m[blockIdx.z];
+  if ((int)blockIdx.x >= r.tiles || (int)blockIdx.y >= r.nsplit) return;
+  const WgP p = wg_member_desc(g.base, r);
+  wgrad_ring_block<MA, KT, NS>(p, r.per, blockIdx.x, blockIdx.y);
 }
 
 }  // namespace
@@ -1509,20 +1537,109 @@ bool wgrad_ring_eligible(const WgP& p, int dtype) {
   return true;
 }
 
+WgRingShape wgrad_ring_shape(const WgP& p) {
+  WgRingShape s;
+  s.KT = p.KHp <= 1 ? 1 : (p.KHp <= 3 ? 3 : 5);
+  s.nchunk = p.CB / 32;
+  s.ntapgrp = (p.KHp + s.KT - 1) / s.KT;
+  s.nstages = (int)(((long)p.nseq * p.Q + WPOS - 1) / WPOS);
+  // 128-channel tiles when that still yields enough blocks, else 64
+  const long tiles128 = p.CA % 128 == 0 ? (long)(p.CA / 128) * s.nchunk * s.ntapgrp : 0;
+  s.MA = (tiles128 >= 128 || (tiles128 > 0 && tiles128 * (s.nstages / 4) >= 512)) ? 4 : 2;
+  s.tiles = (long)(p.CA / (32 * s.MA)) * s.nchunk * s.ntapgrp;
+  return s;
+}
+
+void wgrad_group_plan(const long* tiles, const int* nstages, const int* min_stages, const int* parts, int n, long target,
+                      int* nsplit, int* per) {
+  long total = 0;
+  for (int i = 0; i < n; ++i) total += tiles[i];
+  if (total < 1) total = 1;
+  const long want = (target + total - 1) / total;          // the launch as a whole aims at `target` blocks
+  for (int i = 0; i < n; ++i) {
+    long split = want;
+    const int ms = min_stages[i] > 0 ? min_stages[i] : 1;
+    if (split > nstages[i] / ms) split = nstages[i] / ms;
+    if (parts[i] > 0 && split > parts[i]) split = parts[i];
+    if (split < 1) split = 1;
+    per[i] = (int)((nstages[i] + split - 1) / split);
+    if (per[i] < 1) per[i] = 1;
+    nsplit[i] = (nstages[i] + per[i] - 1) / per[i];        // every split owns at least one stage
+    if (nsplit[i] < 1) nsplit[i] = 1;
+  }
+}
+
+template <int MA, int KT, int NS>
+static int launch_ring_group_inst(const WgGroup& g, int n, int max_tiles, int max_split, hipStream_t st) {
+  constexpr size_t lds = (size_t)NS * (WPOS * 64 * MA + KT * WB_BYTES);
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ring_group<MA, KT, NS>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return EVT_ELAUNCH;
+    attr = true;
+  }
+  evt_set_last_tag("wgrad_ring<bf16, %d, %dx32, 64, x%d> group of %d", 32 * MA, KT, NS, n);
+  hipLaunchKernelGGL((wgrad_ring_group<MA, KT, NS>), dim3((unsigned)max_tiles, (unsigned)max_split, (unsigned)n), dim3(256),
+                     lds, st, g);
+  return evt_check_launch();
+}
+
+int launch_wgrad_ring_group(WgP* ps, int n, hipStream_t st) {
+  if (n < 2 || n > WG_GROUP_MAX) return EVT_EINVAL;
+  long tiles[WG_GROUP_MAX];
+  int nstages[WG_GROUP_MAX], min_stages[WG_GROUP_MAX], parts[WG_GROUP_MAX], nsplit[WG_GROUP_MAX], per[WG_GROUP_MAX];
+  WgRingShape sh[WG_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    if (!wgrad_ring_eligible(ps[i], EVT_DT_HALF)) return EVT_ENOTSUP;
+    sh[i] = wgrad_ring_shape(ps[i]);
+    if (sh[i].MA != sh[0].MA || sh[i].KT != sh[0].KT || ps[i].s != ps[0].s) return EVT_EINVAL;
+    for (int j = 0; j < i; ++j)
+      if (ps[j].dw == ps[i].dw) return EVT_EINVAL;          // two launches into one image have an order: not one grid
+    tiles[i] = sh[i].tiles; nstages[i] = sh[i].nstages; min_stages[i] = WG_RING_MIN_STAGES; parts[i] = ps[i].parts;
+  }
+  wgrad_group_plan(tiles, nstages, min_stages, parts, n, WG_RING_TARGET, nsplit, per);
+  WgGroup g;
+  g.base = ps[0];
+  g.base.used_host = nullptr;
+  int max_tiles = 0, max_split = 0;
+  for (int i = 0; i < n; ++i) {
+    WgP& p = ps[i];
+    p.nchunk = sh[i].nchunk; p.ntapgrp = sh[i].ntapgrp;
+    p.nsplit = nsplit[i];
+    p.now_used = p.prev_used > nsplit[i] ? p.prev_used : nsplit[i];
+    if (p.parts > 0 && p.used_host) *p.used_host = p.now_used;
+    WgMember& r = g.m[i];
+    r.A = p.A; r.B = p.B; r.dw = p.dw; r.dw_extra = p.dw_extra; r.db_part = p.db_part; r.dbias = p.dbias; r.used = p.used;
+    r.part_stride = p.part_stride;
+    r.nseq = p.nseq; r.LA = p.LA; r.LB = p.LB; r.CA = p.CA; r.CB = p.CB; r.KH = p.KH; r.KHp = p.KHp; r.dil = p.dil;
+    r.off = p.off; r.Q = p.Q; r.nchunk = p.nchunk; r.ntapgrp = p.ntapgrp;
+    r.parts = p.parts; r.prev_used = p.prev_used; r.now_used = p.now_used; r.dirty0 = p.dirty0;
+    r.nsplit = nsplit[i]; r.per = per[i]; r.tiles = (int)tiles[i];
+    if (r.tiles > max_tiles) max_tiles = r.tiles;
+    if (r.nsplit > max_split) max_split = r.nsplit;
+  }
+  for (int i = n; i < WG_GROUP_MAX; ++i) g.m[i] = g.m[0];   // never read (grid z = n); defined bytes for the graph node's copy
+#define RINGG(MA_, KT_)                                                                               \
+  (MA_ == 4 && KT_ == 5 ? launch_ring_group_inst<MA_, KT_, 3>(g, n, max_tiles, max_split, st)        \
+                        : launch_ring_group_inst<MA_, KT_, 4>(g, n, max_tiles, max_split, st))
+  const int MA = sh[0].MA, KT = sh[0].KT;
+  if (MA == 4) return KT == 1 ? RINGG(4, 1) : (KT == 3 ? RINGG(4, 3) : RINGG(4, 5));
+  return KT == 1 ? RINGG(2, 1) : (KT == 3 ? RINGG(2, 3) : RINGG(2, 5));
+#undef RINGG
+}
+
 int launch_wgrad_ring(const WgP& p_in, hipStream_t st) {
   WgP p = p_in;
   if (!wgrad_ring_eligible(p, EVT_DT_HALF)) return EVT_ENOTSUP;
-  const int KT = p.KHp <= 1 ? 1 : (p.KHp <= 3 ? 3 : 5);
-  p.nchunk = p.CB / 32;
-  p.ntapgrp = (p.KHp + KT - 1) / KT;
-  const int nstages = (int)(((long)p.nseq * p.Q + WPOS - 1) / WPOS);
-  // 128-channel tiles when that still yields enough blocks, else 64
-  const long tiles128 = p.CA % 128 == 0 ? (long)(p.CA / 128) * p.nchunk * p.ntapgrp : 0;
-  const int MA = (tiles128 >= 128 || (tiles128 > 0 && tiles128 * (nstages / 4) >= 512)) ? 4 : 2;
-  const long tiles = (long)(p.CA / (32 * MA)) * p.nchunk * p.ntapgrp;
-  constexpr long target = 256;                    // measured: 256 best
+  const WgRingShape sh = wgrad_ring_shape(p);
+  const int KT = sh.KT, MA = sh.MA, nstages = sh.nstages;
+  p.nchunk = sh.nchunk;
+  p.ntapgrp = sh.ntapgrp;
+  const long tiles = sh.tiles;
+  constexpr long target = WG_RING_TARGET;         // measured: 256 best
   int nsplit, per;                                // ~1 block per CU: more splits only add partial tiles; >= 3 K stages per block
-  wgrad_pick_split(p, tiles, nstages, target, 3, &nsplit, &per);
+  wgrad_pick_split(p, tiles, nstages, target, WG_RING_MIN_STAGES, &nsplit, &per);
   // Plain grid.  An XCD-aware order (split count a multiple of 8, all tiles of a split on one XCD) was measured in round 4:
   // FETCH_SIZE of the WN in-layer gradient (192 -> 384 k5, 3200 positions, 36 tiles x 8 splits) 12.1 -> 1.9 MB per launch,
   // and the launch 15 -> 20 us: the 36 tiles of a split land on the 32 CUs of one XCD at once.  These operands fit every

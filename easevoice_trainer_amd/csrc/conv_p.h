@@ -91,6 +91,43 @@ int launch_fold_partials2(const float* part, long stride, int nb, float* out, lo
 // (classic mode: `target` blocks; slab mode: additionally nsplit <= parts)
 void wgrad_pick_split(const WgP& p, long tiles, int nstages, long target, int min_stages, int* nsplit, int* per);
 
+// ---- grouped launches (evt_conv1d_bwd_weight_group): several convolutions' tiles in ONE grid ----
+// What varies between the members of a grouped launch; everything else (stride, the identity slopes / activations the
+// eligibility tests demand) is WgGroup::base.  The table travels BY VALUE in the kernel arguments -- a captured graph node
+// copies it, nothing has to outlive the call -- so 16 records and the base stay well under the 4 KB argument limit.
+struct WgMember {
+  const void* A;
+  const void* B;
+  float* dw;
+  float* dw_extra;
+  float* db_part;
+  float* dbias;
+  int* used;
+  long part_stride;
+  int nseq, LA, LB, CA, CB, KH, KHp, dil, off, Q, nchunk, ntapgrp;
+  int parts, prev_used, now_used, dirty0;
+  int nsplit, per, tiles;     // this member's plan: blocks (x < tiles, y < nsplit) of grid plane z = member work, the rest return
+};
+constexpr int WG_GROUP_MAX = EVT_WGRAD_GROUP_MAX;
+struct WgGroup {
+  WgP base;
+  WgMember m[WG_GROUP_MAX];
+};
+static_assert(sizeof(WgGroup) <= 3072, "grouped weight-gradient table: kernel arguments are limited to 4 KB");
+
+// how wgrad_ring tiles a descriptor: template instantiation (MA, KT), chunk / tap-group counts, tiles and K stages --
+// the single launcher and the grouped one both take it from here, so a member runs the kernel it would run alone
+struct WgRingShape { int MA, KT, nchunk, ntapgrp, nstages; long tiles; };
+constexpr long WG_RING_TARGET = 256;       // blocks a wgrad_ring launch aims at (measured: 256 best)
+constexpr int WG_RING_MIN_STAGES = 3;
+WgRingShape wgrad_ring_shape(const WgP& p);
+// the split of every member of ONE grouped launch (evt_wgrad_group_plan in evt.h states the rule)
+void wgrad_group_plan(const long* tiles, const int* nstages, const int* min_stages, const int* parts, int n, long target,
+                      int* nsplit, int* per);
+// ps[0..n): descriptors that wgrad_ring_eligible accepts and that share (MA, KT), 2 <= n <= WG_GROUP_MAX, no two with the
+// same dw; sets each ps[i].nsplit / now_used (and *used_host) like the single launcher
+int launch_wgrad_ring_group(WgP* ps, int n, hipStream_t st);
+
 // rows_gemm.hip: k = 1 layers applied to at most 16 rows in total (one vector per batch item)
 bool rows16_eligible(const struct evt_conv1d_params* c, int rows, int n_out, int k_red, bool fused);
 int launch_rows16(const void* x, const void* w, const float* bias, void* y, int M, int N, int K, hipStream_t st);

@@ -65,12 +65,14 @@ __device__ __forceinline__ void wg_store_slab(const WgP& p, float* slab, bool ad
   }
 }
 
-// the common tail of the kernels: classic atomics or the slab store; `smem` is the block's whole dynamic LDS
+// the common tail of the kernels: classic atomics or the slab store; `smem` is the block's whole dynamic LDS.  `split` and
+// `first` (the one block of the convolution that records the slab count: tile 0 of split 0) are the caller's DECODED
+// indices -- in a grouped launch the grid holds several convolutions
 template <int MI, int NT>
 __device__ __forceinline__ void wg_finish(const WgP& p, unsigned char* smem, const f32x4 (&acc)[MI][NT], int ntap, int a0,
-                                          int ch, int t0, int wr, int wc, int g8, int j16, int split) {
+                                          int ch, int t0, int wr, int wc, int g8, int j16, int split, bool first) {
   if (p.parts > 0) {
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.used[0] = p.now_used;
+    if (first && threadIdx.x == 0) p.used[0] = p.now_used;
     wg_store_slab<MI, NT>(p, wg_slab(p, split), split == 0 ? p.dirty0 != 0 : split < p.prev_used, reinterpret_cast<float*>(smem), acc, ntap,
                           a0, ch, t0, wr, wc, g8, j16);
     return;

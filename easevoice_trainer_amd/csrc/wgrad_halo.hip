@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void wgrad_halo(WgP p, int spq, int stages_per
     asm volatile("" ::: "memory");
   }
   if (do_bias) wg_finish_bias_mma<MA>(p, bacc, a0, wr, wc, g8, j16, blockIdx.y);
-  wg_finish<MA, NT>(p, smem, acc, NT, a0, ch, 0, wr, wc, g8, j16, blockIdx.y);
+  wg_finish<MA, NT>(p, smem, acc, NT, a0, ch, 0, wr, wc, g8, j16, blockIdx.y, blockIdx.x == 0 && blockIdx.y == 0);
 }
 
 template <int MA, int NT, int NS>

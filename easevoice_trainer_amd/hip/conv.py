@@ -146,7 +146,9 @@ def slab_count(image_bytes, d0, budget=48 << 20, cap=32):
     all their parallelism comes from the split: images of a few KB (the 16- / 32-channel vocoder stages: 11 - 45 KB for
     160 K - 330 K positions) and layers with at most 64 output channels (one or two output tiles: 64 -> 64 k11 over 81920
     positions, in the step: 66 us with 32 slabs, 23 us with 128).  The s2 generator's slabs come to 5.2 GB, the
-    discriminators' to 0.7 GB, of the 288 GB."""
+    discriminators' to 0.7 GB, of the 288 GB.  The count is an UPPER bound: a convolution launched with others of its
+    WN stack (evt_conv1d_bwd_weight_group) fills the chip with their tiles and uses about half the splits it needs alone;
+    the kernels record how many slabs hold sums, and the fold reads those."""
     limit = 256 if image_bytes <= (64 << 10) else (128 if d0 <= 64 else cap)
     return max(1, min(limit, -(-budget // max(image_bytes, 1))))
 
@@ -170,6 +172,8 @@ class WeightBank:
         # Round 6, under the branch streams (profiles/r06_streams.txt): the generator's ~150 launches flushed every 48 instead
         # of every 64 is 0.3 ms ahead (40-56 level except 52; 32 and 80-96 behind -- it matters which stretch of the backward a
         # flush lands beside); the discriminators' 42 stay one flush at the end either way (in pieces: +0.2 ms).
+        # A declared group (_bwd_weight_group: four gradients of a WN stack) is one entry of the queue that counts with all
+        # its members (queued()); re-swept with the groups: 16 / 24 / 32 / 64 are 0.7 - 2.1 ms behind 48.
         self.defer_n = int(os.environ.get("EVT_WGRAD_DEFER", "48")) if self.device.type == "cuda" else 0
         self._deferred = []
         self._deferred_on = set()
@@ -223,7 +227,8 @@ class WeightBank:
         # slabs per image: more slabs = more split-K blocks for the weight-gradient launches, and as many more bytes for the
         # fold at the end of the backward (wn_grad).  32 until the launches moved off the critical path (side stream, branch
         # streams); since then the fold's bytes weigh more: 16-24 measured level and 0.2 ms ahead of 32, 8 and 4 behind
-        # (profiles/r06_streams.txt)
+        # (profiles/r06_streams.txt).  The WN stacks' grouped launches use fewer than the cap (profiles/wgrad_groups_after.txt:
+        # the generator's fold 599 -> 512 us with whole-stack groups); the arenas keep the upper bound
         cap = 20
         # operands held for the deferred weight-gradient launches: flushed on a byte budget as well as on a count
         self.defer_bytes = max(256, int(4096 * mem_scale)) << 20
@@ -411,6 +416,10 @@ class WeightBank:
             self._side = L.role_stream(self.device, "bank")
         return self._side
 
+    def queued(self):
+        """convolutions waiting in the queue (a declared group counts with all its members: the flushes stay where they were)"""
+        return sum(len(e) if isinstance(e, WgGroup) else 1 for e in self._deferred)
+
     def flush_deferred(self):
         """hand the queued weight-gradient launches to the side stream (one fork)"""
         if not self._deferred:
@@ -422,8 +431,12 @@ class WeightBank:
         self._deferred_on.clear()
         with torch.cuda.stream(side):
             for args in self._deferred:
-                _bwd_weight_now(*args)
-        self._held.extend((a[1], a[2], a[3]) for a in self._deferred)
+                if isinstance(args, WgGroup):         # a declared group: one entry, one call
+                    _bwd_weight_group_now(args)
+                else:
+                    _bwd_weight_now(*args)
+        for args in self._deferred:
+            self._held.extend((a[1], a[2], a[3]) for a in (args if isinstance(args, WgGroup) else (args,)))
         self._deferred.clear()
         self._deferred_bytes = 0
 
@@ -647,33 +660,114 @@ def _bwd_weight(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope):
         bank._deferred.append((slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope))
         bank._deferred_on.add(torch.cuda.current_stream(bank.device))   # a branch stream of the discriminators, or the main one
         bank._deferred_bytes += x.numel() * x.element_size() + dy.numel() * dy.element_size()
-        if len(bank._deferred) >= bank.defer_n or bank._deferred_bytes >= bank.defer_bytes:
+        if bank.queued() >= bank.defer_n or bank._deferred_bytes >= bank.defer_bytes:
             bank.flush_deferred()
         return
     _bwd_weight_now(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope)
 
 
+GROUP_FLUSH = False  # measurements: True = a declared group is released to the side stream at once
+
+
+class WgGroup(list):
+    """a DECLARED group of weight gradients as one entry of WeightBank._deferred: the argument tuples of _bwd_weight for
+    convolutions that become ready together (the layers of a WN stack), handed over by the module that owns them -- what
+    is in a group never depends on when the queue is flushed"""
+
+
+def _bwd_weight_group(members):
+    """weight gradients of several convolutions at once (members: argument tuples of _bwd_weight, all of one bank):
+    evt_conv1d_bwd_weight_group launches those that meet in one kernel together, each with fewer splits -- fewer slabs
+    written and folded -- than it would need alone.  A traced run launches them one by one, as before."""
+    members = WgGroup(members)
+    if not members:
+        return
+    bank = members[0][0].bank
+    for a in members:
+        if a[0].packed_member or a[0].bank is not bank:
+            raise L.EvtError("a weight-gradient group takes convolutions of one bank, none of them a packed projection member")
+    if TRACE is not None:
+        for a in members:
+            _bwd_weight_now(*a)
+        return
+    if bank.defer_n > 0:
+        bank._deferred.append(members)
+        bank._deferred_on.add(torch.cuda.current_stream(bank.device))
+        bank._deferred_bytes += sum(a[1].numel() * a[1].element_size() + a[2].numel() * a[2].element_size() for a in members)
+        # The group waits in the queue like its members would (queued() counts them one by one, so the flushes stay where
+        # they were).  Measured on the s2 step (profiles/wgrad_groups_step_ab.txt): groups of a whole stack counted as ONE
+        # entry left the WN stacks -- the end of the generator's backward -- for the join, +0.5 ms; released at once
+        # (GROUP_FLUSH) in runs of eight layers, their long blocks crowd the backward-data chain, +1.0 ms.
+        if GROUP_FLUSH or bank.queued() >= bank.defer_n or bank._deferred_bytes >= bank.defer_bytes:
+            bank.flush_deferred()
+        return
+    _bwd_weight_group_now(members)
+
+
+def _bwd_weight_group_now(members):
+    # two launches into one gradient image have an order: a slot that comes again starts the next call
+    run, seen = [], set()
+    for a in members:
+        if id(a[0]) in seen:
+            _bwd_weight_group_call(run)
+            run, seen = [], set()
+        run.append(a)
+        seen.add(id(a[0]))
+    _bwd_weight_group_call(run)
+
+
+def _bwd_weight_group_call(members):
+    if len(members) == 1:
+        _bwd_weight_now(*members[0])
+        return
+    arr = (L.WgradMember * len(members))()
+    keep = []
+    for r, (slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope) in zip(arr, members):
+        p = slot.params(nseq, lin, in_slope, out_act, out_slope)
+        dbias = _dbias_of(slot.module)
+        sp = _wgrad_parts(slot, dbias) if slot.bank.parts_on else None
+        keep.append((p, sp))
+        r.p, r.x, r.dy = C.addressof(p), x.data_ptr(), dy.data_ptr()
+        r.y = y.data_ptr() if (out_act != L.ACT_NONE and y is not None) else None
+        r.dw, r.dbias = slot.dw.data_ptr(), (dbias.data_ptr() if dbias is not None else None)
+        r.sp = C.addressof(sp) if sp is not None else None
+    L.check(L.lib().evt_conv1d_bwd_weight_group(arr, len(members), L.stream_ptr()), "evt_conv1d_bwd_weight_group")
+    for (slot, *_), (_p, sp) in zip(members, keep):
+        if sp is not None:
+            slot.wg_used, slot.wg_dirty = max(slot.wg_used, int(sp.used)), True
+
+
+def _dbias_of(m):
+    if m.bias is None:
+        return None
+    if m.bias.grad is None:
+        m.bias.grad = torch.zeros_like(m.bias)
+    return m.bias.grad
+
+
+def _wgrad_parts(slot, dbias):
+    """the slot's evt_wgrad_parts record, brought up to date for the next launch into its image"""
+    sp = slot._wgp
+    if sp is None:
+        sp = slot._wgp = L.WgradParts()
+        sp.dw_extra = slot.dw_extra.data_ptr() if slot.parts > 1 else None
+        sp.part_stride = (slot.layout.reg_elems + 127) // 128 * 128
+        sp.db_part = slot.db_part.data_ptr() if (dbias is not None and not slot.module.transposed) else None
+        sp.used_dev = slot.used.data_ptr()
+        sp.parts = slot.parts
+    sp.prev_used, sp.dirty0 = slot.wg_used, int(slot.wg_dirty)
+    ws = slot.bank.scratch()
+    sp.ws, sp.ws_floats = ws.data_ptr(), ws.numel()
+    return sp
+
+
 def _bwd_weight_now(slot, x, dy, y, nseq, lin, in_slope, out_act, out_slope):
     m = slot.module
     p = slot.params(nseq, lin, in_slope, out_act, out_slope)
-    dbias = None
-    if m.bias is not None:
-        if m.bias.grad is None:
-            m.bias.grad = torch.zeros_like(m.bias)
-        dbias = m.bias.grad
+    dbias = _dbias_of(m)
     e0 = _t0()
     if slot.bank.parts_on:
-        sp = slot._wgp
-        if sp is None:
-            sp = slot._wgp = L.WgradParts()
-            sp.dw_extra = slot.dw_extra.data_ptr() if slot.parts > 1 else None
-            sp.part_stride = (slot.layout.reg_elems + 127) // 128 * 128
-            sp.db_part = slot.db_part.data_ptr() if (dbias is not None and not m.transposed) else None
-            sp.used_dev = slot.used.data_ptr()
-            sp.parts = slot.parts
-        sp.prev_used, sp.dirty0 = slot.wg_used, int(slot.wg_dirty)
-        ws = slot.bank.scratch()
-        sp.ws, sp.ws_floats = ws.data_ptr(), ws.numel()
+        sp = _wgrad_parts(slot, dbias)
         L.check(L.lib().evt_conv1d_bwd_weight_parts(C.byref(p), L.ptr(x), L.ptr(dy),
                                                     L.ptr(y if out_act != L.ACT_NONE else None), L.ptr(slot.dw),
                                                     L.ptr(dbias), C.byref(sp), L.stream_ptr()),

@@ -82,6 +82,21 @@ class WgradParts(C.Structure):
                 ("ws", C.c_void_p), ("ws_floats", C.c_int64)]
 
 
+class WgradMember(C.Structure):
+    """evt_wgrad_member: one convolution of evt_conv1d_bwd_weight_group"""
+    _fields_ = [("p", C.c_void_p), ("x", C.c_void_p), ("dy", C.c_void_p), ("y", C.c_void_p), ("dw", C.c_void_p),
+                ("dbias", C.c_void_p), ("sp", C.c_void_p)]
+
+
+class WgradPlan(C.Structure):
+    """evt_wgrad_plan: a member of evt_wgrad_group_plan"""
+    _fields_ = [("tiles", C.c_int64), ("stages", C.c_int32), ("min_stages", C.c_int32), ("parts", C.c_int32),
+                ("launch", C.c_int32), ("nsplit", C.c_int32), ("per", C.c_int32)]
+
+
+WGRAD_GROUP_MAX = 16     # EVT_WGRAD_GROUP_MAX
+
+
 class Seg(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("da", C.c_void_p), ("n", C.c_int64),
                 ("scale", C.c_float), ("pad_", C.c_int32)]

@@ -81,6 +81,21 @@ class WNStackFn(torch.autograd.Function):
         dx_next = None
         dg32 = torch.zeros((n_layers, B, 2 * H), dtype=torch.float32, device=dev) if g_lbh is not None else None
         fused = FUSED_BACKWARD and _layer_fused(dt, H, in_slots, rs_slots)
+        # the stack's weight gradients -- in_layers of one shape, res_skip layers of one shape -- are declared as groups of
+        # GROUP_LAYERS layers: launched together they fill the chip with their tiles and need half the splits of their 3200
+        # positions (half the slabs written, and folded at the end of the backward)
+        # (a traced run keeps every launch where it was: behind the data half of its layer)
+        group = [] if (GROUP_WGRADS and HC.TRACE is None) else None
+
+        def wgrad(*args):
+            if group is None:
+                HC._bwd_weight(*args)
+                return
+            group.append(args)
+            if len(group) >= 2 * GROUP_LAYERS:       # a long stack hands its layers over in runs, beside its own data chain
+                HC._bwd_weight_group(list(group))
+                group.clear()
+
         for i in reversed(range(n_layers)):
             last = i == n_layers - 1
             x, x_in, acts = saved[3 * i: 3 * i + 3]
@@ -103,9 +118,9 @@ class WNStackFn(torch.autograd.Function):
                 if last:
                     dacc = drs
                 if sr.bank.weight_grads:
-                    HC._bwd_weight(sr, acts, drs, None, B, T, 1.0, L.ACT_NONE, 1.0)
+                    wgrad(sr, acts, drs, None, B, T, 1.0, L.ACT_NONE, 1.0)
                 if si.bank.weight_grads:
-                    HC._bwd_weight(si, x, dx_in, None, B, T, 1.0, L.ACT_NONE, 1.0)
+                    wgrad(si, x, dx_in, None, B, T, 1.0, L.ACT_NONE, 1.0)
                 dx_next = dx
                 continue
             drs = torch.empty((B, T, rs_w), dtype=dtype, device=dev)
@@ -116,7 +131,7 @@ class WNStackFn(torch.autograd.Function):
                 dacc = drs          # out = (acc + rs) * mask: the skip sum's gradient is masked too
             s = rs_slots[i]
             if s.bank.weight_grads:
-                HC._bwd_weight(s, acts, drs, None, B, T, 1.0, L.ACT_NONE, 1.0)
+                wgrad(s, acts, drs, None, B, T, 1.0, L.ACT_NONE, 1.0)
             dacts = HC._bwd_data(s, drs, None, acts, None, B, T, 1.0, L.ACT_NONE, 1.0)
             dx_in = torch.empty_like(x_in)
             L.check(L.lib().evt_gated_act_bwd(dt, L.ptr(x_in), L.ptr(g_lbh[i] if g_lbh is not None else None), L.ptr(dacts),
@@ -124,15 +139,23 @@ class WNStackFn(torch.autograd.Function):
                                               L.stream_ptr()), "evt_gated_act_bwd")
             s = in_slots[i]
             if s.bank.weight_grads:
-                HC._bwd_weight(s, x, dx_in, None, B, T, 1.0, L.ACT_NONE, 1.0)
+                wgrad(s, x, dx_in, None, B, T, 1.0, L.ACT_NONE, 1.0)
             need_dx = i > 0 or ctx.needs_input_grad[0]
             dx_next = HC._bwd_data(s, dx_in, None, x, dx_res, B, T, 1.0, L.ACT_NONE, 1.0) if need_dx else None
+        if group:
+            HC._bwd_weight_group(group)
         dg = dg32.to(g_lbh.dtype) if (dg32 is not None and ctx.needs_input_grad[1]) else None
         return dx_next, dg, None, None, None, None, None
 
 
 FUSED_FORWARD = True     # tests / measurements: False = the four-launch layer forward at every shape
 FUSED_BACKWARD = True    # likewise: False = the four-launch data half of the layer backward
+GROUP_WGRADS = True      # likewise: False = every weight gradient of a stack queued on its own (single launches)
+# layers per declared group.  2: two in_layers are 72 tiles of 64 x (5 x 32) -> 4 splits of 13 K stages (8 of 7 alone), two
+# res_skip layers 36 tiles -> 8 splits (15 alone).  Whole stacks (16 layers: no split at all, blocks of 50 stages) make the
+# weight-gradient kernels and the fold shorter still, and the STEP longer: launches of 576 blocks that each hold a CU's LDS
+# for 50 stages crowd the backward-data chain they run beside (profiles/wgrad_groups_step_ab.txt)
+GROUP_LAYERS = 2
 
 
 def _layer_fused(dt, H, in_slots, rs_slots):

@@ -203,6 +203,45 @@ typedef struct evt_wgrad_parts {
 int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* p, const void* x, const void* dy, const void* y,
                                 float* dw, float* dbias, evt_wgrad_parts* sp, void* stream);
 
+/* Weight gradients of n convolutions that are ready TOGETHER (the layers of a WN stack, the convolutions of a vocoder
+ * stage), declared as a group by the module that owns them.  A convolution launched alone has to fill the chip from the
+ * split over its positions, and every split is one more slab of its gradient image written and folded; a group fills it
+ * with the tiles of its members, so each member needs fewer splits.  Every member is routed exactly as
+ * evt_conv1d_bwd_weight_parts would route it alone (same kernel, same template instantiation); the members that meet in
+ * one instantiation of wgrad_ring are launched together, up to EVT_WGRAD_GROUP_MAX per launch (their records travel by
+ * value in the kernel arguments), with the split of evt_wgrad_group_plan; every other member goes through
+ * evt_conv1d_bwd_weight_parts, in member order.  A launch that ends up with one member is the single launch.  No two
+ * members may share a gradient image (EVT_EINVAL).  sp (may be NULL: fp32 atomics) as in evt_conv1d_bwd_weight_parts; its
+ * `used` is returned per member. */
+#define EVT_WGRAD_GROUP_MAX 16
+typedef struct evt_wgrad_member {
+  const evt_conv1d_params* p;
+  const void* x;
+  const void* dy;
+  const void* y;
+  float* dw;
+  float* dbias;
+  evt_wgrad_parts* sp;
+} evt_wgrad_member;
+int evt_conv1d_bwd_weight_group(const evt_wgrad_member* members, int32_t n, void* stream);
+
+/* The split policy of a grouped launch, on the host alone (no device, no pointers, no stream).  members[0..n) are the
+ * members of ONE kernel instantiation in the order they were declared; member i goes to launch i / EVT_WGRAD_GROUP_MAX.
+ * Per launch: split = ceil(target / tiles of all its members), and per member clamped to
+ * [1, min(parts, stages / min_stages)] (parts <= 0: no slabs, no bound from them); per = ceil(stages / split) and
+ * nsplit = ceil(stages / per), so every split owns at least one stage.  `target` is the block count the kernel's single
+ * launcher aims at.  With n == 1 this is what the single launcher computes. */
+typedef struct evt_wgrad_plan {
+  int64_t tiles;        /* in: output tiles of the member */
+  int32_t stages;       /* in: K stages of its reduction */
+  int32_t min_stages;   /* in: fewest stages a split should own */
+  int32_t parts;        /* in: slabs provided */
+  int32_t launch;       /* out */
+  int32_t nsplit;       /* out */
+  int32_t per;          /* out: stages per split */
+} evt_wgrad_plan;
+int evt_wgrad_group_plan(evt_wgrad_plan* members, int32_t n, int64_t target);
+
 /* One HiFi-GAN ResBlock1 step  y = x + c2(lrelu(c1(lrelu(x), dilation d)))  (modules.py:299-308 of the reference; both
  * convolutions C -> C, kernel k, "same" padding, c2 undilated) as ONE launch for the narrow vocoder stages: bf16,
  * C in {16, 32}, k in {3, 7, 11}, d in 1..5.  x, y, xa, mid_a: [nseq][L][C]; w1_reg / w2_reg: the REG images of the two
