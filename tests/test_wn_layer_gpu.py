@@ -211,6 +211,8 @@ def test_fragment_images_follow_the_fold(gpu):
     x = (torch.randn(B, T, H, device=gpu) * live).to(dtype)
     with torch.no_grad():
         y0 = m(x, live.to(dtype), lens=lens).float()
+        # (the ALT images are registered before the change, as a backward would have: the fold below has to re-make them)
+        alt0 = [bank.frag(c._slot, "alt").clone() for c in (m.in_layers[0], m.res_skip_layers[0])]
         for p_ in m.parameters():
             p_.mul_(1.5)
         bank.fold()
@@ -231,3 +233,16 @@ def test_fragment_images_follow_the_fold(gpu):
     want = reg.view(lay.d0 // 16, 16, ktot // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)   # [tile][ks][g][n][8]
     torch.cuda.synchronize()
     assert torch.equal(frag, want)
+    # the ALT images the backward reads (rows = input channels; in_layer: 2H / 32 chunks x 5 flipped taps, res_skip: 2H / 32
+    # K steps), in the order wn_layer_bwd's weight loads imply: fragment (16-row tile, K step) at ((tile nk + ks) 64 + lane) 8,
+    # lane = 16 g + n holding row 16 tile + n, K elements 32 ks + 8 g .. + 7
+    for s, before in zip((m.in_layers[0]._slot, m.res_skip_layers[0]._slot), alt0):
+        lay = s.layout
+        ktot = lay.alt_nchunk * lay.alt_kp * lay.alt_ck
+        assert lay.d1 == H and ktot == 2 * H * s.module.k
+        alt = s.alt.view(lay.d1, ktot)
+        want = alt.view(lay.d1 // 16, 16, ktot // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+        got = bank.frag(s, "alt")
+        torch.cuda.synchronize()
+        assert got.numel() == H * ktot and torch.equal(got, want)
+        assert float(got.float().abs().max()) > 0 and not torch.equal(got, before)          # the change arrived here too
