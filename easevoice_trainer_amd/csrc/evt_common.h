@@ -113,6 +113,22 @@ __device__ __forceinline__ float block_reduce_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// (int16) trunc(v), saturating where the C cast is undefined; NaN -> 0
+__device__ __forceinline__ int16_t trunc_s16(float v) {
+  const float t = fminf(fmaxf(truncf(v), -32768.f), 32767.f);
+  return v != v ? (int16_t)0 : (int16_t)(int)t;
+}
+
+// (v / pk) * ca + cb * v as numpy evaluates the float32 expression (the clip rescale of the `ssl` step and of the slicer):
+// every operation rounded to fp32 on its own, no fma may be formed from the product and the sum
+__device__ __forceinline__ float rescale_one(float v, float pk, float ca, float cb) {
+#pragma clang fp contract(off)
+  const float q = __fdiv_rn(v, pk);
+  const float a = __fmul_rn(q, ca);
+  const float b = __fmul_rn(cb, v);
+  return __fadd_rn(a, b);
+}
+
 // name of the kernel instantiation the last entry point launched on this host thread (bench.py's roofline leg reads
 // it right after a call to attribute HIP-event timings to the same names rocprofv3 reports)
 extern "C" void evt_set_last_tag(const char* fmt, ...);

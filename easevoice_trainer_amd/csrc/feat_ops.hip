@@ -248,21 +248,6 @@ __global__ __launch_bounds__(1024) void clip_peak_kernel(const float* __restrict
   }
 }
 
-// (int16) trunc(v), saturating where the C cast is undefined; NaN -> 0
-__device__ __forceinline__ int16_t trunc_s16(float v) {
-  const float t = fminf(fmaxf(truncf(v), -32768.f), 32767.f);
-  return v != v ? (int16_t)0 : (int16_t)(int)t;
-}
-
-// every operation rounded to fp32 on its own: no fma may be formed from the product and the sum
-__device__ __forceinline__ float rescale_one(float v, float pk, float ca, float cb) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(v, pk);
-  const float a = __fmul_rn(q, ca);
-  const float b = __fmul_rn(cb, v);
-  return __fadd_rn(a, b);
-}
-
 __global__ __launch_bounds__(256) void clip_rescale_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens, int N,
                                                            const float* __restrict__ peak, float c1, float c2, float c1b,
                                                            float c2b, float* __restrict__ f, int16_t* __restrict__ q) {

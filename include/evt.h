@@ -1077,6 +1077,47 @@ int evt_bert_embed_ln_rows(int32_t dtype, const int32_t* ids, const int32_t* tt,
                            int32_t types, const float* gamma, const float* beta, float eps, int32_t C, void* out,
                            void* stream);
 
+/* The audio slicer (src/audiokit/slicer/slicer.py, AudioService.slicer of the reference) on a ragged batch of recordings.
+ * The recordings lie in ONE packed fp32 buffer x of x_len elements: recording r is x[off[r] : off[r] + len[r]], off and
+ * len device int64, 1 <= len[r] < 2^31.  Nothing outside a recording's (a span's) own elements is read; an entry that
+ * does not lie inside [0, x_len) is skipped on the device (its outputs are not written).  No host synchronisation.
+ *
+ * evt_rms_frames_rows: get_rms (slicer.py:149-180).  Recording r has F_r = (len_r + 2 * (win / 2) - win) / hop + 1 frames
+ * (integer divisions); frame f is
+ *     rms[frame_off[r] + f] = fsqrt(fdiv(sum_k fmul(v_k, v_k), (float)win)),  v_k = x_r[f * hop - win / 2 + k], k < win,
+ * samples outside [0, len_r) taken as 0.  frame_off device int64 [nrec + 1]: the prefix sum of F_r from 0 to total_frames
+ * (the host's; rms has total_frames elements, nothing behind them is written).  The win additions are taken in the order
+ * of NumPy's pairwise float32 summation of a contiguous run of n values:
+ *     n < 8:    sequential;
+ *     n <= 128: eight accumulators r[j] = a[j], r[j] += a[i + j] for i = 8, 16, .. < n - n % 8, then
+ *               ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the n % 8 leftovers one by one;
+ *     n > 128:  n2 = n / 2, n2 -= n2 % 8, sum(a[:n2]) + sum(a[n2:]), recursively;
+ * every operation rounded to fp32 on its own, division and square root correctly rounded: a frame equals the reference's
+ * bit for bit, and it does not depend on the other recordings of the buffer.  One wave per frame.
+ * EVT_EINVAL for a NULL pointer or x_len, nrec, win, hop, total_frames <= 0; EVT_ENOTSUP for win > 8192. */
+int evt_rms_frames_rows(const float* x, int64_t x_len, const int64_t* off, const int64_t* len, int32_t nrec, int32_t win,
+                        int32_t hop, float* rms, const int64_t* frame_off, int64_t total_frames, void* stream);
+
+/* peak[s] = max_{i < n[s]} |x[src_off[s] + i]| for nspan spans of the buffer (src_off, n device int64): fp32 [nspan], a NaN
+ * if the span holds one (as np.abs(x).max()), 0 for n[s] == 0.  max_n: an upper bound of the n[s] the host knows (it sizes
+ * the grid; a larger span is still served).  A memset of peak and one launch.
+ * EVT_EINVAL for a NULL pointer, x_len <= 0, nspan <= 0 or > 65535, max_n < 0. */
+int evt_span_peak_rows(const float* x, int64_t x_len, const int64_t* src_off, const int64_t* n, int32_t nspan, int64_t max_n,
+                       float* peak, void* stream);
+
+/* The per-chunk arithmetic of AudioService.slicer (audio.py:172-178) for nspan chunks in one launch, in numpy's float32
+ * steps (fdiv / fmul / fadd, each rounded on its own), i < n[s]:
+ *     v = x[src_off[s] + i];  if (peak[s] > 1) v = fdiv(v, peak[s]);
+ *     w = fadd(fmul(fdiv(v, peak[s]), c1), fmul(c2, v))
+ *     out[dst_off[s] + i] = (int16) trunc(fmul(w, 32767.0f))
+ * c1 = (float)(normalize_max * alpha_mix), the product in double; c2 = (float)(1 - alpha_mix).  peak[s] == 0 is an all-zero
+ * chunk, where numpy casts a NaN (undefined): zeros are written for it.  out int16 of out_len elements; a chunk that does
+ * not fit into it is skipped.  The cast saturates and maps NaN to 0, as evt_clip_rescale_rows does.
+ * EVT_EINVAL for a NULL pointer, x_len or out_len <= 0, nspan <= 0 or > 65535, max_n < 0. */
+int evt_slice_pack_rows(const float* x, int64_t x_len, const int64_t* src_off, const int64_t* n, const int64_t* dst_off,
+                        const float* peak, float c1, float c2, int32_t nspan, int64_t max_n, int16_t* out, int64_t out_len,
+                        void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
