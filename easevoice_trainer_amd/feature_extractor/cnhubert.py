@@ -245,6 +245,13 @@ class HubertModel(nn.Module):
         return self.encoder(x, flens), frame_lens
 
 
+def rows_to_feats(hs, frame_lens):
+    """(last_hidden_state [B, Tmax, 768], frame counts) -> per row the tensor `CNHubert.__call__` returns and 4-cnhubert/<name>.pt
+    holds: [1, 768, T_b] float32 on the CPU, a transposed view's strides kept (channels-last in memory)"""
+    hs = hs.float().cpu()
+    return [hs[b:b + 1, :t].transpose(1, 2).clone(memory_format=torch.preserve_format) for b, t in enumerate(frame_lens)]
+
+
 class CNHubert:
     """src/easevoice/feature_extractor/cnhubert.py:16-32 on the GPU: `model(wav16k [n]) -> [1, 768, T]` float32 on the CPU,
     the tensor normalize.py:165,176 saves as 4-cnhubert/<name>.pt.  `weights`: a transformers HubertModel state_dict (or a
@@ -300,9 +307,7 @@ class CNHubert:
     @torch.no_grad()
     def batch(self, wavs16k):
         """what `__call__` returns for each clip -- [1, 768, T_b] float32 on the CPU -- from one ragged pass"""
-        hs, frame_lens = self.last_hidden_state_batch(wavs16k)
-        hs = hs.float().cpu()
-        return [hs[b:b + 1, :t].transpose(1, 2).clone(memory_format=torch.preserve_format) for b, t in enumerate(frame_lens)]
+        return rows_to_feats(*self.last_hidden_state_batch(wavs16k))
 
 
 def _read_state_dict(weights):

@@ -65,14 +65,15 @@ class FeatureWriter:
     feature_extractor.BertFeatures (or any object with phone_level_feature(input_ids, word2ph); `text_batch` takes a list of
     items through its phone_level_features_batch(ids_list, word2ph_list, group=))."""
 
-    def __init__(self, out_dir, hubert=None, bert=None):
-        self.out_dir, self.hubert, self.bert = out_dir, hubert, bert
+    def __init__(self, out_dir, hubert=None, bert=None, voice=None):
+        self.out_dir, self.hubert, self.bert, self.voice = out_dir, hubert, bert, voice
         self.bert_dir = os.path.join(out_dir, "3-bert")
         self.hubert_dir = os.path.join(out_dir, "4-cnhubert")
         self.wav_dir = os.path.join(out_dir, "5-wav32k")
         for d in (self.bert_dir, self.hubert_dir, self.wav_dir):
             os.makedirs(d, exist_ok=True)
         self._text_lines = []
+        self._codes = {}                 # name -> semantic codes kept by ssl_batch(tokens=True) for write_semantic
 
     def ssl(self, name, audio32k) -> bool:
         """normalize.py:_name2go: False when the features came out non-finite (the reference then retries in fp32)"""
@@ -116,15 +117,24 @@ class FeatureWriter:
         q = q.cpu().numpy()
         return peak.cpu().tolist(), [q[b, :lens[b]] for b in range(len(clips))], rows16, list(packed.lengths)
 
-    def ssl_batch(self, names, clips32k) -> list:
+    def ssl_batch(self, names, clips32k, tokens=False) -> list:
         """`ssl` for several clips with ONE pass of the model over the ragged batch (hubert: feature_extractor.CNHubert, or
         any object with its `device` and `batch((rows [B, N], lengths))`).  Per name what `ssl` returns: True for a name
         whose feature file exists (skipped before anything is uploaded) and for a clip the reference skips (peak above
         2.2, nothing written), False for a non-finite peak or non-finite features (nothing written), True after writing
         4-cnhubert/<name>.pt and 5-wav32k/<name>.  The int16 file is byte for byte `ssl`'s; the features differ from
-        `ssl`'s within fp32 rounding (the resampler accumulates in fp32, resample_half in float64)."""
+        `ssl`'s within fp32 rounding (the resampler accumulates in fp32, resample_half in float64).
+        tokens=True (needs `voice`, an object with SoVITSVoice.extract_latent_rows, and a hubert with
+        last_hidden_state_batch; ValueError otherwise, before anything is uploaded): the features of the items that are
+        written also go through voice.extract_latent_rows while they are on the device -- as the float32 values that are
+        saved, so the codes are the codes of the file -- and are kept per name for `write_semantic`.  Items that are
+        skipped or refused get no codes; the return value and the files are the same."""
         from scipy.io import wavfile
 
+        if tokens and (self.voice is None or not hasattr(self.voice, "extract_latent_rows")
+                       or not hasattr(self.hubert, "last_hidden_state_batch")):
+            raise ValueError("ssl_batch(tokens=True) needs a voice with extract_latent_rows and a hubert with "
+                             "last_hidden_state_batch")
         names = list(names)
         if len(names) != len(clips32k):
             raise ValueError(f"{len(names)} names for {len(clips32k)} clips")
@@ -144,12 +154,25 @@ class FeatureWriter:
             return done
         if len(keep) < len(todo):
             rows16 = rows16[torch.tensor(keep, device=rows16.device)]
-        feats = self.hubert.batch((rows16, [lens16[j] for j in keep]))
-        for j, ssl in zip(keep, feats):
+        codes = None
+        if tokens:
+            from ..inference.semantic import codes_to_host
+            from .cnhubert import rows_to_feats
+
+            with torch.no_grad():
+                hs, frame_lens = self.hubert.last_hidden_state_batch((rows16, [lens16[j] for j in keep]))
+                hs = hs.float().contiguous()                                    # the values CNHubert.batch saves
+                codes = codes_to_host(self.voice.extract_latent_rows(hs, frame_lens))
+            feats = rows_to_feats(hs, frame_lens)                               # what CNHubert.batch returns
+        else:
+            feats = self.hubert.batch((rows16, [lens16[j] for j in keep]))
+        for n, (j, ssl) in enumerate(zip(keep, feats)):
             i = todo[j]
             if not bool(torch.isfinite(ssl).all()):
                 done[i] = False
                 continue
+            if codes is not None:
+                self._codes[names[i]] = codes[n]
             wavfile.write(os.path.join(self.wav_dir, names[i]), 32000, wav16[j])
             torch.save(ssl, os.path.join(self.hubert_dir, names[i] + ".pt"))
         return done
@@ -186,6 +209,27 @@ class FeatureWriter:
                 torch.save(feat.float().clone(), os.path.join(self.bert_dir, items[i][0] + ".pt"))
         for name, phones, word2ph, norm_text, _language, _ids in items:
             self._text_lines.append("%s\t%s\t%s\t%s" % (name, " ".join(phones), word2ph, norm_text))
+
+    def write_semantic(self, names, group=16) -> int:
+        """the `token` step (normalize.py:181-211): 6-name2semantic.tsv in the order of `names`, in write_semantic_tsv's
+        format.  A name whose codes `ssl_batch(tokens=True)` kept takes those; any other name with a 4-cnhubert/<name>.pt is
+        tokenised from the file, in groups of at most `group` (inference/semantic.py::codes_of_files, needs `voice`); a name
+        with neither is skipped.  -> the number of lines written."""
+        from ..inference.semantic import codes_of_files, semantic_line
+
+        names = list(names)
+        path = lambda n: os.path.join(self.hubert_dir, n + ".pt")
+        files = [n for n in dict.fromkeys(names) if n not in self._codes and os.path.exists(path(n))]
+        got = dict(self._codes)
+        if files:
+            if self.voice is None:
+                raise ValueError("write_semantic needs a voice to tokenise feature files")
+            device = getattr(self.voice, "device", None) or getattr(self.hubert, "device", "cuda:0")
+            got.update(zip(files, codes_of_files(self.voice.extract_latent_rows, [path(n) for n in files], group, device)))
+        lines = [semantic_line(n, got[n]) for n in names if n in got]
+        with open(os.path.join(self.out_dir, "6-name2semantic.tsv"), "w", encoding="utf8") as f:
+            f.write("\n".join(["item_name\tsemantic_audio"] + lines) + "\n")
+        return len(lines)
 
     def close(self):
         with open(os.path.join(self.out_dir, "2-name2text.txt"), "w", encoding="utf8") as f:

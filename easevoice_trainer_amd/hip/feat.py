@@ -165,6 +165,75 @@ def bert_embed_ln_rows(ids, lens, word, pos, type_emb, gamma, beta, eps, dtype, 
     return out
 
 
+SEMANTIC_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+SEMANTIC_MAX_D = 1152     # EVT_SEMANTIC_MAX_D
+
+
+def make_proj_image(weight):
+    """ssl_proj.weight [O, C, taps] -> the fp32 image [taps * C, O] evt_semantic_codes_rows reads: row tap * C + c, column o"""
+    if not torch.is_tensor(weight) or weight.dim() != 3:
+        raise L.EvtError("make_proj_image: a convolution weight [O, C, taps] expected")
+    o, c, taps = weight.shape
+    return weight.detach().float().permute(2, 1, 0).reshape(taps * c, o).contiguous()
+
+
+def rvq_norms(embed):
+    """ee[k] = |embed[k]|^2 (evt_rvq_norms)"""
+    K, D = embed.shape
+    ee = torch.empty(K, dtype=torch.float32, device=embed.device)
+    L.check(L.lib().evt_rvq_norms(L.ptr(embed), L.ptr(ee), K, D, L.stream_ptr()), "evt_rvq_norms")
+    return ee
+
+
+def semantic_codes_rows(hs, frames, proj_image, bias, embed, ee=None):
+    """hs [B, Tmax, D] hidden states (fp32 or the build's 16-bit type, contiguous, on the GPU), frames: B frame counts (a list
+    or a tensor; a device tensor costs one read-back) -> (codes, offsets): the packed int64 codes of all rows and the
+    int64 [B + 1] exclusive prefix sum of frames[b] // 2 on the device; row b's codes are codes[offsets[b]: offsets[b + 1]].
+    proj_image fp32 [2 D, D] (`make_proj_image(ssl_proj.weight)`), bias fp32 [D], embed fp32 [K, D], ee fp32 [K] (computed by
+    evt_rvq_norms when None, one more launch).  One upload of the frame counts and offsets and ONE launch of
+    evt_semantic_codes_rows (include/evt.h has the definition): the k = 2, stride 2 projection and the nearest code, nothing behind a row's frames read, a row's codes bit for bit those of the row alone."""
+    if not torch.is_tensor(hs) or hs.dim() != 3 or not hs.is_cuda or not hs.is_contiguous():
+        raise L.EvtError("semantic_codes_rows: contiguous hidden states [B, Tmax, D] on the GPU expected")
+    B, Tmax, D = hs.shape
+    if torch.is_tensor(frames):
+        frames = frames.reshape(-1).tolist()
+    frames = [int(t) for t in frames]
+    if len(frames) != B:
+        raise L.EvtError(f"semantic_codes_rows: {len(frames)} frame counts for {B} rows")
+    if B < 1 or Tmax < 1 or D % 64 or not 64 <= D <= SEMANTIC_MAX_D or any(t < 0 or t > Tmax for t in frames):
+        raise L.EvtError(f"semantic_codes_rows: rows {tuple(hs.shape)} with frame counts {frames} are not served")
+    K = embed.size(0) if torch.is_tensor(embed) and embed.dim() == 2 else 0
+    for name, t, shape in (("proj_image", proj_image, (2 * D, D)), ("bias", bias, (D,)), ("embed", embed, (K, D)),
+                           ("ee", ee, (K,))):
+        if name == "ee" and t is None:
+            continue
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != hs.device or tuple(t.shape) != shape
+                or not t.is_contiguous() or t.data_ptr() % 16 or K < 1):
+            raise L.EvtError(f"semantic_codes_rows: {name} must be contiguous, 16-byte aligned float32 {shape} on {hs.device}")
+    if torch.is_grad_enabled() and hs.requires_grad:
+        raise L.EvtError("semantic_codes_rows is inference only: run it under torch.no_grad()")
+    if ee is None:
+        ee = rvq_norms(embed)
+    off = [0]
+    for t in frames:
+        off.append(off[-1] + t // 2)
+    total = off[-1]
+    # one int32 buffer for one upload: the int64 offsets (as pairs of words) in front, the frame counts behind them
+    host = torch.empty(2 * (B + 1) + B, dtype=torch.int32)
+    host[: 2 * (B + 1)].view(torch.int64).copy_(torch.tensor(off, dtype=torch.int64))
+    host[2 * (B + 1):] = torch.tensor(frames, dtype=torch.int32)
+    frames_host = host[2 * (B + 1):]
+    dev = host.to(hs.device)
+    frames_dev, offsets = dev[2 * (B + 1):], dev[: 2 * (B + 1)].view(torch.int64)
+    codes = torch.empty(total, dtype=torch.int64, device=hs.device)
+    L.check(_rows_entry("evt_semantic_codes_rows", SEMANTIC_ARGTYPES)(
+        L.dt_of(hs), hs.data_ptr(), frames_dev.data_ptr(), frames_host.data_ptr(), offsets.data_ptr(), B, Tmax, D, K,
+        proj_image.data_ptr(), bias.data_ptr(), embed.data_ptr(), ee.data_ptr(), codes.data_ptr() if total else None, total,
+        L.stream_ptr()), "evt_semantic_codes_rows")
+    return codes, offsets
+
+
 def add_layernorm(x, r, gamma, beta, eps):
     """LayerNorm(x + r) over the last axis (r may be None): evt_add_layernorm_fwd, statistics discarded"""
     x = x.contiguous()

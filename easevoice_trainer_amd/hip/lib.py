@@ -228,7 +228,8 @@ def lib():
         for name in ("evt_resunit_fwd_multi_lens", "evt_resunit_wide_fwd_lens", "evt_mask_tail", "evt_resample_rows",
                      "evt_resample_pack_rows", "evt_hubert_front_rows", "evt_clip_rescale_rows", "evt_phone_expand_rows",
                      "evt_bert_embed_ln_rows", "evt_ref_spec_rows", "evt_mish_rows_fwd", "evt_glu_res_rows_fwd",
-                     "evt_mean_rows", "evt_rms_frames_rows", "evt_span_peak_rows", "evt_slice_pack_rows"):
+                     "evt_mean_rows", "evt_rms_frames_rows", "evt_span_peak_rows", "evt_slice_pack_rows",
+                     "evt_semantic_codes_rows"):
             getattr(_lib, name).restype = C.c_int
         _lib.evt_hubert_front_ws_floats.restype = C.c_int64
     return _lib

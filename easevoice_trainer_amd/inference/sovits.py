@@ -76,3 +76,10 @@ class SoVITSVoice:
     def extract_latent(self, ssl):
         L.set_half(self.dtype)
         return self.model.extract_latent(ssl.to(self.device))
+
+    @torch.no_grad()
+    def extract_latent_rows(self, hs, frames):
+        """SynthesizerTrn.extract_latent_rows: hidden states [B, Tmax, 768] as CNHubert.last_hidden_state_batch leaves them
+        (on this voice's device, fp32 or 16-bit) + B frame counts -> a list of B 1-D int64 code tensors from one launch"""
+        L.set_half(hs.dtype if torch.is_tensor(hs) and L.is_half(hs.dtype) else self.dtype)
+        return self.model.extract_latent_rows(hs, frames)

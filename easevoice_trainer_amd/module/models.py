@@ -914,6 +914,42 @@ class SynthesizerTrn(nn.Module, _ComputeDtype):
         return codes.transpose(0, 1)
 
     @torch.no_grad()
+    def extract_latent_rows(self, hs, frames):
+        """`extract_latent` for a ragged batch as CN-HuBERT leaves it: hs [B, Tmax, 768] channels-last (fp32 or the build's
+        16-bit type) on the model's device, frames: B frame counts -> a list of B 1-D int64 code tensors (frames[b] // 2
+        codes, views of one packed buffer) from ONE launch (hip/feat.py::semantic_codes_rows): no transposed copy, no codes
+        for the padding, a row's codes those of the row alone.  The projection image and the codebook's norms are kept and
+        rebuilt when the live tensors were replaced or written (torch's version counters, as FrozenBank.prepare).  The
+        codebook must be initialised: this path never runs the k-means of a first training batch."""
+        from ..hip import feat as HF
+
+        cb = self.quantizer.vq.layers[0]._codebook
+        w, bias, embed = self.ssl_proj.weight, self.ssl_proj.bias, cb.embed
+        if self.semantic_frame_rate != "25hz":
+            raise L.EvtError("extract_latent_rows serves the 25 Hz quantizer (ssl_proj with k = 2, stride 2)")
+        if not torch.is_tensor(hs) or hs.dim() != 3:
+            raise L.EvtError("extract_latent_rows: hidden states [B, Tmax, 768] expected")
+        if hs.size(2) != embed.size(1):
+            raise L.EvtError(f"extract_latent_rows: features of width {hs.size(2)}, the quantizer takes {embed.size(1)}")
+        if hs.device != embed.device:
+            raise L.EvtError(f"extract_latent_rows: features on {hs.device}, the model on {embed.device}")
+        frames = [int(t) for t in (frames.reshape(-1).tolist() if torch.is_tensor(frames) else frames)]   # one read-back
+        if len(frames) != hs.size(0):
+            raise L.EvtError(f"extract_latent_rows: {len(frames)} frame counts for {hs.size(0)} rows")
+        stamp = tuple((t.data_ptr(), t._version) for t in (w, bias, embed, cb.inited))
+        cache = getattr(self, "_rows_cache", None)
+        if cache is None or cache[0] != stamp:
+            if not bool(cb.inited.cpu().item()):
+                raise L.EvtError("extract_latent_rows: the codebook is not initialised (load a trained quantizer first)")
+            al = lambda t: t if t.data_ptr() % 16 == 0 else t.clone()      # the kernel loads 16 bytes at a time
+            e = al(embed.detach().float().contiguous())
+            cache = (stamp, HF.make_proj_image(w), al(bias.detach().float().contiguous()), e, HF.rvq_norms(e))
+            object.__setattr__(self, "_rows_cache", cache)
+        _stamp, image, b32, e32, ee = cache
+        codes, _off = HF.semantic_codes_rows(hs.contiguous(), frames, image, b32, e32, ee)
+        return list(torch.split(codes, [t // 2 for t in frames]))
+
+    @torch.no_grad()
     def decode(self, codes, text, refer, noise_scale=0.5, speed=1, noise=None, style=None):
         """Inference: semantic codes [1, B, Tc] + phoneme ids [B, Tt] + reference spectrogram(s) [B, spec, Tr] (a list
         averages the style vectors) -> waveform [B, 1, T*hop] (models.py:974-1013): prior from the text/ssl encoder,

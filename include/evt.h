@@ -1118,6 +1118,31 @@ int evt_slice_pack_rows(const float* x, int64_t x_len, const int64_t* src_off, c
                         const float* peak, float c1, float c2, int32_t nspan, int64_t max_n, int16_t* out, int64_t out_len,
                         void* stream);
 
+/* Semantic codes of a ragged batch of CN-HuBERT hidden states (models.py:1015-1018: ssl_proj, a Conv1d D -> D with k = 2 and
+ * stride 2, + the nearest code of the frozen codebook, n_q = 1) in one launch, fp32 throughout on the fp32-input MFMA.
+ *   hs [B][Tmax][D] channels-last of dtype (fp32 or the build's 16-bit type, widened on load); frames device int32 [B];
+ *   offsets device int64 [B + 1]: the exclusive prefix sum of frames[b] / 2 (integer division), offsets[B] = total;
+ *   proj_image fp32 [2 D][D]: row tap * D + c, column o holds ssl_proj.weight[o][c][tap]; bias fp32 [D]; embed fp32 [K][D];
+ *   ee fp32 [K] from evt_rvq_norms.
+ * Row b gets frames[b] / 2 codes at codes[offsets[b] ..] (int64, `total` elements; an odd last frame is dropped):
+ *     h_t = bias + sum_{tap, c} hs[b][2 t + tap][c] * proj_image[tap * D + c][.],   xx = sum_d h_t[d]^2,
+ *     code = the smallest k among the maxima of -((xx - 2 h_t . embed[k]) + ee[k]), 0 when no k has one (an all-NaN frame):
+ * evt_rvq_select's decision.  A block owns EVT_SEMANTIC_TILE code frames of one row counted from its frame 0; h, the dots
+ * and the code vectors are never written to memory, and every sum has an order fixed by D and K alone, so a row's codes are
+ * bit for bit those of nseq = 1 with any Tmax >= frames[b].  Nothing at or behind frame frames[b] of a row is read (the
+ * device clamps frames[b] to 0 .. Tmax), nothing of a row with fewer than two frames; no code is written outside `total`.
+ * frames_host (may be NULL): the host's copy of frames, checked here.
+ * EVT_EINVAL (nothing launched) for a NULL pointer other than frames_host (codes when total > 0), B <= 0 or > 65535,
+ * Tmax <= 0, K <= 0, total < 0, D not a multiple of 64 or above EVT_SEMANTIC_MAX_D (h must fit LDS), hs / proj_image / bias /
+ * embed not 16-byte aligned, a dtype the build does not serve, a frames_host[b] outside 0 .. Tmax.  total == 0 is EVT_OK
+ * without a launch. */
+#define EVT_SEMANTIC_TILE 32
+#define EVT_SEMANTIC_MAX_D 1152
+int evt_semantic_codes_rows(int32_t dtype, const void* hs, const int32_t* frames, const int32_t* frames_host,
+                            const int64_t* offsets, int32_t B, int32_t Tmax, int32_t D, int32_t K, const float* proj_image,
+                            const float* bias, const float* embed, const float* ee, int64_t* codes, int64_t total,
+                            void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
