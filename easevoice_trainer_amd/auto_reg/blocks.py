@@ -32,8 +32,8 @@ def _res_drop_ln_fwd(x, y, gamma, beta, p, site, eps):
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     L.check(L.lib().evt_res_dropout_ln_fwd(L.dt_of(x), L.ptr(x), L.ptr(y), L.ptr(gamma), L.ptr(beta), None, x.size(-2),
-                                           C.c_float(p), L.ptr(rng_counter(x.device)), C.c_uint32(site), L.ptr(out),
-                                           L.ptr(mean), L.ptr(rstd), C.c_int64(rows), Cc, C.c_float(eps), L.stream_ptr()),
+                                           float(p), L.ptr(rng_counter(x.device)), int(site), L.ptr(out),
+                                           L.ptr(mean), L.ptr(rstd), rows, Cc, float(eps), L.stream_ptr()),
             "evt_res_dropout_ln_fwd")
     return out, mean, rstd
 
@@ -53,9 +53,9 @@ def _res_drop_ln_bwd(x, y, gamma, beta_param, gamma_param, dout, mean, rstd, p, 
         dgb = torch.zeros(2, Cc, dtype=torch.float32, device=x.device)
         dgamma, dbeta = dgb[0], dgb[1]
     L.check(L.lib().evt_res_dropout_ln_bwd(L.dt_of(x), L.ptr(x), L.ptr(y), L.ptr(gamma), L.ptr(dout), L.ptr(mean),
-                                           L.ptr(rstd), None, x.size(-2), C.c_float(p), L.ptr(rng_counter(x.device)),
-                                           C.c_uint32(site), L.ptr(dx), L.ptr(dy), L.ptr(dgamma), L.ptr(dbeta),
-                                           C.c_int64(rows), Cc, L.stream_ptr()), "evt_res_dropout_ln_bwd")
+                                           L.ptr(rstd), None, x.size(-2), float(p), L.ptr(rng_counter(x.device)),
+                                           int(site), L.ptr(dx), L.ptr(dy), L.ptr(dgamma), L.ptr(dbeta),
+                                           rows, Cc, L.stream_ptr()), "evt_res_dropout_ln_bwd")
     return dx, (dy if dy is not None else dx), (None if sunk else dgamma), (None if sunk else dbeta)
 
 

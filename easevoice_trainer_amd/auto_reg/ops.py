@@ -62,7 +62,7 @@ class AddLayerNormFn(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         L.check(L.lib().evt_add_layernorm_fwd(L.dt_of(x), L.ptr(x), L.ptr(r), L.ptr(gamma), L.ptr(beta), L.ptr(y),
-                                              L.ptr(mean), L.ptr(rstd), C.c_int64(rows), C_, C.c_float(eps),
+                                              L.ptr(mean), L.ptr(rstd), rows, C_, float(eps),
                                               L.stream_ptr()), "evt_add_layernorm_fwd")
         ctx.save_for_backward(x, r, gamma, mean, rstd)
         return y
@@ -77,7 +77,7 @@ class AddLayerNormFn(torch.autograd.Function):
         dgamma = torch.zeros(C_, dtype=torch.float32, device=x.device)
         dbeta = torch.zeros(C_, dtype=torch.float32, device=x.device)
         L.check(L.lib().evt_add_layernorm_bwd(L.dt_of(x), L.ptr(x), L.ptr(r), L.ptr(gamma), L.ptr(dy), L.ptr(mean),
-                                              L.ptr(rstd), L.ptr(dxr), L.ptr(dgamma), L.ptr(dbeta), C.c_int64(rows), C_,
+                                              L.ptr(rstd), L.ptr(dxr), L.ptr(dgamma), L.ptr(dbeta), rows, C_,
                                               L.stream_ptr()), "evt_add_layernorm_bwd")
         return dxr, (dxr if r is not None else None), dgamma, dbeta, None
 
@@ -96,8 +96,8 @@ class CrossEntropySumFn(torch.autograd.Function):
         loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
         hits = torch.zeros(2, dtype=torch.int32, device=logits.device)
         L.check(L.lib().evt_ce_sum_fwd_bwd_ld(L.dt_of(logits), L.ptr(logits), L.ptr(targets.contiguous()), L.ptr(dlogits),
-                                              L.ptr(loss), L.ptr(hits), C.c_int64(rows), V, C.c_int64(ld), int(topk),
-                                              C.c_int64(int(ignore_index)), C.c_float(1.0), L.stream_ptr()),
+                                              L.ptr(loss), L.ptr(hits), rows, V, ld, int(topk),
+                                              int(ignore_index), 1.0, L.stream_ptr()),
                 "evt_ce_sum_fwd_bwd_ld")
         ctx.save_for_backward(dlogits)
         ctx.mark_non_differentiable(hits)
@@ -123,8 +123,8 @@ class CrossEntropyRowsFn(torch.autograd.Function):
         row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
         hits = torch.zeros(2, dtype=torch.int32, device=logits.device)
         L.check(L.lib().evt_ce_rows_fwd_bwd_ld(L.dt_of(logits), L.ptr(logits), L.ptr(targets.contiguous()), L.ptr(dlogits),
-                                               L.ptr(row_loss), L.ptr(hits), C.c_int64(rows), V, C.c_int64(ld), int(topk),
-                                               C.c_int64(int(ignore_index)), L.stream_ptr()), "evt_ce_rows_fwd_bwd_ld")
+                                               L.ptr(row_loss), L.ptr(hits), rows, V, ld, int(topk),
+                                               int(ignore_index), L.stream_ptr()), "evt_ce_rows_fwd_bwd_ld")
         ctx.save_for_backward(dlogits)
         ctx.mark_non_differentiable(hits)
         return row_loss, hits

@@ -102,7 +102,7 @@ class _Session:
         N, K = w.shape
         fn = self.gemv_fn
         L.check(getattr(L.lib(), fn)(L.dt_of(w), L.ptr(w), L.ptr(bias), L.ptr(a), L.ptr(r), L.ptr(g), L.ptr(b),
-                                     C.c_float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu), L.stream_ptr()), fn)
+                                     float(eps), L.ptr(x_out), L.ptr(y), self.B, N, K, int(relu), L.stream_ptr()), fn)
 
     def step_launches(self, W, sp, noise, pe, fused_qkv=False):
         """one token: 24 x (in-projection, cache attention, out-proj, ffn1, ffn2) + logits + the end of the step (sampling
@@ -165,7 +165,7 @@ class DecodeSession(_Session):
         """sampling, append, embedding of the new token and the counter update: one launch for one sequence, three for a
         batch (the counters may only move after every row's workgroup has read them)"""
         lib = L.lib()
-        xs = C.c_float(self.model.ar_audio_position.x_scale)
+        xs = float(self.model.ar_audio_position.x_scale)
         if self.B == 1:
             L.check(lib.evt_dec_sample_embed(
                 C.byref(sp), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.ctr), L.ptr(noise), L.ptr(self.stop),
@@ -193,7 +193,7 @@ class DecodeSession(_Session):
 
     def _qkv_attn(self, i, w, a, r, g, b, eps, x_out):
         L.check(L.lib().evt_dec_qkv_attn(L.dt_of(self.kc), L.ptr(w["wqkv"]), L.ptr(w["bqkv"]), L.ptr(a), L.ptr(r), L.ptr(g),
-                                         L.ptr(b), C.c_float(eps), L.ptr(x_out), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
+                                         L.ptr(b), float(eps), L.ptr(x_out), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
                                          L.ptr(self.ctr), L.ptr(self.att), self.B, self.H, self.E // self.H, self.Lmax,
                                          L.ptr(self.x_lens), self.x_len, L.stream_ptr()), "evt_dec_qkv_attn")
 
@@ -269,7 +269,7 @@ class StreamSession(_Session):
         L.check(getattr(L.lib(), fn)(
             C.byref(sp), L.ptr(self.row_sample), L.ptr(self.logits), L.ptr(self.y), L.ptr(self.rstate), L.ptr(noise),
             L.ptr(self.stop), None, L.ptr(self.row_seed), L.ptr(mask), L.ptr(W.emb), L.ptr(pe), L.ptr(W.alpha),
-            C.c_float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), *logp, self.B, self.E, pe.size(0), dpos,
+            float(self.model.ar_audio_position.x_scale), L.ptr(self.xa), *logp, self.B, self.E, pe.size(0), dpos,
             L.stream_ptr()), fn)
 
     def _end_step(self, W, sp, noise, pe):

@@ -18,6 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libevt_hip.so")
 LIB_F16 = os.path.join(HERE, "libevt_hip_f16.so")
+HEADER = os.path.join(HERE, "..", "include", "evt.h")   # the C ABI: hashed into evt_version(), declared to ctypes by hip/lib.py
 HALF_BUILDS = {"bf16": (OBJ, LIB, []), "f16": (os.path.join(HERE, "csrc", "_obj_f16"), LIB_F16, ["-DEVT_HALF_F16"])}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -37,7 +38,7 @@ def _sha(paths, extra=""):
 
 def _headers():
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "evt.h"))
+    hdrs.append(HEADER)
     return hdrs
 
 

@@ -4,7 +4,6 @@ has the operator's definition).  The int16 conversion and the silence interval a
 (inference/tts.py:878-908); the resampler is resampy's kaiser_best filter as feature_extractor/normalize.py restates it for
 the ratio 1/2, written for any ratio: at 1/2 its taps are normalize._half_band_taps() and the operator is resample_half.
 The filter's constants are taken from there."""
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import List
@@ -126,7 +125,7 @@ def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, inter
         raise L.EvtError(f"resample_pack: {nseq} lengths >= 0 and mul >= 1 expected, got {lens} and mul = {mul}")
     if lens_dev is None:
         lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
-    _conv._check_lens(x, lens_dev, mul)
+    L.check_lens("resample_pack", x, lens_dev, mul)
     up, down = rate_ratio(in_rate, out_rate)
     if interval < 0:
         raise L.EvtError(f"interval = {interval} must be >= 0")
@@ -146,7 +145,7 @@ def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, inter
     table, j_pad = (None, 0) if up == down == 1 else (phase_table(up, down, x.device), table_shape(up, down)[1])
     e0 = _conv._t0()
     L.check(L.lib().evt_resample_pack_rows(L.dt_of(x), L.ptr(x), L.ptr(lens_dev), mul, nseq, length, up, down, L.ptr(table),
-                                           j_pad, code, L.ptr(data), C.c_int64(total), L.ptr(off_dev), gap, L.stream_ptr()),
+                                           j_pad, code, L.ptr(data), total, L.ptr(off_dev), gap, L.stream_ptr()),
             "evt_resample_pack_rows")
     if e0 is not None:
         _conv._t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
@@ -187,7 +186,7 @@ def ref_spec_rows(x, lens, hop=640, bins=704, lens_dev=None):
                          f"too few for the reflect padding of {(REF_NFFT - hop) // 2} and one frame")
     if lens_dev is None:
         lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
-    _conv._check_lens(x, lens_dev, 1)
+    L.check_lens("ref_spec_rows", x, lens_dev)
     from ..module.mel_processing import _window
 
     window = _window(REF_NFFT, x.device)              # the tensor spectrogram_torch hands its kernel

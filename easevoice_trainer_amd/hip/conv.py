@@ -794,7 +794,7 @@ class ConvFn(torch.autograd.Function):
             # read from the sign of the activated tensor
             xa = torch.empty_like(x)
             e0 = _t0()
-            L.check(L.lib().evt_leaky_relu(L.dt_of(x), L.ptr(x), C.c_float(in_slope), L.ptr(xa), C.c_int64(x.numel()),
+            L.check(L.lib().evt_leaky_relu(L.dt_of(x), L.ptr(x), float(in_slope), L.ptr(xa), x.numel(),
                                            L.stream_ptr()), "evt_leaky_relu")
             if e0 is not None:
                 _t1_elt(e0, "lrelu_kernel", 2 * x.numel() * x.element_size(), slot.module)
@@ -819,8 +819,8 @@ class ConvFn(torch.autograd.Function):
             # wide layers: apply the activation derivative once, both backward GEMMs then take plain operands
             dy_eff = torch.empty_like(dy)
             e0 = _t0()
-            L.check(L.lib().evt_dact_mul(L.dt_of(dy), L.ptr(dy), L.ptr(y), int(out_act), C.c_float(out_slope),
-                                         L.ptr(dy_eff), C.c_int64(dy.numel()), L.stream_ptr()), "evt_dact_mul")
+            L.check(L.lib().evt_dact_mul(L.dt_of(dy), L.ptr(dy), L.ptr(y), int(out_act), float(out_slope),
+                                         L.ptr(dy_eff), dy.numel(), L.stream_ptr()), "evt_dact_mul")
             if e0 is not None:
                 _t1_elt(e0, "dact_mul_kernel", 3 * dy.numel() * dy.element_size(), slot.module)
             dy, y, out_act, out_slope = dy_eff, None, L.ACT_NONE, 1.0
@@ -877,8 +877,8 @@ def _t1_unit(e0, m1, m2, x):
 def _lrelu(x, slope, owner=None):
     out = torch.empty_like(x)
     e0 = _t0()
-    L.check(L.lib().evt_leaky_relu(L.dt_of(x), L.ptr(x), C.c_float(slope), L.ptr(out), C.c_int64(x.numel()),
-                                   L.stream_ptr()), "evt_leaky_relu")
+    L.check(L.lib().evt_leaky_relu(L.dt_of(x), L.ptr(x), float(slope), L.ptr(out), x.numel(), L.stream_ptr()),
+            "evt_leaky_relu")
     if e0 is not None:
         _t1_elt(e0, "lrelu_kernel", 2 * x.numel() * x.element_size(), owner)
     return out
@@ -886,8 +886,8 @@ def _lrelu(x, slope, owner=None):
 
 def _add3(a, b, c, scale, out, owner):
     e0 = _t0()
-    L.check(L.lib().evt_add3_scale(L.dt_of(a), L.ptr(a), L.ptr(b), L.ptr(c), C.c_float(scale), L.ptr(out),
-                                   C.c_int64(a.numel()), L.stream_ptr()), "evt_add3_scale")
+    L.check(L.lib().evt_add3_scale(L.dt_of(a), L.ptr(a), L.ptr(b), L.ptr(c), float(scale), L.ptr(out), a.numel(),
+                                   L.stream_ptr()), "evt_add3_scale")
     if e0 is not None:
         _t1_elt(e0, "add3_scale_kernel", (2 + (b is not None) + (c is not None)) * a.numel() * a.element_size(), owner)
     return out
@@ -955,7 +955,7 @@ class ResUnitFn(torch.autograd.Function):
                 m1, m2 = s1.module, s2.module
                 dmid, dx = torch.empty_like(dy), torch.empty_like(dy)
                 e0 = _t0()
-                L.check(L.lib().evt_resunit_wide_bwd_data(C.byref(wide), L.ptr(dy), C.c_float(1.0), L.ptr(xa), L.ptr(mid_a),
+                L.check(L.lib().evt_resunit_wide_bwd_data(C.byref(wide), L.ptr(dy), 1.0, L.ptr(xa), L.ptr(mid_a),
                                                           L.ptr(s1.alt), L.ptr(s2.alt), L.ptr(dmid), L.ptr(dx),
                                                           L.stream_ptr()), "evt_resunit_wide_bwd_data")
                 if e0 is not None:
@@ -1020,9 +1020,9 @@ def resunit_bwd(s1, s2, dy, xa, mid_a, slope, dy_scale=1.0):
         db2 = m2.bias.grad if m2.bias is not None else None
         ws = bank.scratch()
     e0 = _t0()
-    L.check(lib.evt_resunit_bwd(C.byref(fused), L.ptr(dy), C.c_float(dy_scale), L.ptr(xa), L.ptr(mid_a), L.ptr(s1.alt),
+    L.check(lib.evt_resunit_bwd(C.byref(fused), L.ptr(dy), float(dy_scale), L.ptr(xa), L.ptr(mid_a), L.ptr(s1.alt),
                                 L.ptr(s2.alt), L.ptr(dx), L.ptr(dmid), L.ptr(dw1), L.ptr(dw2), L.ptr(db1), L.ptr(db2),
-                                L.ptr(ws), C.c_int64(ws.numel() if ws is not None else 0), L.stream_ptr()),
+                                L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()),
             "evt_resunit_bwd")
     if e0 is not None:
         _t1_unit_bwd(e0, m1, m2, xa, wg_in)
@@ -1042,7 +1042,7 @@ def mask_tail(x, lens, mul=1, owner=None):
     tails of a ragged batch in front of a consumer that has no masked load (csrc/elementwise.hip::evt_mask_tail)"""
     if x.dim() != 3 or not x.is_contiguous():
         raise L.EvtError("mask_tail takes a contiguous [nseq, L, C] tensor")
-    _check_lens(x, lens, mul)
+    L.check_lens("mask_tail", x, lens, mul)
     e0 = _t0()
     L.check(L.lib().evt_mask_tail(L.dt_of(x), L.ptr(x), L.ptr(lens), int(mul), x.size(0), x.size(1), x.size(2),
                                   L.stream_ptr()), "evt_mask_tail")
@@ -1058,8 +1058,8 @@ def resample_rows(x, in_lens, out_lens, Lout, owner=None):
     (csrc/elementwise.hip::evt_resample_rows)"""
     if x.dim() != 3 or not x.is_contiguous() or int(Lout) < 1:
         raise L.EvtError("resample_rows takes a contiguous [nseq, Lin, C] tensor and Lout >= 1")
-    _check_lens(x, in_lens, 1)
-    _check_lens(x, out_lens, 1)
+    L.check_lens("resample_rows", x, in_lens)
+    L.check_lens("resample_rows", x, out_lens)
     y = torch.empty(x.size(0), int(Lout), x.size(2), dtype=x.dtype, device=x.device)
     e0 = _t0()
     L.check(L.lib().evt_resample_rows(L.dt_of(x), L.ptr(x), L.ptr(in_lens), L.ptr(out_lens), x.size(0), x.size(1),
@@ -1067,14 +1067,6 @@ def resample_rows(x, in_lens, out_lens, Lout, owner=None):
     if e0 is not None:
         _t1_elt(e0, "resample_rows_kernel", (x.numel() + y.numel()) * x.element_size(), owner)
     return y
-
-
-def _check_lens(x, lens, mul):
-    if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
-            or lens.numel() != x.size(0) or not lens.is_contiguous() or int(mul) < 1):
-        raise L.EvtError(f"ragged launch: lens must be a contiguous int32 [{x.size(0)}] tensor on {x.device} and mul >= 1")
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise L.EvtError("the ragged (lens) paths of the vocoder are inference only: run them under torch.no_grad()")
 
 
 def _bias(m):
@@ -1085,7 +1077,7 @@ def _res_unit_lens(x, s1, s2, slope, lens, mul):
     """res_unit on a ragged batch, no grad: row s is live on [0, lens[s] * mul) and comes out with a zero tail.  Narrow, wide
     or unfused exactly as ResUnitFn.forward chooses; the unfused path expects x with a zero tail already (the fused kernels
     mask their loads) and masks behind each of its two convolutions, whose biases fill the tail."""
-    _check_lens(x, lens, mul)
+    L.check_lens("res_unit", x, lens, mul)
     m1, m2 = s1.module, s2.module
     lib = L.lib()
     fused = _resunit_params(s1, s2, x, slope)
@@ -1250,7 +1242,7 @@ class ResStageFn(torch.autograd.Function):
                     later.append((s1, s2, xa, mid_a, d[i], dmid))
                 outs.append(dx)
             e0 = _t0()
-            L.check(lib.evt_resunit_bwd_multi(jobs, nb, L.ptr(ws), C.c_int64(ws.numel() if ws is not None else 0),
+            L.check(lib.evt_resunit_bwd_multi(jobs, nb, L.ptr(ws), ws.numel() if ws is not None else 0,
                                               L.stream_ptr()), "evt_resunit_bwd_multi")
             if e0 is not None:
                 _t1_multi(e0, "bwd_unit", pairs, dy, wg)
@@ -1271,7 +1263,7 @@ class ResStageFn(torch.autograd.Function):
 def _res_stage_lens(x, plan, slope, scale, lens, mul):
     """ResStageFn.forward on a ragged batch, no grad: the grouped launches mask their loads of x by the rows' lengths and
     store zero tails, so the stage mean has a zero tail too; nothing is kept for a backward"""
-    _check_lens(x, lens, mul)
+    L.check_lens("res_stage", x, lens, mul)
     lib = L.lib()
     cur = [x] * len(plan[0][0])
     for pairs, ps in plan:

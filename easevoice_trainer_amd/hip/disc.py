@@ -188,7 +188,7 @@ class MPDGenLossFn(torch.autograd.Function):
         L.check(L.lib().evt_l1_multi_fwd(dt, L.ptr(_seg_table(fa, fb, [None] * len(fa), fs, dev)), len(fa),
                                          L.ptr(out[1:]), L.stream_ptr()), "evt_l1_multi_fwd")
         L.check(L.lib().evt_lsgan_multi_fwd(dt, L.ptr(_seg_table(la, [None] * nd, [None] * nd, ls, dev)), nd,
-                                            C.c_float(1.0), L.ptr(out[:1]), L.stream_ptr()), "evt_lsgan_multi_fwd")
+                                            1.0, L.ptr(out[:1]), L.stream_ptr()), "evt_lsgan_multi_fwd")
         ctx.plan, ctx.dt = plan, dt
         ctx.counts = [len(ys) for ys in maps]
         ctx.in_shapes = [(x.size(0) // 2, x.size(1), 1) for x in both]
@@ -224,7 +224,7 @@ class MPDGenLossFn(torch.autograd.Function):
         dl = torch.stack([dgen.reshape(()).float(), dfm.reshape(()).float()]).contiguous()
         L.check(L.lib().evt_l1_multi_bwd(dt, L.ptr(_seg_table(fa, fb, fg, fs, dev)), len(fa), L.ptr(dl[1:]),
                                          L.stream_ptr()), "evt_l1_multi_bwd")
-        L.check(L.lib().evt_lsgan_multi_bwd(dt, L.ptr(_seg_table(la, [None] * nd, lgr, ls, dev)), nd, C.c_float(1.0),
+        L.check(L.lib().evt_lsgan_multi_bwd(dt, L.ptr(_seg_table(la, [None] * nd, lgr, ls, dev)), nd, 1.0,
                                             L.ptr(dl[:1]), L.stream_ptr()), "evt_lsgan_multi_bwd")
         grads, gi = [], 0
         lanes, sides = _branches(dev, nd)
@@ -259,8 +259,8 @@ def _branch_bwd(slots, acts, ys, mg, lg_grad, in_shape, dt):
         a_kind, a_slope, y_arg = act, slope, (y_act if act != L.ACT_NONE else None)
         if act != L.ACT_NONE and L.lib().evt_conv1d_wants_plain_dy(C.byref(s.params(half, lin, 1.0, act, slope))):
             dy_eff = torch.empty_like(dy)
-            L.check(L.lib().evt_dact_mul(dt, L.ptr(dy), L.ptr(y_act), int(act), C.c_float(slope), L.ptr(dy_eff),
-                                         C.c_int64(dy.numel()), L.stream_ptr()), "evt_dact_mul")
+            L.check(L.lib().evt_dact_mul(dt, L.ptr(dy), L.ptr(y_act), int(act), float(slope), L.ptr(dy_eff),
+                                         dy.numel(), L.stream_ptr()), "evt_dact_mul")
             dy, y_arg, a_kind, a_slope = dy_eff, None, L.ACT_NONE, 1.0
         dy = HC._bwd_data(s, dy.contiguous(), y_arg, None, add, half, lin, 1.0, a_kind, a_slope)
     return dy

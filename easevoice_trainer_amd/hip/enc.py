@@ -30,7 +30,7 @@ def seed_rng(device, seed: int):
 def bump_rng(device):
     """advance the dropout stream by one step (call once per training step, inside the captured region)"""
     t = rng_counter(device)
-    L.check(L.lib().evt_counter_inc(L.ptr(t), C.c_uint32(1), L.stream_ptr()), "evt_counter_inc")
+    L.check(L.lib().evt_counter_inc(L.ptr(t), 1, L.stream_ptr()), "evt_counter_inc")
 
 
 def grad_sink(p):
@@ -64,9 +64,8 @@ class ResDropLNFn(torch.autograd.Function):
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         seed = rng_counter(x.device)
         L.check(L.lib().evt_res_dropout_ln_fwd(L.dt_of(x), L.ptr(x), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(lens),
-                                               rps, C.c_float(p), L.ptr(seed), C.c_uint32(site), L.ptr(out), L.ptr(mean),
-                                               L.ptr(rstd), C.c_int64(rows), Cc, C.c_float(eps), L.stream_ptr()),
-                "evt_res_dropout_ln_fwd")
+                                               rps, p, L.ptr(seed), site, L.ptr(out), L.ptr(mean), L.ptr(rstd), rows, Cc,
+                                               eps, L.stream_ptr()), "evt_res_dropout_ln_fwd")
         ctx.save_for_backward(x, y, gamma, mean, rstd, lens)
         ctx.cfg = (p, site, rps, rows, Cc)
         ctx.sinks = (grad_sink(gamma), grad_sink(beta))
@@ -87,9 +86,8 @@ class ResDropLNFn(torch.autograd.Function):
             dgamma, dbeta = dgb[0], dgb[1]
         seed = rng_counter(x.device)
         L.check(L.lib().evt_res_dropout_ln_bwd(L.dt_of(x), L.ptr(x), L.ptr(y), L.ptr(gamma), L.ptr(dout), L.ptr(mean),
-                                               L.ptr(rstd), L.ptr(lens), rps, C.c_float(p), L.ptr(seed),
-                                               C.c_uint32(site), L.ptr(dx), L.ptr(dy), L.ptr(dgamma), L.ptr(dbeta),
-                                               C.c_int64(rows), Cc, L.stream_ptr()), "evt_res_dropout_ln_bwd")
+                                               L.ptr(rstd), L.ptr(lens), rps, p, L.ptr(seed), site, L.ptr(dx), L.ptr(dy),
+                                               L.ptr(dgamma), L.ptr(dbeta), rows, Cc, L.stream_ptr()), "evt_res_dropout_ln_bwd")
         if sunk:
             dgamma = dbeta = None
         return dx, (dy if dy is not None else dx), dgamma, dbeta, None, None, None, None
@@ -332,7 +330,7 @@ class WNResidualFn(torch.autograd.Function):
         acc_out = torch.empty(rs.shape[:-1] + (H,), dtype=rs.dtype, device=rs.device)
         x_out = None if last else torch.empty_like(acc_out)
         L.check(L.lib().evt_wn_residual_fwd(L.dt_of(rs), L.ptr(x), L.ptr(rs), L.ptr(acc), L.ptr(lens), rps, L.ptr(x_out),
-                                            L.ptr(acc_out), C.c_int64(rows), H, int(last), L.stream_ptr()),
+                                            L.ptr(acc_out), rows, H, int(last), L.stream_ptr()),
                 "evt_wn_residual_fwd")
         ctx.save_for_backward(lens)
         ctx.cfg = (H, rows, rps, last, rs.shape, rs.dtype, acc is not None)
@@ -354,7 +352,7 @@ class WNResidualFn(torch.autograd.Function):
         drs = torch.empty(rs_shape, dtype=dtype, device=dev)
         dx = None if last else torch.empty(rs_shape[:-1] + (H,), dtype=dtype, device=dev)
         L.check(L.lib().evt_wn_residual_bwd(L.dt_code(dtype), L.ptr(dx_out), L.ptr(dacc),
-                                            L.ptr(lens), rps, L.ptr(dx), L.ptr(drs), C.c_int64(rows), H, int(last),
+                                            L.ptr(lens), rps, L.ptr(dx), L.ptr(drs), rows, H, int(last),
                                             L.stream_ptr()), "evt_wn_residual_bwd")
         # d(acc): the skip sum passes through unchanged, except for the last layer where the row mask applies to it too
         return dx, drs, ((drs if last else dacc) if has_acc else None), None, None
@@ -377,9 +375,8 @@ class MishDropoutFn(torch.autograd.Function):
     def forward(ctx, x, p, site, out_dtype):
         x = x.contiguous()
         y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-        L.check(L.lib().evt_mish_dropout_fwd(L.dt_of(x), L.dt_of(y), L.ptr(x), C.c_float(p), L.ptr(rng_counter(x.device)),
-                                             C.c_uint32(site), L.ptr(y), C.c_int64(x.numel()), L.stream_ptr()),
-                "evt_mish_dropout_fwd")
+        L.check(L.lib().evt_mish_dropout_fwd(L.dt_of(x), L.dt_of(y), L.ptr(x), p, L.ptr(rng_counter(x.device)),
+                                             site, L.ptr(y), x.numel(), L.stream_ptr()), "evt_mish_dropout_fwd")
         ctx.save_for_backward(x)
         ctx.cfg = (p, site, out_dtype)
         return y
@@ -390,9 +387,8 @@ class MishDropoutFn(torch.autograd.Function):
         p, site, out_dtype = ctx.cfg
         dy = dy.to(out_dtype).contiguous()
         dx = torch.empty_like(x)
-        L.check(L.lib().evt_mish_dropout_bwd(L.dt_of(x), L.dt_of(dy), L.ptr(x), L.ptr(dy), C.c_float(p),
-                                             L.ptr(rng_counter(x.device)), C.c_uint32(site), L.ptr(dx), C.c_int64(x.numel()),
-                                             L.stream_ptr()), "evt_mish_dropout_bwd")
+        L.check(L.lib().evt_mish_dropout_bwd(L.dt_of(x), L.dt_of(dy), L.ptr(x), L.ptr(dy), p, L.ptr(rng_counter(x.device)),
+                                             site, L.ptr(dx), x.numel(), L.stream_ptr()), "evt_mish_dropout_bwd")
         return dx, None, None, None
 
 
@@ -412,10 +408,9 @@ class GluDropoutResFn(torch.autograd.Function):
         res = res.contiguous()
         Cc = h.size(-1) // 2
         y = torch.empty_like(res)
-        L.check(L.lib().evt_glu_dropout_res_fwd(L.dt_of(h), L.dt_of(res), L.ptr(h), L.ptr(res), C.c_float(p),
-                                                L.ptr(rng_counter(h.device)), C.c_uint32(site), L.ptr(y),
-                                                C.c_int64(h.numel() // (2 * Cc)), Cc, L.stream_ptr()),
-                "evt_glu_dropout_res_fwd")
+        L.check(L.lib().evt_glu_dropout_res_fwd(L.dt_of(h), L.dt_of(res), L.ptr(h), L.ptr(res), p,
+                                                L.ptr(rng_counter(h.device)), site, L.ptr(y), h.numel() // (2 * Cc), Cc,
+                                                L.stream_ptr()), "evt_glu_dropout_res_fwd")
         ctx.save_for_backward(h)
         ctx.cfg = (p, site, Cc, res.dtype)
         return y
@@ -426,10 +421,9 @@ class GluDropoutResFn(torch.autograd.Function):
         p, site, Cc, rdt = ctx.cfg
         dy = dy.to(rdt).contiguous()
         dh = torch.empty_like(h)
-        L.check(L.lib().evt_glu_dropout_res_bwd(L.dt_of(h), L.dt_of(dy), L.ptr(h), L.ptr(dy), C.c_float(p),
-                                                L.ptr(rng_counter(h.device)), C.c_uint32(site), L.ptr(dh),
-                                                C.c_int64(h.numel() // (2 * Cc)), Cc, L.stream_ptr()),
-                "evt_glu_dropout_res_bwd")
+        L.check(L.lib().evt_glu_dropout_res_bwd(L.dt_of(h), L.dt_of(dy), L.ptr(h), L.ptr(dy), p,
+                                                L.ptr(rng_counter(h.device)), site, L.ptr(dh), h.numel() // (2 * Cc), Cc,
+                                                L.stream_ptr()), "evt_glu_dropout_res_bwd")
         return dh, dy, None, None
 
 
@@ -437,20 +431,17 @@ def glu_dropout_res(h, res, p, site):
     return GluDropoutResFn.apply(h, res, float(p), int(site))
 
 
-def _rows_lens(x, lens):
-    if (x.dim() != 3 or not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
-            or lens.numel() != x.size(0) or not lens.is_contiguous()):
-        raise L.EvtError(f"ragged style encoder: rows [B, T, C] and a contiguous int32 [B] lens on {x.device} expected, got "
-                         f"{tuple(x.shape)} and {lens.dtype if torch.is_tensor(lens) else type(lens)}")
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise L.EvtError("the ragged (lens) forms of the style encoder are inference only: run them under torch.no_grad()")
+def _check_rows3(what, x, lens):
+    if x.dim() != 3:
+        raise L.EvtError(f"{what}: rows [B, T, C] expected, got {tuple(x.shape)}")
+    L.check_lens(what, x, lens)
 
 
 def mish_rows(x, lens, out_dtype=None):
     """mish_dropout at p = 0 on a ragged batch x [B, T, C]: frames t >= lens[b] come out as exact zeros (one launch,
     evt_mish_rows_fwd); no grad"""
     x = x.contiguous()
-    _rows_lens(x, lens)
+    _check_rows3("mish_rows", x, lens)
     y = torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
     L.check(L.lib().evt_mish_rows_fwd(L.dt_of(x), L.dt_of(y), L.ptr(x), L.ptr(lens), x.size(0), x.size(1), x.size(2),
                                       L.ptr(y), L.stream_ptr()), "evt_mish_rows_fwd")
@@ -464,7 +455,7 @@ def glu_res_rows(h, res, lens):
     if res.dtype not in (h.dtype, torch.float32):
         res = res.to(h.dtype)
     res = res.contiguous()
-    _rows_lens(h, lens)
+    _check_rows3("glu_res_rows", h, lens)
     Cc = h.size(-1) // 2
     if tuple(res.shape) != (h.size(0), h.size(1), Cc):
         raise L.EvtError(f"glu_res_rows: res {tuple(res.shape)} does not go with h {tuple(h.shape)}")
@@ -478,7 +469,7 @@ def mean_rows(x, lens):
     """x [B, T, C] (fp32 or the library's 16-bit type), lens int32 [B] -> fp32 [B, C]: the mean over every row's live frames
     in fp32, in an order that depends on the row's length alone (evt_mean_rows); a row of length 0 gives zeros"""
     x = x.contiguous()
-    _rows_lens(x, lens)
+    _check_rows3("mean_rows", x, lens)
     out = torch.empty((x.size(0), x.size(2)), dtype=torch.float32, device=x.device)
     L.check(L.lib().evt_mean_rows(L.dt_of(x), L.ptr(x), L.ptr(lens), x.size(0), x.size(1), x.size(2), L.ptr(out),
                                   L.stream_ptr()), "evt_mean_rows")
@@ -497,7 +488,7 @@ class ReparamFn(torch.autograd.Function):
         Cc = C2 // 2
         z = torch.empty((B, T, Cc), dtype=torch.float32, device=stats.device)
         m, logs = torch.empty_like(z), torch.empty_like(z)
-        L.check(L.lib().evt_reparam_fwd(L.dt_of(stats), L.ptr(stats), L.ptr(eps), L.ptr(lens), T, C.c_int64(B * T), Cc,
+        L.check(L.lib().evt_reparam_fwd(L.dt_of(stats), L.ptr(stats), L.ptr(eps), L.ptr(lens), T, B * T, Cc,
                                         L.ptr(z), L.ptr(m), L.ptr(logs), L.stream_ptr()), "evt_reparam_fwd")
         ctx.save_for_backward(eps, logs, lens)
         ctx.sdt, ctx.dims = stats.dtype, (B, T, Cc)
@@ -511,7 +502,7 @@ class ReparamFn(torch.autograd.Function):
         dstats = torch.empty((B, T, 2 * Cc), dtype=ctx.sdt, device=eps.device)
         dt = L.dt_code(ctx.sdt)
         L.check(L.lib().evt_reparam_bwd(dt, L.ptr(gs[0]), L.ptr(gs[1]), L.ptr(gs[2]), L.ptr(eps), L.ptr(logs), L.ptr(lens), T,
-                                        C.c_int64(B * T), Cc, L.ptr(dstats), L.stream_ptr()), "evt_reparam_bwd")
+                                        B * T, Cc, L.ptr(dstats), L.stream_ptr()), "evt_reparam_bwd")
         return dstats, None, None
 
 
@@ -533,7 +524,7 @@ class CouplingFlipFn(torch.autograd.Function):
         stats = stats.contiguous()
         y = torch.empty_like(x)
         x0n = torch.empty((B, T, h), dtype=stats.dtype, device=x.device) if want_x0n else None
-        L.check(L.lib().evt_coupling_flip_fwd(L.dt_of(stats), L.ptr(x), L.ptr(stats), L.ptr(lens), T, C.c_int64(B * T), h,
+        L.check(L.lib().evt_coupling_flip_fwd(L.dt_of(stats), L.ptr(x), L.ptr(stats), L.ptr(lens), T, B * T, h,
                                               L.ptr(y), L.ptr(x0n), L.stream_ptr()), "evt_coupling_flip_fwd")
         ctx.save_for_backward(lens)
         ctx.dims, ctx.sdt = (B, T, h), stats.dtype
@@ -553,7 +544,7 @@ class CouplingFlipFn(torch.autograd.Function):
         dx = torch.empty_like(dy)
         dstats = torch.empty((B, T, h), dtype=ctx.sdt, device=dy.device)
         dt = L.dt_code(ctx.sdt)
-        L.check(L.lib().evt_coupling_flip_bwd(dt, L.ptr(dy), L.ptr(dx0n), L.ptr(lens), T, C.c_int64(B * T), h, L.ptr(dx),
+        L.check(L.lib().evt_coupling_flip_bwd(dt, L.ptr(dy), L.ptr(dx0n), L.ptr(lens), T, B * T, h, L.ptr(dx),
                                               L.ptr(dstats), L.stream_ptr()), "evt_coupling_flip_bwd")
         return dx, dstats, None, None
 
@@ -589,8 +580,8 @@ class ReluDropoutFn(torch.autograd.Function):
         x = x.contiguous()
         y = torch.empty_like(x)
         rps, Cc = (x.size(-2), x.size(-1)) if lens is not None else (0, 0)
-        L.check(L.lib().evt_relu_dropout_fwd(L.dt_of(x), L.ptr(x), C.c_float(p), L.ptr(rng_counter(x.device)),
-                                             C.c_uint32(site), L.ptr(lens), rps, Cc, L.ptr(y), C.c_int64(x.numel()),
+        L.check(L.lib().evt_relu_dropout_fwd(L.dt_of(x), L.ptr(x), p, L.ptr(rng_counter(x.device)),
+                                             site, L.ptr(lens), rps, Cc, L.ptr(y), x.numel(),
                                              L.stream_ptr()), "evt_relu_dropout_fwd")
         ctx.save_for_backward(x, lens)
         ctx.cfg = (p, site, rps, Cc)
@@ -602,8 +593,8 @@ class ReluDropoutFn(torch.autograd.Function):
         p, site, rps, Cc = ctx.cfg
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        L.check(L.lib().evt_relu_dropout_bwd(L.dt_of(x), L.ptr(x), L.ptr(dy), C.c_float(p), L.ptr(rng_counter(x.device)),
-                                             C.c_uint32(site), L.ptr(lens), rps, Cc, L.ptr(dx), C.c_int64(x.numel()),
+        L.check(L.lib().evt_relu_dropout_bwd(L.dt_of(x), L.ptr(x), L.ptr(dy), p, L.ptr(rng_counter(x.device)),
+                                             site, L.ptr(lens), rps, Cc, L.ptr(dx), x.numel(),
                                              L.stream_ptr()), "evt_relu_dropout_bwd")
         return dx, None, None, None
 

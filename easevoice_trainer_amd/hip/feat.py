@@ -1,7 +1,5 @@
 """Bindings of the feature extractors' own launches (csrc/feat_ops.hip) and the LayerNorm entry point they share with the s1
 blocks.  Inference only: nothing here records an autograd graph."""
-import ctypes as C
-
 import torch
 
 from . import lib as L
@@ -14,7 +12,7 @@ def gelu_rows(x, bias=None, t_out=None):
     B, T, Cc = x.shape
     t_out = T if t_out is None else int(t_out)
     out = torch.empty((B, t_out, Cc), dtype=x.dtype, device=x.device)
-    L.check(L.lib().evt_gelu_rows_fwd(L.dt_of(x), L.ptr(x), L.ptr(bias), L.ptr(out), C.c_int64(B), T, t_out, Cc,
+    L.check(L.lib().evt_gelu_rows_fwd(L.dt_of(x), L.ptr(x), L.ptr(bias), L.ptr(out), B, T, t_out, Cc,
                                       L.stream_ptr()), "evt_gelu_rows_fwd")
     return out
 
@@ -25,34 +23,19 @@ def channel_norm_gelu(x, gamma, beta, eps, gelu=True):
         raise L.EvtError(f"channel_norm_gelu: contiguous [B, T, C] expected, got {tuple(x.shape)}")
     B, T, Cc = x.shape
     out = torch.empty_like(x)
-    L.check(L.lib().evt_channel_norm_gelu_fwd(L.dt_of(x), L.ptr(x), L.ptr(gamma), L.ptr(beta), C.c_float(eps), L.ptr(out), B,
+    L.check(L.lib().evt_channel_norm_gelu_fwd(L.dt_of(x), L.ptr(x), L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(out), B,
                                               T, Cc, 1 if gelu else 0, L.stream_ptr()), "evt_channel_norm_gelu_fwd")
     return out
 
 
 FRONT_CHANNELS, FRONT_K, FRONT_STRIDE = 512, 10, 5     # HuBERT's first convolution
-# the argument lists of include/evt.h, given to ctypes so that a call with another count or kind of argument is refused
-FRONT_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-RESCALE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
-def _rows_entry(name, argtypes):
-    fn = getattr(L.lib(), name)          # AttributeError for a library without the entry: there is no fallback
-    if fn.argtypes is None:
-        fn.argtypes, fn.restype = argtypes, C.c_int
-    return fn
-
-
-def _check_rows(what, x, lens):
-    """the lens checks of hip/conv.py::_check_lens for the clip front end: fp32 rows [nseq, N] and int32 lengths on one GPU"""
+def _check_clips(what, x, lens):
+    """the clip front end takes fp32 rows [nseq, N] with their lengths"""
     if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.size(0) < 1:
         raise L.EvtError(f"{what}: contiguous float32 rows [nseq, N] expected")
-    if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
-            or lens.numel() != x.size(0) or not lens.is_contiguous()):
-        raise L.EvtError(f"{what}: lens must be a contiguous int32 [{x.size(0)}] tensor on {x.device}")
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise L.EvtError(f"{what} is inference only: run it under torch.no_grad()")
+    L.check_lens(what, x, lens)
 
 
 def front_frames(n):
@@ -65,7 +48,7 @@ def hubert_front_rows(wav, lens, weight, gamma, beta, eps, dtype):
     gamma / beta fp32 [512] -> [nseq, (N - 10) // 5 + 1, 512] of dtype: conv + GroupNorm(512, 512) + GELU per row over the
     row's own frames, zeros behind them (evt_hubert_front_rows; include/evt.h has the definition).  wav is not read at or
     behind a row's length, a row comes out bit for bit as it does alone."""
-    _check_rows("hubert_front_rows", wav, lens)
+    _check_clips("hubert_front_rows", wav, lens)
     nseq, n = wav.shape
     if n < FRONT_K:
         raise L.EvtError(f"hubert_front_rows: rows of at least {FRONT_K} samples expected, got {n}")
@@ -78,7 +61,7 @@ def hubert_front_rows(wav, lens, weight, gamma, beta, eps, dtype):
     ws_floats = L.lib().evt_hubert_front_ws_floats(nseq, n)
     ws = torch.empty(ws_floats, dtype=torch.float32, device=wav.device)
     out = torch.empty(nseq, front_frames(n), FRONT_CHANNELS, dtype=dtype, device=wav.device)
-    L.check(_rows_entry("evt_hubert_front_rows", FRONT_ARGTYPES)(
+    L.check(L.lib().evt_hubert_front_rows(
         code, wav.data_ptr(), lens.data_ptr(), nseq, n, weight.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps),
         out.data_ptr(), ws.data_ptr(), ws_floats, L.stream_ptr()), "evt_hubert_front_rows")
     return out
@@ -89,23 +72,17 @@ def clip_rescale_rows(x, lens):
     normalize.py:148-153 per row -- rescale_clip's float clip for HuBERT, its int16 clip for 5-wav32k and the row's peak --
     bit for bit numpy's float32 arithmetic, zeros behind a row's length (evt_clip_rescale_rows).  The caller reads `peak`
     to drop rows above 2.2; q saturates where numpy's cast is undefined."""
-    _check_rows("clip_rescale_rows", x, lens)
+    _check_clips("clip_rescale_rows", x, lens)
     nseq, n = x.shape
     if n < 1:
         raise L.EvtError("clip_rescale_rows: empty rows")
     f = torch.empty_like(x)
     q = torch.empty(nseq, n, dtype=torch.int16, device=x.device)
     peak = torch.empty(nseq, dtype=torch.float32, device=x.device)
-    L.check(_rows_entry("evt_clip_rescale_rows", RESCALE_ARGTYPES)(
+    L.check(L.lib().evt_clip_rescale_rows(
         x.data_ptr(), lens.data_ptr(), nseq, n, f.data_ptr(), q.data_ptr(), peak.data_ptr(), L.stream_ptr()),
         "evt_clip_rescale_rows")
     return f, q, peak
-
-
-EXPAND_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                   C.c_int32, C.c_void_p, C.c_void_p]
-EMBED_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                  C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]
 
 
 def _check_i32(what, name, t, numel, device):
@@ -131,7 +108,7 @@ def phone_expand_rows(h, src, item_off, n_items, total, out_dtype=torch.float32)
     if torch.is_grad_enabled() and h.requires_grad:
         raise L.EvtError("phone_expand_rows is inference only: run it under torch.no_grad()")
     out = torch.empty(Cc * total, dtype=out_dtype, device=h.device)
-    L.check(_rows_entry("evt_phone_expand_rows", EXPAND_ARGTYPES)(
+    L.check(L.lib().evt_phone_expand_rows(
         L.dt_of(h), h.data_ptr(), B, T, Cc, src.data_ptr(), item_off.data_ptr(), n_items, total, L.dt_code(out_dtype),
         out.data_ptr(), L.stream_ptr()), "evt_phone_expand_rows")
     return out
@@ -146,7 +123,7 @@ def bert_embed_ln_rows(ids, lens, word, pos, type_emb, gamma, beta, eps, dtype, 
         raise L.EvtError("bert_embed_ln_rows: ids [B, T] on the GPU expected")
     B, T = ids.shape
     _check_i32("bert_embed_ln_rows", "ids", ids, B * T, ids.device)
-    _check_i32("bert_embed_ln_rows", "lens", lens, B, ids.device)
+    L.check_lens("bert_embed_ln_rows", ids, lens)
     if token_type_ids is not None:
         _check_i32("bert_embed_ln_rows", "token_type_ids", token_type_ids, B * T, ids.device)
     Cc = word.size(-1)
@@ -158,15 +135,13 @@ def bert_embed_ln_rows(ids, lens, word, pos, type_emb, gamma, beta, eps, dtype, 
     if B < 1 or T < 1 or T > pos.size(0) or Cc % 4 or not 4 <= Cc <= 8192:
         raise L.EvtError(f"bert_embed_ln_rows: ids {tuple(ids.shape)} with tables of {pos.size(0)} positions x {Cc} are not served")
     out = torch.empty(B, T, Cc, dtype=dtype, device=ids.device)
-    L.check(_rows_entry("evt_bert_embed_ln_rows", EMBED_ARGTYPES)(
+    L.check(L.lib().evt_bert_embed_ln_rows(
         L.dt_code(dtype), ids.data_ptr(), None if token_type_ids is None else token_type_ids.data_ptr(), lens.data_ptr(), B, T,
         word.data_ptr(), word.size(0), pos.data_ptr(), pos.size(0), type_emb.data_ptr(), type_emb.size(0), gamma.data_ptr(),
         beta.data_ptr(), float(eps), Cc, out.data_ptr(), L.stream_ptr()), "evt_bert_embed_ln_rows")
     return out
 
 
-SEMANTIC_ARGTYPES = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 SEMANTIC_MAX_D = 1152     # EVT_SEMANTIC_MAX_D
 
 
@@ -227,7 +202,7 @@ def semantic_codes_rows(hs, frames, proj_image, bias, embed, ee=None):
     dev = host.to(hs.device)
     frames_dev, offsets = dev[2 * (B + 1):], dev[: 2 * (B + 1)].view(torch.int64)
     codes = torch.empty(total, dtype=torch.int64, device=hs.device)
-    L.check(_rows_entry("evt_semantic_codes_rows", SEMANTIC_ARGTYPES)(
+    L.check(L.lib().evt_semantic_codes_rows(
         L.dt_of(hs), hs.data_ptr(), frames_dev.data_ptr(), frames_host.data_ptr(), offsets.data_ptr(), B, Tmax, D, K,
         proj_image.data_ptr(), bias.data_ptr(), embed.data_ptr(), ee.data_ptr(), codes.data_ptr() if total else None, total,
         L.stream_ptr()), "evt_semantic_codes_rows")
@@ -243,6 +218,6 @@ def add_layernorm(x, r, gamma, beta, eps):
     y = torch.empty_like(x)
     stats = torch.empty(2, rows, dtype=torch.float32, device=x.device)
     L.check(L.lib().evt_add_layernorm_fwd(L.dt_of(x), L.ptr(x), L.ptr(r), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(stats[0]),
-                                          L.ptr(stats[1]), C.c_int64(rows), Cc, C.c_float(eps), L.stream_ptr()),
+                                          L.ptr(stats[1]), rows, Cc, float(eps), L.stream_ptr()),
             "evt_add_layernorm_fwd")
     return y

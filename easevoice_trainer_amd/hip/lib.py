@@ -6,8 +6,11 @@ this boundary is a raw `data_ptr()`.
 """
 import ctypes as C
 import os
+import re
 
 import torch
+
+from ..build import HEADER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libevt_hip.so")           # bfloat16 build
@@ -201,8 +204,56 @@ def _check_fresh(handle, LIB_PATH=LIB_PATH):
                        "rebuild with `python -m easevoice_trainer_amd.build` (EVT_ALLOW_STALE_LIB=1 overrides)")
 
 
+_PARAM_TYPES = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "float": C.c_float}
+_RETURN_TYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p, "void": None}
+
+
+def prototypes(header_text):
+    """{name: (restype, [argtypes])} of every function a C header declares, in ctypes terms.  The kinds of include/evt.h and
+    no others: a parameter with a `*` is c_void_p, int32_t / uint32_t / int64_t / float by value are themselves; anything
+    else (double, size_t, a struct by value) is an EvtError naming the function and the parameter, so that a new kind in
+    the header is added here knowingly."""
+    text = re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    out = {}
+    for stmt in re.split(r"[;{}]", text):        # struct bodies fall apart into fields, which have no parentheses
+        m = re.fullmatch(r"\s*(.*?)\b(\w+)\s*\(([^()]*)\)\s*", stmt, flags=re.S)
+        if m is None:
+            continue
+        ret, name, params = " ".join(m.group(1).replace("*", "* ").split()).replace(" *", "*"), m.group(2), m.group(3)
+        if ret not in _RETURN_TYPES:
+            raise EvtError(f"{name}: return type {ret!r} is not one of {sorted(_RETURN_TYPES)}")
+        argtypes = []
+        for param in ([] if params.split() in ([], ["void"]) else params.split(",")):
+            words = [w for w in param.split() if w != "const"]
+            kind = " ".join(words[:-1] if len(words) > 1 else words)
+            if "*" in param:
+                argtypes.append(C.c_void_p)
+            elif kind in _PARAM_TYPES:
+                argtypes.append(_PARAM_TYPES[kind])
+            else:
+                raise EvtError(f"{name}: parameter {' '.join(param.split())!r} is not a pointer or one of {sorted(_PARAM_TYPES)}")
+        out[name] = (_RETURN_TYPES[ret], argtypes)
+    return out
+
+
+_protos = None     # prototypes() of include/evt.h, parsed once for both builds
+
+
+def _declare(handle, name, path):
+    """restype and argtypes of one entry point, from the header: a call with another count or kind of argument is refused
+    by ctypes (TypeError / ctypes.ArgumentError) instead of reaching the kernel"""
+    fn = getattr(handle, name, None)
+    if fn is None:
+        raise EvtError(f"{path} does not export {name}, which include/evt.h declares: rebuild it")
+    fn.restype, fn.argtypes = _protos[name]
+
+
 def lib():
-    """The selected build (set_half), loaded once; raise loudly if it is missing (no CPU / eager fallback)."""
+    """The selected build (set_half), loaded once, with every prototype of include/evt.h declared to ctypes; raise loudly if
+    it is missing (no CPU / eager fallback)."""
+    global _protos
     _lib = _libs.get(_half)
     if _lib is None:
         path = LIB_PATH if _half == torch.bfloat16 else LIB_PATH_F16
@@ -210,29 +261,31 @@ def lib():
             raise EvtError(
                 f"{path} not found: build it with `python -m easevoice_trainer_amd.build` "
                 "(or __graft_entry__.build()). There is no fallback path.")
+        if _protos is None:
+            if not os.path.exists(HEADER):
+                raise EvtError(f"{HEADER} not found: the library is used from its source tree, whose header declares "
+                               "every call to ctypes. There is no fallback path.")
+            with open(HEADER) as f:
+                _protos = prototypes(f.read())
         _lib = C.CDLL(path)
-        _lib.evt_version.restype = C.c_char_p
+        _declare(_lib, "evt_version", path)       # what _check_fresh reads, before anything a stale library may lack
         _check_fresh(_lib, path)
-        _lib.evt_half_dtype.restype = C.c_int32
+        for name in _protos:
+            _declare(_lib, name, path)
         if _lib.evt_half_dtype() != (DT_BF16 if _half == torch.bfloat16 else DT_F16):
             raise EvtError(f"{path} serves half code {_lib.evt_half_dtype()}: not the {_half} build")
         _libs[_half] = _lib
-        _lib.evt_conv1d_lout.restype = C.c_int32
-        _lib.evt_mel_workspace_floats.restype = C.c_int64
-        _lib.evt_workspace_bytes.restype = C.c_int64
-        _lib.evt_last_kernel_tag.restype = C.c_char_p
-        _lib.evt_resunit_bwd_ws_floats.restype = C.c_int64
-        _lib.evt_debug_kernel_tags.restype = None
-        # the ragged (inference) entry points of the vocoder, of the clip front end and of the two ends of BERT: both builds
-        # export them, a library without them fails here
-        for name in ("evt_resunit_fwd_multi_lens", "evt_resunit_wide_fwd_lens", "evt_mask_tail", "evt_resample_rows",
-                     "evt_resample_pack_rows", "evt_hubert_front_rows", "evt_clip_rescale_rows", "evt_phone_expand_rows",
-                     "evt_bert_embed_ln_rows", "evt_ref_spec_rows", "evt_mish_rows_fwd", "evt_glu_res_rows_fwd",
-                     "evt_mean_rows", "evt_rms_frames_rows", "evt_span_peak_rows", "evt_slice_pack_rows",
-                     "evt_semantic_codes_rows"):
-            getattr(_lib, name).restype = C.c_int
-        _lib.evt_hubert_front_ws_floats.restype = C.c_int64
     return _lib
+
+
+def check_lens(what, x, lens, mul=1):
+    """the conditions of every ragged launch on its lengths: lens a contiguous int32 [x.size(0)] tensor on x's device, in
+    units of mul >= 1 positions, and no autograd graph to record (the ragged paths are inference only)"""
+    if (not torch.is_tensor(lens) or lens.dtype != torch.int32 or lens.device != x.device or lens.dim() != 1
+            or lens.numel() != x.size(0) or not lens.is_contiguous() or int(mul) < 1):
+        raise EvtError(f"{what}: lens must be a contiguous int32 [{x.size(0)}] tensor on {x.device} and mul >= 1")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise EvtError(f"{what} is inference only: run it under torch.no_grad()")
 
 
 def check(rc: int, what: str) -> None:

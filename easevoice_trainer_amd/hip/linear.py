@@ -212,8 +212,8 @@ def gemm_fwd(slot, x, relu=False, drop=None, add=None):
             raise L.EvtError("dropout epilogue without relu is not used by the s1 blocks")
         z = y
         y = torch.empty_like(z)
-        L.check(lib.evt_relu_dropout_fwd(L.dt_of(z), L.ptr(z), C.c_float(p_drop), L.ptr(_rng(x.device)), C.c_uint32(site),
-                                         None, 0, 0, L.ptr(y), C.c_int64(z.numel()), L.stream_ptr()),
+        L.check(lib.evt_relu_dropout_fwd(L.dt_of(z), L.ptr(z), float(p_drop), L.ptr(_rng(x.device)), int(site),
+                                         None, 0, 0, L.ptr(y), z.numel(), L.stream_ptr()),
                 "evt_relu_dropout_fwd")
     if add is not None:
         y.add_(add)
@@ -239,8 +239,8 @@ def gemm_bwd_data(slot, dy, gate=None, gate_pos=1.0, add=None):
                                        L.stream_ptr()), "evt_gemm_bf16_bwd_data")
     if gate is not None:     # the same derivative as its own launch (odd shapes, the fp32 parity path)
         g = torch.empty_like(dx)
-        L.check(lib.evt_dact_mul(L.dt_of(dx), L.ptr(dx), L.ptr(gate), L.ACT_LRELU, C.c_float(0.0), L.ptr(g),
-                                 C.c_int64(dx.numel()), L.stream_ptr()), "evt_dact_mul")
+        L.check(lib.evt_dact_mul(L.dt_of(dx), L.ptr(dx), L.ptr(gate), L.ACT_LRELU, 0.0, L.ptr(g), dx.numel(),
+                                 L.stream_ptr()), "evt_dact_mul")
         dx = g if gate_pos == 1.0 else g.mul_(gate_pos)
     if add is not None:
         dx.add_(add)
@@ -299,8 +299,8 @@ class LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         if ctx.relu:
             dy_eff = torch.empty_like(dy)
-            L.check(L.lib().evt_dact_mul(L.dt_of(dy), L.ptr(dy), L.ptr(y), L.ACT_LRELU, C.c_float(0.0), L.ptr(dy_eff),
-                                         C.c_int64(dy.numel()), L.stream_ptr()), "evt_dact_mul")
+            L.check(L.lib().evt_dact_mul(L.dt_of(dy), L.ptr(dy), L.ptr(y), L.ACT_LRELU, 0.0, L.ptr(dy_eff), dy.numel(),
+                                         L.stream_ptr()), "evt_dact_mul")
             dy = dy_eff
         dw = db = None
         if ctx.needs_input_grad[1]:

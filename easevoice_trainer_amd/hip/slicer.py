@@ -2,26 +2,12 @@
 peaks and the rescale-and-pack to int16 for recordings that lie in one packed fp32 device buffer.  The offsets and lengths
 come from the host, which packed the buffer: they are checked against it here, before a pointer reaches a kernel, and
 uploaded as one int64 table.  Inference only."""
-import ctypes as C
-
 import torch
 
 from . import lib as L
 
-RMS_ARGTYPES = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                C.c_int64, C.c_void_p]
-PEAK_ARGTYPES = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
-PACK_ARGTYPES = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
-                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
 MAX_WIN = 8192          # kRmsMaxWin of csrc/slicer.hip
 MAX_SPANS = 65535       # spans of one launch (a grid's second dimension); longer tables go out in pieces
-
-
-def _entry(name, argtypes):
-    fn = getattr(L.lib(), name)          # AttributeError for a library without the entry: there is no fallback
-    if fn.argtypes is None:
-        fn.argtypes, fn.restype = argtypes, C.c_int
-    return fn
 
 
 def _check_buffer(what, x):
@@ -66,7 +52,7 @@ def rms_frames_rows(x, offs, lens, win, hop):
     nrec, total = len(offs), frame_off[-1]
     table = torch.tensor(offs + lens + frame_off, dtype=torch.int64).to(x.device)
     rms = torch.empty(total, dtype=torch.float32, device=x.device)
-    L.check(_entry("evt_rms_frames_rows", RMS_ARGTYPES)(
+    L.check(L.lib().evt_rms_frames_rows(
         x.data_ptr(), x.numel(), table.data_ptr(), table[nrec:].data_ptr(), nrec, win, hop, rms.data_ptr(),
         table[2 * nrec:].data_ptr(), total, L.stream_ptr()), "evt_rms_frames_rows")
     return rms, frame_off
@@ -112,7 +98,7 @@ def span_peaks(x, spans):
     empty span (evt_span_peak_rows).  One launch for up to 65535 spans."""
     _check_spans("span_peaks", x, spans)
     peak = torch.empty(len(spans), dtype=torch.float32, device=x.device)
-    fn = _entry("evt_span_peak_rows", PEAK_ARGTYPES)
+    fn = L.lib().evt_span_peak_rows
     for s0 in range(0, len(spans), MAX_SPANS):
         ns = min(MAX_SPANS, len(spans) - s0)
         L.check(fn(x.data_ptr(), x.numel(), spans.table[0, s0:].data_ptr(), spans.table[1, s0:].data_ptr(), ns, spans.max_n,
@@ -134,7 +120,7 @@ def slice_pack(x, spans, peak, c1, c2):
     out = (torch.empty if dense else torch.zeros)(spans.out_len, dtype=torch.int16, device=x.device)
     if spans.out_len == 0:
         return out
-    fn = _entry("evt_slice_pack_rows", PACK_ARGTYPES)
+    fn = L.lib().evt_slice_pack_rows
     for s0 in range(0, len(spans), MAX_SPANS):
         ns = min(MAX_SPANS, len(spans) - s0)
         L.check(fn(x.data_ptr(), x.numel(), spans.table[0, s0:].data_ptr(), spans.table[1, s0:].data_ptr(),

@@ -11,8 +11,6 @@ single node removes is everything between them that torch issued: the element-wi
 every layer input (now the add-epilogue of the in_layer backward-data launch), a zero fill and a cast per layer for the
 conditioning gradient (one fp32 buffer and one cast per stack), the unbind / stack bookkeeping, and ~80 autograd nodes.
 """
-import ctypes as C
-
 import torch
 
 from . import conv as HC
@@ -61,7 +59,7 @@ class WNStackFn(torch.autograd.Function):
             acc_out = torch.empty((B, T, H), dtype=x.dtype, device=x.device)
             x_out = None if last else torch.empty_like(acc_out)
             L.check(L.lib().evt_wn_residual_fwd(dt, L.ptr(None if last else x), L.ptr(rs), L.ptr(out), L.ptr(lens), T,
-                                                L.ptr(x_out), L.ptr(acc_out), C.c_int64(rows), H, int(last),
+                                                L.ptr(x_out), L.ptr(acc_out), rows, H, int(last),
                                                 L.stream_ptr()), "evt_wn_residual_fwd")
             saved += [x, x_in, acts]
             x, out = x_out, acc_out
@@ -126,7 +124,7 @@ class WNStackFn(torch.autograd.Function):
             drs = torch.empty((B, T, rs_w), dtype=dtype, device=dev)
             dx_res = None if last else torch.empty((B, T, H), dtype=dtype, device=dev)
             L.check(L.lib().evt_wn_residual_bwd(dt, L.ptr(dx_next), L.ptr(dacc), L.ptr(lens), T, L.ptr(dx_res), L.ptr(drs),
-                                                C.c_int64(rows), H, int(last), L.stream_ptr()), "evt_wn_residual_bwd")
+                                                rows, H, int(last), L.stream_ptr()), "evt_wn_residual_bwd")
             if last:
                 dacc = drs          # out = (acc + rs) * mask: the skip sum's gradient is masked too
             s = rs_slots[i]

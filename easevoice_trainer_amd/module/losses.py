@@ -29,11 +29,11 @@ class _SegLossFn(torch.autograd.Function):
         dt = L.dt_of(a_list[0])
         out = torch.zeros(1, dtype=torch.float32, device=dev)
         tab = _table(list(zip(a_list, b_list)), scales, [None] * n_a, dev)
-        fn = L.lib().evt_l1_multi_fwd if mode == 0 else L.lib().evt_lsgan_multi_fwd
         if mode == 0:
-            L.check(fn(dt, L.ptr(tab), n_a, L.ptr(out), L.stream_ptr()), "evt_l1_multi_fwd")
+            L.check(L.lib().evt_l1_multi_fwd(dt, L.ptr(tab), n_a, L.ptr(out), L.stream_ptr()), "evt_l1_multi_fwd")
         else:
-            L.check(fn(dt, L.ptr(tab), n_a, C.c_float(target), L.ptr(out), L.stream_ptr()), "evt_lsgan_multi_fwd")
+            L.check(L.lib().evt_lsgan_multi_fwd(dt, L.ptr(tab), n_a, target, L.ptr(out), L.stream_ptr()),
+                    "evt_lsgan_multi_fwd")
         ctx.mode, ctx.target, ctx.scales, ctx.n_a, ctx.dt = mode, target, scales, n_a, dt
         ctx.save_for_backward(*a_list, *[b for b in b_list if b is not None])
         return out[0]
@@ -51,7 +51,7 @@ class _SegLossFn(torch.autograd.Function):
         if ctx.mode == 0:
             L.check(L.lib().evt_l1_multi_bwd(ctx.dt, L.ptr(tab), n_a, L.ptr(dl), L.stream_ptr()), "evt_l1_multi_bwd")
         else:
-            L.check(L.lib().evt_lsgan_multi_bwd(ctx.dt, L.ptr(tab), n_a, C.c_float(ctx.target), L.ptr(dl),
+            L.check(L.lib().evt_lsgan_multi_bwd(ctx.dt, L.ptr(tab), n_a, ctx.target, L.ptr(dl),
                                                 L.stream_ptr()), "evt_lsgan_multi_bwd")
         return (None, None, None, None, *grads, *([None] * (len(saved) - n_a)))
 
@@ -97,7 +97,7 @@ class _DLossBatchedFn(torch.autograd.Function):
         for k, target in ((0, 1.0), (1, 0.0)):
             segs = [h[k] for h in halves]
             tab = _table([(t, None) for t in segs], [1.0 / t.numel() for t in segs], [None] * len(segs), dev)
-            L.check(L.lib().evt_lsgan_multi_fwd(dt, L.ptr(tab), len(segs), C.c_float(target), L.ptr(out), L.stream_ptr()),
+            L.check(L.lib().evt_lsgan_multi_fwd(dt, L.ptr(tab), len(segs), target, L.ptr(out), L.stream_ptr()),
                     "evt_lsgan_multi_fwd")
         ctx.dt = dt
         ctx.save_for_backward(*outs)
@@ -113,7 +113,7 @@ class _DLossBatchedFn(torch.autograd.Function):
             segs = [(o[: o.size(0) // 2], g[: o.size(0) // 2]) if k == 0 else (o[o.size(0) // 2:], g[o.size(0) // 2:])
                     for o, g in zip(outs, grads)]
             tab = _table([(a, None) for a, _ in segs], [1.0 / a.numel() for a, _ in segs], [g for _, g in segs], dev)
-            L.check(L.lib().evt_lsgan_multi_bwd(ctx.dt, L.ptr(tab), len(segs), C.c_float(target), L.ptr(dl),
+            L.check(L.lib().evt_lsgan_multi_bwd(ctx.dt, L.ptr(tab), len(segs), target, L.ptr(dl),
                                                 L.stream_ptr()), "evt_lsgan_multi_bwd")
         return tuple(grads)
 

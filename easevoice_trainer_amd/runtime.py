@@ -154,15 +154,15 @@ class FlatAdamW:
         if skip is not None:
             self._guarded = True
             L.check(L.lib().evt_adamw_flat_dev_guarded(L.ptr(a.param), L.ptr(a.grad), L.ptr(self.exp_avg),
-                                                       L.ptr(self.exp_avg_sq), C.c_int64(a.numel), L.ptr(tab), nseg,
-                                                       C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                                                       L.ptr(self._step_dev), C.c_float(grad_scale), L.ptr(skip),
+                                                       L.ptr(self.exp_avg_sq), a.numel, L.ptr(tab), nseg,
+                                                       float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                                                       L.ptr(self._step_dev), float(grad_scale), L.ptr(skip),
                                                        L.stream_ptr()), "evt_adamw_flat_dev_guarded")
             return
         L.check(L.lib().evt_adamw_flat_dev(L.ptr(a.param), L.ptr(a.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                           C.c_int64(a.numel), L.ptr(tab), nseg, C.c_float(self.betas[0]),
-                                           C.c_float(self.betas[1]), C.c_float(self.eps), L.ptr(self._step_dev),
-                                           C.c_float(grad_scale), L.stream_ptr()), "evt_adamw_flat_dev")
+                                           a.numel, L.ptr(tab), nseg, float(self.betas[0]), float(self.betas[1]),
+                                           float(self.eps), L.ptr(self._step_dev), float(grad_scale), L.stream_ptr()),
+                "evt_adamw_flat_dev")
 
     def sync_step_count(self):
         """the number of updates actually applied (the device counter: guarded steps that were skipped do not count)"""
@@ -180,9 +180,9 @@ class FlatAdamW:
         tab, nseg = self._segments()
         a = self.arena
         L.check(L.lib().evt_adamw_flat_dev_range(L.ptr(a.param), L.ptr(a.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                                 C.c_int64(lo), C.c_int64(hi), L.ptr(tab), nseg, C.c_float(self.betas[0]),
-                                                 C.c_float(self.betas[1]), C.c_float(self.eps), L.ptr(self._step_dev),
-                                                 1 if bump else 0, C.c_float(grad_scale), L.stream_ptr()),
+                                                 int(lo), int(hi), L.ptr(tab), nseg, float(self.betas[0]),
+                                                 float(self.betas[1]), float(self.eps), L.ptr(self._step_dev),
+                                                 1 if bump else 0, float(grad_scale), L.stream_ptr()),
                 "evt_adamw_flat_dev_range")
 
     def note_replayed_step(self):
@@ -358,7 +358,7 @@ class ModelRuntime:
     def grad_sumsq(self):
         """sum of squares of all gradients, as a device scalar (no host sync)"""
         self._sumsq.zero_()
-        L.check(L.lib().evt_sumsq(L.ptr(self.arena.grad), C.c_int64(self.arena.numel), L.ptr(self._sumsq),
+        L.check(L.lib().evt_sumsq(L.ptr(self.arena.grad), self.arena.numel, L.ptr(self._sumsq),
                                   L.stream_ptr()), "evt_sumsq")
         return self._sumsq
 
@@ -401,7 +401,7 @@ class DeviceGradScaler:
         if not self.enabled:
             return
         a = owner.arena
-        L.check(L.lib().evt_scaler_unscale(L.ptr(a.grad), C.c_int64(a.numel), L.ptr(self._scale), L.ptr(self.found_inf(owner)),
+        L.check(L.lib().evt_scaler_unscale(L.ptr(a.grad), a.numel, L.ptr(self._scale), L.ptr(self.found_inf(owner)),
                                            L.stream_ptr()), "evt_scaler_unscale")
 
     def update(self):
@@ -411,7 +411,7 @@ class DeviceGradScaler:
             flags = list(self._found.values())
             self._flag_table = (C.c_void_p * len(flags))(*[f.data_ptr() for f in flags])
         L.check(L.lib().evt_scaler_update(L.ptr(self._scale), L.ptr(self._tracker), self._flag_table, len(self._found),
-                                          C.c_float(self.growth_factor), C.c_float(self.backoff_factor),
+                                          float(self.growth_factor), float(self.backoff_factor),
                                           int(self.growth_interval), L.stream_ptr()), "evt_scaler_update")
 
     def get_scale(self):

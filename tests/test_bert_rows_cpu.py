@@ -247,7 +247,6 @@ def test_text_batch_skip_logic_and_file_formats(tmp_path):
 def test_libraries_export_the_bert_rows_entry_points():
     """both builds export evt_phone_expand_rows / evt_bert_embed_ln_rows, and the bindings pass as many arguments as
     include/evt.h declares"""
-    from easevoice_trainer_amd.hip import feat
     from easevoice_trainer_amd.hip import lib as L
 
     hdr = open(os.path.join(HERE, "..", "include", "evt.h")).read()
@@ -257,21 +256,20 @@ def test_libraries_export_the_bert_rows_entry_points():
         assert m, f"{name} is not declared in evt.h"
         declared[name] = len(m.group(1).split(","))
     assert declared == {"evt_phone_expand_rows": 12, "evt_bert_embed_ln_rows": 18}
-    assert len(feat.EXPAND_ARGTYPES) == declared["evt_phone_expand_rows"]
-    assert len(feat.EMBED_ARGTYPES) == declared["evt_bert_embed_ln_rows"]
     for half in (torch.bfloat16, torch.float16):
         L.set_half(half)
         lib = L.lib()
-        for name in declared:
+        for name, count in declared.items():
             assert hasattr(lib, name), f"{name} is not exported by the {half} build"
+            assert len(getattr(lib, name).argtypes) == count, f"{name} of the {half} build"
         # the argument checks return an error code before anything is launched (NULL pointers, C not a multiple of 8)
-        fn = feat._rows_entry("evt_phone_expand_rows", feat.EXPAND_ARGTYPES)
+        fn = lib.evt_phone_expand_rows
         assert fn(L.DT_F32, None, 1, 10, 64, None, None, 1, 5, L.DT_F32, None, None) == 22
         assert fn(L.DT_F32, 16, 1, 10, 60, 16, 16, 1, 5, L.DT_F32, 16, None) == 22
         assert fn(L.DT_F32, 16, 1, 10, 4104, 16, 16, 1, 5, L.DT_F32, 16, None) == 22
         assert fn(L.DT_F32, 16, 1, 10, 64, 16, 16, 1, 0, L.DT_F32, 16, None) == 0          # no columns: nothing to do
         assert fn(7, 16, 1, 10, 64, 16, 16, 1, 5, L.DT_F32, 16, None) == 95
-        fn = feat._rows_entry("evt_bert_embed_ln_rows", feat.EMBED_ARGTYPES)
+        fn = lib.evt_bert_embed_ln_rows
         assert fn(L.DT_F32, None, None, None, 1, 4, None, 10, None, 512, None, 2, None, None, 1e-12, 64, None, None) == 22
         assert fn(L.DT_F32, 16, None, 16, 1, 600, 16, 10, 16, 512, 16, 2, 16, 16, 1e-12, 64, 16, None) == 22   # T > max_pos
     L.set_half(torch.bfloat16)

@@ -94,10 +94,8 @@ def _expand_ref(h, src, item_off, out_dtype):
 
 def _expand_raw(L, h, src_d, off_d, n_items, total, buf):
     """the C entry on a caller's buffer: `buf` has GUARD elements in front of and behind the packed range"""
-    from easevoice_trainer_amd.hip import feat
-
     B, T, Cc = h.shape
-    rc = feat._rows_entry("evt_phone_expand_rows", feat.EXPAND_ARGTYPES)(
+    rc = L.lib().evt_phone_expand_rows(
         L.dt_of(h), h.data_ptr(), B, T, Cc, src_d.data_ptr(), off_d.data_ptr(), n_items, total, L.dt_code(buf.dtype),
         buf.data_ptr() + GUARD * buf.element_size(), L.stream_ptr())
     assert rc == 0, rc

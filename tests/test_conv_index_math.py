@@ -131,13 +131,24 @@ def test_igemm_index_math(case, dt):
 
 
 def test_library_exports_header_symbols():
-    """every function declared in include/evt.h is exported by the built library (no compute calls)"""
+    """every function declared in include/evt.h is exported by the built library and declared to ctypes with the header's
+    parameter count and return kind (no compute calls)"""
+    import ctypes as C
     import os
     import re
 
     hdr = open(os.path.join(os.path.dirname(__file__), "..", "include", "evt.h")).read()
     names = set(re.findall(r"\b(evt_[a-z0-9_]+)\s*\(", hdr))
     assert names, "no declarations parsed"
+    # parameters per prototype by comma count, independent of the parser of hip/lib.py; (void) is none
+    code = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    params = {n: 0 if p.strip() == "void" else p.count(",") + 1
+              for n, p in re.findall(r"\b(evt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)}
+    assert set(params) == names
+    restypes = {"evt_version": C.c_char_p, "evt_last_kernel_tag": C.c_char_p, "evt_debug_kernel_tags": None,
+                "evt_workspace_bytes": C.c_int64, "evt_mel_workspace_floats": C.c_int64,
+                "evt_resunit_bwd_ws_floats": C.c_int64, "evt_hubert_front_ws_floats": C.c_int64}
+    assert len(re.findall(r"\bconst char\s*\*\s*evt_", code)) == 2 and len(re.findall(r"\bint64_t\s+evt_\w+\s*\(", code)) == 4
     import torch
 
     # both builds of the sources export exactly the header: libevt_hip.so (bfloat16) and libevt_hip_f16.so (IEEE half)
@@ -146,6 +157,13 @@ def test_library_exports_header_symbols():
         lib = L.lib()
         missing = [n for n in sorted(names) if not hasattr(lib, n)]
         assert not missing, f"declared in evt.h but not exported by the {half} build: {missing}"
+        for n in sorted(names):
+            fn = getattr(lib, n)
+            assert fn.argtypes is not None and len(fn.argtypes) == params[n], f"{n} of the {half} build"
+            if n in restypes:
+                assert fn.restype is restypes[n], f"{n} of the {half} build returns {fn.restype}"
+            else:
+                assert fn.restype in (C.c_int, C.c_int32), f"{n} of the {half} build returns {fn.restype}"
         assert lib.evt_half_dtype() == code and tag in lib.evt_version().decode()
     L.set_half(torch.bfloat16)
 

@@ -149,7 +149,6 @@ def test_prompt_semantics_padding_and_cut():
 def test_libraries_export_the_rows_entry_points():
     """both builds export evt_hubert_front_rows / evt_clip_rescale_rows, and the bindings pass as many arguments as
     include/evt.h declares (the existing ABI test's way: the header is the list)"""
-    from easevoice_trainer_amd.hip import feat
     from easevoice_trainer_amd.hip import lib as L
 
     hdr = open(os.path.join(HERE, "..", "include", "evt.h")).read()
@@ -159,18 +158,14 @@ def test_libraries_export_the_rows_entry_points():
         assert m, f"{name} is not declared in evt.h"
         declared[name] = len(m.group(1).split(","))
     assert declared == {"evt_hubert_front_rows": 13, "evt_clip_rescale_rows": 8, "evt_hubert_front_ws_floats": 2}
-    assert len(feat.FRONT_ARGTYPES) == declared["evt_hubert_front_rows"]
-    assert len(feat.RESCALE_ARGTYPES) == declared["evt_clip_rescale_rows"]
     for half in (torch.bfloat16, torch.float16):
         L.set_half(half)
         lib = L.lib()
-        for name in declared:
+        for name, count in declared.items():
             assert hasattr(lib, name), f"{name} is not exported by the {half} build"
-        lib.evt_hubert_front_ws_floats.restype = __import__("ctypes").c_int64
+            assert len(getattr(lib, name).argtypes) == count, f"{name} of the {half} build"
         assert lib.evt_hubert_front_ws_floats(3, 9000) == 3 * 512 * (29 + 2)        # host arithmetic, no launch
         # NULL pointers are refused before anything is launched
-        fn = feat._rows_entry("evt_hubert_front_rows", feat.FRONT_ARGTYPES)
-        assert fn(L.DT_F32, None, None, 1, 100, None, None, None, 1e-5, None, None, 0, None) == 22
-        fn = feat._rows_entry("evt_clip_rescale_rows", feat.RESCALE_ARGTYPES)
-        assert fn(None, None, 1, 100, None, None, None, None) == 22
+        assert lib.evt_hubert_front_rows(L.DT_F32, None, None, 1, 100, None, None, None, 1e-5, None, None, 0, None) == 22
+        assert lib.evt_clip_rescale_rows(None, None, 1, 100, None, None, None, None) == 22
     L.set_half(torch.bfloat16)

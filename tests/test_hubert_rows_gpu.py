@@ -109,7 +109,6 @@ def _front_raw(gpu, dtype_code, wav, lens, w, gamma, beta, out, ws, ws_floats=No
 
     p = lambda t: C.c_void_p(t if isinstance(t, int) else (t.data_ptr() if t is not None else 0))  # noqa: E731
     fn = L.lib().evt_hubert_front_rows
-    fn.argtypes, fn.restype = None, C.c_int
     return fn(C.c_int32(dtype_code), p(wav), p(lens), C.c_int32(wav.size(0) if nseq is None else nseq),
               C.c_int32(wav.size(1) if n is None else n), p(w), p(gamma), p(beta), C.c_float(eps), p(out), p(ws),
               C.c_int64(ws.numel() if ws_floats is None else ws_floats), L.stream_ptr())
@@ -125,7 +124,6 @@ def test_front_rows_write_every_element_and_refuse_bad_arguments(gpu):
     lens = torch.tensor([r.numel() for r in rows], dtype=torch.int32).to(gpu)
     w, gamma, beta = case["w"].to(gpu), case["gamma"].to(gpu), case["beta"].to(gpu)
     lib = L.lib()
-    lib.evt_hubert_front_ws_floats.restype = C.c_int64
     t1 = (9003 - 10) // 5 + 1
     need = lib.evt_hubert_front_ws_floats(len(rows), 9003)
     assert need == len(rows) * 512 * (-(-t1 // 64) + 2)

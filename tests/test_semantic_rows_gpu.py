@@ -123,7 +123,7 @@ def test_invalid_calls_return_einval(gpu):
     from easevoice_trainer_amd.hip import lib as L
 
     EINVAL = 22
-    fn = HF._rows_entry("evt_semantic_codes_rows", HF.SEMANTIC_ARGTYPES)
+    fn = L.lib().evt_semantic_codes_rows
     B, T, D, K = 2, 8, 128, 72
     hs = torch.zeros(B, T, D, device=gpu)
     frames = torch.tensor([8, 4], dtype=torch.int32, device=gpu)
