@@ -11,7 +11,7 @@ from typing import List
 import numpy as np
 import torch
 
-from . import conv as _conv
+from . import trace as T
 from . import lib as L
 from ..feature_extractor.normalize import _BETA, _ROLLOFF, _ZEROS
 
@@ -143,12 +143,12 @@ def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, inter
         return PackedAudio(data, offsets, lengths, int(out_rate), gap)
     off_dev = torch.tensor(offsets, dtype=torch.int64).to(x.device)
     table, j_pad = (None, 0) if up == down == 1 else (phase_table(up, down, x.device), table_shape(up, down)[1])
-    e0 = _conv._t0()
+    e0 = T.t0()
     L.check(L.lib().evt_resample_pack_rows(L.dt_of(x), L.ptr(x), L.ptr(lens_dev), mul, nseq, length, up, down, L.ptr(table),
                                            j_pad, code, L.ptr(data), total, L.ptr(off_dev), gap, L.stream_ptr()),
             "evt_resample_pack_rows")
     if e0 is not None:
-        _conv._t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
+        T.t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
     return PackedAudio(data, offsets, lengths, int(out_rate), gap)
 
 
@@ -192,9 +192,9 @@ def ref_spec_rows(x, lens, hop=640, bins=704, lens_dev=None):
     window = _window(REF_NFFT, x.device)              # the tensor spectrogram_torch hands its kernel
     spec = torch.empty((nseq, ref_frames(n, hop), bins), dtype=torch.float32, device=x.device)
     peak = torch.empty(nseq, dtype=torch.float32, device=x.device)
-    e0 = _conv._t0()
+    e0 = T.t0()
     L.check(L.lib().evt_ref_spec_rows(L.ptr(x), L.ptr(lens_dev), nseq, n, L.ptr(window), REF_NFFT, hop, bins,
                                       L.ptr(spec), L.ptr(peak), L.stream_ptr()), "evt_ref_spec_rows")
     if e0 is not None:
-        _conv._t1_elt(e0, "ref_spec_kernel", (x.numel() + spec.numel()) * 4, None)
+        T.t1_elt(e0, "ref_spec_kernel", (x.numel() + spec.numel()) * 4, None)
     return spec, frames, peak

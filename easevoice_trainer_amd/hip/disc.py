@@ -18,6 +18,7 @@ import torch
 
 from . import conv as HC
 from . import lib as L
+from . import trace as TR
 
 # The six sub-discriminators are independent between the fold of their inputs and the loss launches: with
 # EVT_MPD_STREAMS = n > 1 they are dealt round-robin onto the current stream and n - 1 side streams (forward and
@@ -36,7 +37,7 @@ def _new_stream(dev, k):
 
 def _branches(dev, n_items):
     """stream of every sub-discriminator (None = the current stream) and the distinct side streams among them"""
-    n = MPD_STREAMS if (dev.type == "cuda" and HC.TRACE is None) else 1
+    n = MPD_STREAMS if (dev.type == "cuda" and TR.TRACE is None) else 1
     if n <= 1:
         return [None] * n_items, []
     pool = _side.setdefault(dev, [])
@@ -53,7 +54,7 @@ ENC_STREAM = _ALL and os.environ.get("EVT_ENC_STREAM", "1") != "0"
 def enc_lane(dev):
     """side stream for the prior encoder of SynthesizerTrn.forward (independent of posterior encoder / flow / vocoder until
     the KL term), or None"""
-    if not ENC_STREAM or dev.type != "cuda" or HC.TRACE is not None:
+    if not ENC_STREAM or dev.type != "cuda" or TR.TRACE is not None:
         return None
     pool = _side.setdefault(dev, [])
     if not pool:
@@ -67,7 +68,7 @@ DEC_STREAM = _ALL and os.environ.get("EVT_DEC_STREAM", "1") != "0"
 def dec_lane(dev):
     """side stream for two of the three parallel ResBlocks of a wide vocoder stage (models.py:461-466: xs = sum of the blocks'
     outputs; the narrow stages run the three as grouped launches instead), or None"""
-    if not DEC_STREAM or dev.type != "cuda" or HC.TRACE is not None:
+    if not DEC_STREAM or dev.type != "cuda" or TR.TRACE is not None:
         return None
     pool = _side.setdefault(dev, [])
     while len(pool) < 2:

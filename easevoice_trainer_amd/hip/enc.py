@@ -305,7 +305,7 @@ class RelSelfAttnFn(torch.autograd.Function):
 
 
 def rel_self_attention(x, conv_q, conv_k, conv_v, emb_k, emb_v, lens, n_heads, window, p, site, packed=None, scale=None):
-    """packed: hip/conv.py::PackedConv of the three projections (one launch each way) or None (three); window None: no
+    """packed: hip/bank.py::PackedConv of the three projections (one launch each way) or None (three); window None: no
     relative positions (emb_k / emb_v ignored); scale None: 1/sqrt(head width)"""
     slots = (packed._slot,) if packed is not None and packed._slot is not None else (conv_q._slot, conv_k._slot, conv_v._slot)
     if any(s is None for s in slots):

@@ -13,6 +13,8 @@ import ctypes as C
 import torch
 
 from . import lib as L
+from .bank import align128
+from .launch import _bias
 
 N_ALIGN = 128      # an output width that is not a multiple of 128 is padded up to it (zero rows / columns)
 
@@ -78,8 +80,8 @@ class LinearBank:
             s.layout = lay
             self.slots.append(s)
             offs.append((reg_n, alt_n))
-            reg_n += (lay.reg_elems + 127) // 128 * 128
-            alt_n += (lay.alt_elems + 127) // 128 * 128
+            reg_n += align128(lay.reg_elems)
+            alt_n += align128(lay.alt_elems)
             w._evt_slot = s
         self.reg_arena = torch.zeros(max(reg_n, 1), dtype=dtype, device=device)
         self.alt_arena = torch.zeros(max(alt_n, 1), dtype=dtype, device=device)
@@ -193,7 +195,7 @@ def gemm_fwd(slot, x, relu=False, drop=None, add=None):
                          f"{tuple(x.shape)} {x.dtype} contiguous={x.is_contiguous()}")
     M = x.numel() // slot.K
     y = torch.empty(x.shape[:-1] + (slot.Np,), dtype=x.dtype, device=x.device)
-    bias = slot.bias.data if slot.bias is not None else None
+    bias = _bias(slot)
     lib = L.lib()
     p_drop, site = drop if drop is not None else (0.0, 0)
     if slot.fused(M, False):

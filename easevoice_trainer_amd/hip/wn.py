@@ -15,6 +15,9 @@ import torch
 
 from . import conv as HC
 from . import lib as L
+from . import trace as TR
+from .launch import _bias
+from .wgrad import WgJob
 
 
 class WNStackFn(torch.autograd.Function):
@@ -39,10 +42,9 @@ class WNStackFn(torch.autograd.Function):
                 acts = torch.empty((B, T, H), dtype=x.dtype, device=x.device)
                 acc_out = torch.empty((B, T, H), dtype=x.dtype, device=x.device)
                 x_out = None if last else torch.empty_like(acc_out)
-                e0 = HC._t0()
+                e0 = TR.t0()
                 L.check(L.lib().evt_wn_layer_fwd(dt, L.ptr(x), L.ptr(frag_in[i]),
-                                                 L.ptr(mi.bias.data if mi.bias is not None else None), L.ptr(frag_rs[i]),
-                                                 L.ptr(mr.bias.data if mr.bias is not None else None),
+                                                 L.ptr(_bias(mi)), L.ptr(frag_rs[i]), L.ptr(_bias(mr)),
                                                  L.ptr(g_lbh[i] if g_lbh is not None else None), L.ptr(out), L.ptr(lens),
                                                  L.ptr(x_in), L.ptr(acts), L.ptr(x_out), L.ptr(acc_out), B, T, H, mi.k,
                                                  int(last), L.stream_ptr()), "evt_wn_layer_fwd")
@@ -83,13 +85,13 @@ class WNStackFn(torch.autograd.Function):
         # GROUP_LAYERS layers: launched together they fill the chip with their tiles and need half the splits of their 3200
         # positions (half the slabs written, and folded at the end of the backward)
         # (a traced run keeps every launch where it was: behind the data half of its layer)
-        group = [] if (GROUP_WGRADS and HC.TRACE is None) else None
+        group = [] if (GROUP_WGRADS and TR.TRACE is None) else None
 
         def wgrad(*args):
             if group is None:
                 HC._bwd_weight(*args)
                 return
-            group.append(args)
+            group.append(WgJob(*args))
             if len(group) >= 2 * GROUP_LAYERS:       # a long stack hands its layers over in runs, beside its own data chain
                 HC._bwd_weight_group(list(group))
                 group.clear()
@@ -104,7 +106,7 @@ class WNStackFn(torch.autograd.Function):
                 drs = torch.empty((B, T, rs_w), dtype=dtype, device=dev)
                 dx_in = torch.empty((B, T, 2 * H), dtype=dtype, device=dev)
                 dx = torch.empty((B, T, H), dtype=dtype, device=dev)
-                e0 = HC._t0()
+                e0 = TR.t0()
                 L.check(L.lib().evt_wn_layer_bwd_data(dt, L.ptr(dx_next), L.ptr(dacc), L.ptr(x_in),
                                                       L.ptr(g_lbh[i] if g_lbh is not None else None),
                                                       L.ptr(sr.bank.frag(sr, "alt")), L.ptr(si.bank.frag(si, "alt")),
@@ -193,16 +195,10 @@ def _t1_layer(e0, mi, mr, x, kind="fwd"):
     """trace record of one fused layer launch (bench.py's per-launch table): flops of both convolutions; bytes: forward = x and
     the skip sum in, x_in / acts / x / skip sum out; backward-data = the two gradients and x_in in, drs / dx_in / dx out; both
     weight images either way"""
-    e0, rf = e0
-    e1 = torch.cuda.Event(enable_timing=True)
-    e1.record()
-    if rf is not None:
-        rf.__exit__(None, None, None)
     n, ln, h = x.shape
     macs = n * ln * (mi.cin * mi.cout * mi.k + mr.cin * mr.cout)
-    HC.TRACE.append((L.lib().evt_last_kernel_tag().decode(), kind, 2 * macs,
-                     (7 * x.numel() + mi.v.numel() + mr.v.numel()) * 2, e0, e1,
-                     f"WN layer {h}>{mi.cout}>{mr.cout} k{mi.k} n{n} L{ln}", mi))
+    TR.t1(e0, None, kind, 2 * macs, (7 * x.numel() + mi.v.numel() + mr.v.numel()) * 2,
+         f"WN layer {h}>{mi.cout}>{mr.cout} k{mi.k} n{n} L{ln}", mi)
 
 
 def wn_stack(x, g_lbh, lens, in_layers, rs_layers, hidden):

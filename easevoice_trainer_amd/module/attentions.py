@@ -100,7 +100,7 @@ class MultiHeadAttention(nn.Module):
         nn.init.xavier_uniform_(self.conv_k.weight)
         nn.init.xavier_uniform_(self.conv_v.weight)
         self._site = new_site()      # dropout stream id of the fused attention launch
-        self._qkv_packed = None      # hip/conv.py::PackedConv of the three projections, set by the bf16 WeightBank
+        self._qkv_packed = None      # hip/bank.py::PackedConv of the three projections, set by the bf16 WeightBank
 
     def qkv_pack_modules(self):
         """the three projections when they can run as ONE [3C, C] GEMM: the windowed self-attention layers of the

@@ -14,7 +14,7 @@ mrte_model.py:9-61, core_vq.py:172-228), re-laid-out for the hardware:
     matmul / softmax on the training path;
   * DiscriminatorP's period axis is laid out as extra sequences ([B*p, T/p, C]) instead of a 2-D image.
 
-There is no CPU / eager fallback: the modules need a WeightBank (hip/conv.py) and a GPU.
+There is no CPU / eager fallback: the modules need a WeightBank (hip/bank.py) and a GPU.
 """
 
 import functools
@@ -638,7 +638,7 @@ class Generator(nn.Module, _ComputeDtype):
             if lens is not None:
                 mul *= self.ups[i].stride
             if x.is_cuda:
-                # narrow stages: step j of the three blocks is one grouped launch each way (hip/conv.py::ResStageFn)
+                # narrow stages: step j of the three blocks is one grouped launch each way (hip/resunit.py::ResStageFn)
                 xs = res_stage(x, blocks, LRELU_SLOPE, 1.0 / self.num_kernels, lens, mul)
                 if xs is not None:
                     x = xs

@@ -29,7 +29,7 @@ class ParamArena:
         params = [(n, p) for n, p in model.named_parameters()]
         # sub-modules may ask for some of their parameters to sit next to each other (`arena_adjacent()`: lists of
         # relative names), e.g. the q / k / v projection weights of an attention layer, which then form ONE dense
-        # [3C, C] matrix for a single GEMM launch (hip/conv.py::PackedConv).  The arena order is otherwise the
+        # [3C, C] matrix for a single GEMM launch (hip/bank.py::PackedConv).  The arena order is otherwise the
         # registration order; nothing but the offsets depends on it.
         order = [n for n, _ in params]
         for mod_name, mod in model.named_modules():
@@ -329,8 +329,8 @@ class ModelRuntime:
         bank.check_tables()
         cur, book = torch.cuda.current_stream(self.device), self.book_stream()
         book.wait_stream(cur)
-        if bank._side is not None:
-            book.wait_stream(bank._side)
+        if bank.wgq.side is not None:
+            book.wait_stream(bank.wgq.side)
         with torch.cuda.stream(book):
             for lo, hi in grad_rows:
                 bank.grads(lo, hi, join=False)

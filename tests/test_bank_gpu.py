@@ -1,4 +1,4 @@
-"""WeightBank bookkeeping on the GPU (hip/conv.py): gradient tables that follow replaced .grad tensors, the deferred
+"""WeightBank bookkeeping on the GPU (hip/bank.py): gradient tables that follow replaced .grad tensors, the deferred
 weight-gradient queue cleared by zero_dw(), extra slabs that start as zeros."""
 import pytest
 import torch
@@ -53,9 +53,9 @@ def test_zero_dw_drops_a_stale_deferred_queue(gpu):
     bank.defer_n = 64
     x = torch.randn(2, 320, 64, device=gpu).bfloat16().requires_grad_(True)
     conv(x).backward(torch.randn(2, 320, 64, device=gpu).bfloat16())
-    assert bank._deferred, "the launch must have been queued"
+    assert bank.wgq.pending, "the launch must have been queued"
     bank.zero_dw()
-    assert not bank._deferred and not bank._held and bank._deferred_bytes == 0
+    assert not bank.wgq.pending and not bank.wgq.held and bank.wgq.nbytes == 0
     bank.grads()
     torch.cuda.synchronize()
     assert float(conv.weight_v.grad.abs().max()) == 0.0

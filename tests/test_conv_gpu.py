@@ -189,10 +189,11 @@ def test_conv_narrow_parity(gpu, ci):
 
     case = NARROW_CASES[ci]
     for fusion in (FUSIONS[0], FUSIONS[2], FUSIONS[1]):
-        HC.set_trace([])
+        rec = []
+        HC.set_trace(rec)
         try:
             _run_case(gpu, case, fusion, HALF, 0)
-            tags = {(r[1], r[0].split(",")[0]) for r in HC.TRACE}
+            tags = {(r[1], r[0].split(",")[0]) for r in rec}
         finally:
             HC.set_trace(None)
         if fusion["in_slope"] == 1.0:
@@ -206,10 +207,11 @@ def test_conv_ring_parity(gpu, ci):
 
     case = RING_CASES[ci]
     for fusion in (FUSIONS[2], FUSIONS[0]):
-        HC.set_trace([])
+        rec = []
+        HC.set_trace(rec)
         try:
             _run_case(gpu, case, fusion, HALF, 0)
-            tags = {(r[1], r[0]) for r in HC.TRACE}
+            tags = {(r[1], r[0]) for r in rec}
         finally:
             HC.set_trace(None)
         assert ("fwd", "conv_ring<bf16, 64, 64, 64, x4>") in tags, tags
@@ -224,10 +226,11 @@ def test_conv_deep_parity(gpu, ci):
 
     case = DEEP_CASES[ci]
     for fusion in (FUSIONS[2], FUSIONS[0]):
-        HC.set_trace([])
+        rec = []
+        HC.set_trace(rec)
         try:
             _run_case(gpu, case, fusion, HALF, 0)
-            tags = {(r[1], r[0]) for r in HC.TRACE}
+            tags = {(r[1], r[0]) for r in rec}
         finally:
             HC.set_trace(None)
         deep = {"conv_deep<bf16, 128, 128, 64>", "conv_deep32<bf16, 128, 128, 32>"}
@@ -257,10 +260,11 @@ def test_upsampler_preactivated_parity(gpu, ci):
     for plain in (True, False):
         old = HC.PLAIN_X
         HC.PLAIN_X = plain
-        HC.set_trace([])
+        rec = []
+        HC.set_trace(rec)
         try:
             _run_case(gpu, case, fusion, HALF, 0)
-            tags = {(r[1], r[0]) for r in HC.TRACE}
+            tags = {(r[1], r[0]) for r in rec}
         finally:
             HC.set_trace(None)
             HC.PLAIN_X = old
@@ -319,10 +323,11 @@ def test_wgrad_halo_parity(gpu, ci):
 
     case = HALO_CASES[ci]
     for fusion in (FUSIONS[0], FUSIONS[2]):
-        HC.set_trace([])
+        rec = []
+        HC.set_trace(rec)
         try:
             _run_case(gpu, case, fusion, HALF, 0)
-            tags = {(r[1], r[0]) for r in HC.TRACE}
+            tags = {(r[1], r[0]) for r in rec}
         finally:
             HC.set_trace(None)
         assert any(k == "bwd_weight" and t.startswith("wgrad_halo<") for k, t in tags), tags

@@ -16,7 +16,7 @@ Rounding points the kernels take on purpose, and how the operands stay represent
     16-bit image rounds back to v and an fp32 image keeps.  The fp32 runs therefore take the weight_norm=False module of the
     same geometry (the same kernels: the fold is the only difference); the fp32 weight-norm fold stays with
     tests/test_conv_gpu.py at 1e-3;
-  * hip/conv.py::ResUnitFn / resunit_bwd store xa, the mid activation and dmid in 16 bits: all three are among the tensors
+  * hip/resunit.py::ResUnitFn / resunit_bwd store xa, the mid activation and dmid in 16 bits: all three are among the tensors
     the CPU file bounds (for the dense +-1 pass dmid only where exact_inputs.resunit_dense_judges_first says so).
 """
 import json

@@ -351,7 +351,7 @@ def test_single_gpu_id_selects_that_device(monkeypatch):
 
 def test_param_arena_adjacent_groups_and_prefix_ranges():
     """ParamArena honours a sub-module's arena_adjacent() (the q / k / v projection weights of an attention layer laid out
-    back to back, so that they form one dense matrix: hip/conv.py::PackedConv) without touching names, shapes or state_dict
+    back to back, so that they form one dense matrix: hip/bank.py::PackedConv) without touching names, shapes or state_dict
     order; range_of_prefix gives the contiguous range of a sub-model (what the data-parallel step reduces on its own)."""
     from easevoice_trainer_amd.runtime import ParamArena
 
@@ -585,7 +585,7 @@ def test_reduce_scatter_all_gather_equals_all_reduce():
 
 
 def test_slab_count_policy():
-    """slabs per gradient image (hip/conv.py::slab_count): bounded by the memory budget, by the fold cap for ordinary
+    """slabs per gradient image (hip/bank.py::slab_count): bounded by the memory budget, by the fold cap for ordinary
     layers, lifted for the layers whose parallelism is all position split"""
     from easevoice_trainer_amd.hip.conv import slab_count
 

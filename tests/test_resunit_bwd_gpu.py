@@ -1,4 +1,4 @@
-"""GPU parity of the fused backward of a HiFi-GAN ResBlock step (csrc/resunit_bwd.hip through hip/conv.py::resunit_bwd;
+"""GPU parity of the fused backward of a HiFi-GAN ResBlock step (csrc/resunit_bwd.hip through hip/resunit.py::resunit_bwd;
 reference: torch.autograd over src/easevoice/module/modules.py:299-308): dx, both weight-gradient images and both bias
 gradients of ONE launch against (a) the four launches it replaces (evt_conv1d_bwd_data x 2, evt_conv1d_bwd_weight x 2)
 and (b) the CPU oracle (oracle/ops.py::res_unit differentiated by torch in fp32 on the same bf16-rounded operands);
@@ -161,7 +161,7 @@ def test_fused_backward_vs_oracle(gpu, case):
 @pytest.mark.parametrize("case", [(16, 333), (32, 200), (16, 64), (32, 1000)])
 def test_grouped_stage_vs_block_by_block(gpu, case):
     """one HiFi-GAN stage (three ResBlock1 of kernel sizes 3 / 7 / 11, dilations 1 / 3 / 5, averaged: models.py:457-466)
-    through the grouped launches (hip/conv.py::ResStageFn) against the same modules run block by block, step by step
+    through the grouped launches (hip/resunit.py::ResStageFn) against the same modules run block by block, step by step
     (ResUnitFn + Add3ScaleFn): output, input gradient, every parameter gradient; and the grouped path twice: same bits"""
     from easevoice_trainer_amd.hip import conv as HC
     from easevoice_trainer_amd.module.models import LRELU_SLOPE, ResBlock1

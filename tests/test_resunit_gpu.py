@@ -1,4 +1,4 @@
-"""GPU parity of the fused HiFi-GAN ResBlock step (csrc/resunit.hip through hip/conv.py::ResUnitFn):
+"""GPU parity of the fused HiFi-GAN ResBlock step (csrc/resunit.hip through hip/resunit.py::ResUnitFn):
 y = x + c2(lrelu(c1(lrelu(x)))) (src/easevoice/module/modules.py:299-308) for the narrow vocoder stages, against
 (a) the CPU oracle's convolutions (oracle/ops.py, fp32 on bf16-rounded inputs / folded weights) and (b) the three-launch
 composition it replaces; forward outputs, the two saved activations, dx and all parameter gradients."""

@@ -1,4 +1,4 @@
-"""Grouped weight-gradient launches (evt_conv1d_bwd_weight_group, hip/conv.py::_bwd_weight_group).
+"""Grouped weight-gradient launches (evt_conv1d_bwd_weight_group, hip/wgrad.py::_bwd_weight_group).
 
 Operands are small integers (tests/exact_inputs.py::small_int): every product and every partial sum is an integer far
 below 2^24, so fp32 accumulation is exact in any order and the grouped result has to be BIT-EQUAL to the single launches and
@@ -80,7 +80,7 @@ class Setup:
                 x, dy = X.small_int(shape_x, g), X.small_int(shape_dy, g)
             self.x.append(x)
             self.dy.append(dy)
-        self.args = [(m._slot, self.dev(x), self.dev(dy), None, self.nseq, self.lin, 1.0, L.ACT_NONE, 1.0)
+        self.args = [HC.WgJob(m._slot, self.dev(x), self.dev(dy), None, self.nseq, self.lin, 1.0, L.ACT_NONE, 1.0)
                      for m, x, dy in zip(self.mods, self.x, self.dy)]
 
     def dev(self, t):
@@ -117,8 +117,8 @@ class Setup:
                     HC._bwd_weight(*a)
         bank.join_side()
         torch.cuda.synchronize()
-        used_dev = [tuple(a[0].used.cpu().tolist()) for a in args]
-        used_host = [a[0].wg_used for a in args]
+        used_dev = [tuple(a.slot.used.cpu().tolist()) for a in args]
+        used_host = [a.slot.wg_used for a in args]
         if not finish:           # (the gradient pass folds the slabs into slab 0: exactly once per backward)
             return None, used_dev, used_host
         bank.grads()
@@ -306,7 +306,7 @@ def test_queue_and_stream_order_give_identical_gradients(gpu, dn):
             n = 2 * W.GROUP_LAYERS
             want = [n, 6 - n, n, 8 - n] if W.GROUP_LAYERS == 2 else None
             assert W.GROUP_LAYERS == 2 and seen == ([] if mode == "ungrouped" else want), (mode, seen)
-            assert not bank._deferred and not bank._held
+            assert not bank.wgq.pending and not bank.wgq.held
         for n, a in res["deferred"].items():
             assert torch.equal(a, res["stream"][n]), n
             b = res["ungrouped"][n]
@@ -322,9 +322,9 @@ def test_zero_dw_drops_an_abandoned_group(gpu):
     s = Setup(gpu, "ring5", "bf16")
     s.bank.defer_n = 48
     s.HC._bwd_weight_group(s.args)         # stays in the queue, as behind a backward that never reached grads()
-    assert len(s.bank._deferred) == 1 and isinstance(s.bank._deferred[0], s.HC.WgGroup) and len(s.bank._deferred[0]) == 3
+    assert len(s.bank.wgq.pending) == 1 and isinstance(s.bank.wgq.pending[0], s.HC.WgGroup) and len(s.bank.wgq.pending[0]) == 3
     s.bank.zero_dw()
-    assert not s.bank._deferred and not s.bank._held and s.bank._deferred_bytes == 0
+    assert not s.bank.wgq.pending and not s.bank.wgq.held and s.bank.wgq.nbytes == 0
     s.bank.defer_n = 0
     group, _, _ = s.run(grouped=True)
     assert_reference(s, group, 1.0, "after an abandoned group")
@@ -342,7 +342,7 @@ def test_traced_group_is_single_launches(gpu):
             s.HC.set_trace(None)
         tags = [r[0] for r in rec if r[1] == "bwd_weight"]
         assert len(tags) == 3 and all(t.startswith("wgrad_ring<") and "group" not in t for t in tags), tags
-        assert not s.bank._deferred
+        assert not s.bank.wgq.pending
         assert_reference(s, grads, 1.0, "traced")
 
 
@@ -371,8 +371,8 @@ def test_captured_group_replays_on_new_operands(gpu):
         s._ref.clear()
         for i, a in enumerate(s.args):
             s.x[i], s.dy[i] = X.small_int(tuple(s.x[i].shape), g), X.small_int(tuple(s.dy[i].shape), g)
-            a[1].copy_(s.dev(s.x[i]))
-            a[2].copy_(s.dev(s.dy[i]))
+            a.x.copy_(s.dev(s.x[i]))
+            a.dy.copy_(s.dev(s.dy[i]))
         graph.replay()
         torch.cuda.synchronize()
         got = [(m.v.grad.detach().float().cpu().clone(), None, m.bias.grad.detach().float().cpu().clone()) for m in s.mods]

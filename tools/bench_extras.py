@@ -4,7 +4,8 @@ Per-kernel durations come from torch.profiler (kineto -> roctracer/rocprofiler a
 clock `rocprofv3 --kernel-trace` reads), collected inside bench.py over eager steps of the timed workload.  The
 rocprofv3 summaries of the same command are committed under profiles/ (run with --no-extras: two tracers do not share
 a process); the average duration bench.py reports for the dominant kernel is the figure those files show.
-Algorithmic flops / bytes per launch: hip/conv.py's trace records (every operand tensor of a launch once).
+Algorithmic flops / bytes per launch: the trace records of hip/trace.py, written by the launch sites in hip/ (SURVEY §8(d):
+every operand tensor of a launch once).
 """
 import json
 import os
@@ -73,7 +74,7 @@ def align_records(rec, seq):
     (plus, for some weight gradients, a column-sum helper), and the library's tags start with that kernel's function
     name -- so the records are a subsequence of the conv-family kernels of the run; conv-family kernels launched by an
     untraced entry point are stepped over (greedy two-pointer match on the function name).  The element-wise launches of
-    hip/conv.py and the fold launch behind a fused ResBlock backward have records of their own (kind "elt")."""
+    hip/launch.py and the fold launch behind a fused ResBlock backward have records of their own (kind "elt")."""
     base = lambda n: n.split("<")[0].strip()
     main = [(base(short_name(n)), us) for _t, n, us in seq if _MAIN.match(base(short_name(n)))]
     out, j = {}, 0

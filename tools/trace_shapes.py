@@ -1,5 +1,5 @@
 """Per-(kernel, shape) time table of one s2 training step: the conv entry points are bracketed with HIP events
-(hip/conv.py TRACE) and grouped by the launched kernel instantiation and the layer geometry.  Development tool —
+(hip/trace.py) and grouped by the launched kernel instantiation and the layer geometry.  Development tool —
 shows which layers a kernel's aggregate time in `rocprofv3 --stats` comes from.
 
     python tools/trace_shapes.py [--top 40]
@@ -29,12 +29,12 @@ def main():
 
     world, rank, local = bench.init_dist(1)
     res, eng, step = bench.run_s2(args, world, rank, local)
-    HC.set_trace([])
+    rec = []
+    HC.set_trace(rec)
     n = 2
     for _ in range(n):
         step()
     torch.cuda.synchronize()
-    rec = HC.TRACE
     HC.set_trace(None)
     agg = {}
     for tag, kind, flops, nbytes, e0, e1, shape, _m in rec:
