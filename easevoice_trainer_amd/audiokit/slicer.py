@@ -6,9 +6,12 @@ their peaks, one launch their RMS frames (bit for bit the reference's get_rms), 
 logic below walks them, and one peak launch plus one pack launch rescale every chunk of every recording into one packed
 int16 buffer.  The tag logic is host work by nature: a few comparisons per silent run.
 
-ffmpeg decoding stays outside: recordings are float32 arrays, or PCM16 mono wav files at the slicer's
-rate."""
+Recordings are float32 arrays at the slicer's rate, or WAV files of any encoding, channel count and rate audiokit/wav.py
+serves: their bytes are uploaded as they are and decoded, mixed down and resampled to the slicer's rate by one launch per
+input rate (hip/audio.py::ingest_pcm) into the same packed buffer.  Compressed formats (mp3, flac, ogg) still need a
+decoder in front."""
 import os
+import time
 from dataclasses import dataclass, field
 from typing import NamedTuple
 
@@ -125,19 +128,19 @@ def slice_name(name, start, end):
     return "%s_%010d_%010d.wav" % (os.path.basename(name).split(".")[0], start, end)
 
 
-def _load(rec, params):
-    if isinstance(rec, (str, os.PathLike)):
-        from ..train.dataset import read_wav_pcm16
+def _is_path(rec):
+    return isinstance(rec, (str, os.PathLike))
 
-        rec = read_wav_pcm16(os.fspath(rec), params.sr)
+
+def _check(rec):
     if not isinstance(rec, np.ndarray) or rec.dtype != np.float32 or rec.ndim != 1:
-        raise ValueError("slice_batch: a recording is a 1-D float32 numpy array or the path of a PCM16 mono wav file, got "
+        raise ValueError("slice_batch: a recording is a 1-D float32 numpy array or the path of a wav file, got "
                          f"{type(rec).__name__}" + (f" {rec.dtype} {rec.shape}" if isinstance(rec, np.ndarray) else ""))
     return rec
 
 
 def _upload(recs, device):
-    """the recordings back to back in one fp32 device buffer: one copy from pinned memory"""
+    """the array recordings back to back in one fp32 device buffer: one copy from pinned memory"""
     import torch
 
     host = torch.empty(sum(r.shape[0] for r in recs), dtype=torch.float32, pin_memory=True)
@@ -151,7 +154,10 @@ def _upload(recs, device):
 def slice_batch(names, recordings, params=SlicerParams(), normalize_max=0.9, alpha_mix=0.25, out_dir=None, device="cuda:0",
                 stats=None):
     """AudioService.slicer for a batch: names[r] names recordings[r], a 1-D float32 array at params.sr (32000, the
-    service's rate) or the path of a PCM16 mono wav file at that rate.  params: one SlicerParams, or one per recording
+    service's rate) or the path of a WAV file (audiokit/wav.py: six encodings, 1 .. 8 channels, any rate hip/audio.py's
+    rate_ratio serves; decoded, mixed down and resampled to params.sr on the GPU, the reference's load_audio(file, 32000)
+    with the boundary hip/audio.py::load_audio_batch states; a 32 kHz PCM16 file gives the samples it always gave).
+    params: one SlicerParams, or one per recording
     (recordings that share win and hop share an RMS launch: one launch for one SlicerParams).
 
     -> per recording (ok, [Slice(name, start, end, pcm, peak)]): pcm an int16 view into one packed device buffer (a
@@ -165,8 +171,10 @@ def slice_batch(names, recordings, params=SlicerParams(), normalize_max=0.9, alp
     having written the chunks in front of it: those are returned, with ok = False.  An all-zero chunk, for which the
     reference casts NaN to int16 (undefined in numpy), is written as zeros.
 
-    stats: a dict that receives upload_s and walk_s (host clock; the upload is synchronised for it) and the event pairs
-    rms_events / pack_events around the two groups of launches -- the benchmark's hooks, no cost when None."""
+    stats: a dict that receives upload_s and walk_s (host clock; the upload -- arrays and file bytes -- is synchronised
+    for it), stage_s where files are given (their headers and the reads into page-locked memory, in front of upload_s)
+    and the event pairs ingest_events / rms_events / pack_events around the three groups of launches -- the benchmark's
+    hooks, no cost when None."""
     names, recordings = list(names), list(recordings)
     if len(names) != len(recordings):
         raise ValueError(f"slice_batch: {len(names)} names for {len(recordings)} recordings")
@@ -177,13 +185,26 @@ def slice_batch(names, recordings, params=SlicerParams(), normalize_max=0.9, alp
         raise ValueError(f"slice_batch slices at {SLICE_RATE} Hz, as the service does")
     if not names:
         return []
-    recs = [_load(r, p) for r, p in zip(recordings, plist)]
+    files = [r for r, rec in enumerate(recordings) if _is_path(rec)]
+    arrays = [r for r, rec in enumerate(recordings) if not _is_path(rec)]
+    for r in arrays:
+        _check(recordings[r])
+    lens = [0 if _is_path(rec) else rec.shape[0] for rec in recordings]
+    batch = None
+    if files:
+        from . import wav
+        from ..hip.audio import out_len, rate_ratio
+
+        t0 = time.perf_counter()
+        infos = [wav.probe(recordings[r]) for r in files]
+        for r, info in zip(files, infos):                 # EvtError for a rate pair that is not served: nothing is read yet
+            lens[r] = out_len(info.frames, *rate_ratio(info.rate, SLICE_RATE))
+        batch = wav.stage([recordings[r] for r in files], infos=infos)
+        if stats is not None:
+            stats["stage_s"] = time.perf_counter() - t0
     results = [(False, []) for _ in names]
-    lens = [r.shape[0] for r in recs]
     if not any(lens):
         return results
-
-    import time
 
     import torch
 
@@ -196,10 +217,24 @@ def slice_batch(names, recordings, params=SlicerParams(), normalize_max=0.9, alp
         offs.append(offs[-1] + n)
     t0 = time.perf_counter()
     with torch.no_grad(), torch.cuda.device(device):
-        x = _upload(recs, device)
+        x = _upload([recordings[r] for r in arrays], device) if arrays else None
+        raw_dev = A.upload_raw(batch, device) if files and any(lens[r] for r in files) else None
         if stats is not None:
             torch.cuda.synchronize()
             stats["upload_s"] = time.perf_counter() - t0
+        if files:
+            if stats is not None:
+                stats["ingest_events"] = ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            staged, x = x, torch.empty(offs[-1], dtype=torch.float32, device=device)
+            pos = 0
+            for r in arrays:                              # arrays between files: from the staging buffer to their place
+                x[offs[r]:offs[r] + lens[r]] = staged[pos:pos + lens[r]]
+                pos += lens[r]
+            A.ingest_pcm(batch, SLICE_RATE, device, raw_dev=raw_dev, out=x, offsets=[offs[r] for r in files])
+            if stats is not None:
+                ev[1].record()
+        if stats is not None:
             stats["rms_events"] = ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         live = [r for r, n in enumerate(lens) if n >= 1]

@@ -98,15 +98,25 @@ class FeatureWriter:
         clips for 5-wav32k, the 16 kHz clips as zero-filled rows [B, N16] on the GPU, their lengths).  One upload, one
         hip/feat.py::clip_rescale_rows, one hip/audio.py::resample_pack (32000 -> 16000, float32, no gap: resample_half's
         operator), peaks and int16 rows back in one copy each."""
-        from ..hip.audio import resample_pack
+        from ..hip.audio import ingest_pcm, out_len, rate_ratio, resample_pack
         from ..hip.feat import clip_rescale_rows
 
         device = self.hubert.device
-        lens = [len(c) for c in clips]
+        files = [b for b, c in enumerate(clips) if isinstance(c, str)]
+        if files:                                  # WAV files: headers first (a rate that is not served is an EvtError here)
+            from ..audiokit import wav
+
+            infos = [wav.probe(clips[b]) for b in files]
+            of_file = {b: out_len(i.frames, *rate_ratio(i.rate, 32000)) for b, i in zip(files, infos)}
+        lens = [of_file[b] if isinstance(c, str) else len(c) for b, c in enumerate(clips)]
         host = np.zeros((len(clips), max(lens)), dtype=np.float32)
         for b, c in enumerate(clips):
-            host[b, :lens[b]] = c
+            if not isinstance(c, str):
+                host[b, :lens[b]] = c
         x = torch.from_numpy(host).to(device)
+        if files:                                  # their bytes uploaded once, decoded and resampled into their rows of x
+            ingest_pcm(wav.stage([clips[b] for b in files], infos=infos), 32000, device, out=x.view(-1),
+                       offsets=[b * x.size(1) for b in files])
         lens_dev = torch.tensor(lens, dtype=torch.int32).to(device)
         with torch.no_grad():
             f, q, peak = clip_rescale_rows(x, lens_dev)
@@ -124,6 +134,9 @@ class FeatureWriter:
         2.2, nothing written), False for a non-finite peak or non-finite features (nothing written), True after writing
         4-cnhubert/<name>.pt and 5-wav32k/<name>.  The int16 file is byte for byte `ssl`'s; the features differ from
         `ssl`'s within fp32 rounding (the resampler accumulates in fp32, resample_half in float64).
+        An entry of clips32k may be the path of a WAV file (audiokit/wav.py: any served encoding, channel count and rate)
+        in place of the array: it is read only when its name is not skipped, and decoded and resampled to 32 kHz on the GPU
+        (hip/audio.py::ingest_pcm) -- the clip load_audio_batch([path], 32000) gives.
         tokens=True (needs `voice`, an object with SoVITSVoice.extract_latent_rows, and a hubert with
         last_hidden_state_batch; ValueError otherwise, before anything is uploaded): the features of the items that are
         written also go through voice.extract_latent_rows while they are on the device -- as the float32 values that are
@@ -142,7 +155,8 @@ class FeatureWriter:
         todo = [i for i, name in enumerate(names) if not os.path.exists(os.path.join(self.hubert_dir, name + ".pt"))]
         if not todo:
             return done
-        clips = [np.asarray(clips32k[i], dtype=np.float32).reshape(-1) for i in todo]
+        clips = [os.fspath(clips32k[i]) if isinstance(clips32k[i], (str, os.PathLike))
+                 else np.asarray(clips32k[i], dtype=np.float32).reshape(-1) for i in todo]
         peaks, wav16, rows16, lens16 = self._front_rows(clips)
         keep = []
         for j, i in enumerate(todo):

@@ -3,7 +3,10 @@ sample format and packed into one device buffer by ONE launch (csrc/resample_pol
 has the operator's definition).  The int16 conversion and the silence interval are the reference's audio_postprocess
 (inference/tts.py:878-908); the resampler is resampy's kaiser_best filter as feature_extractor/normalize.py restates it for
 the ratio 1/2, written for any ratio: at 1/2 its taps are normalize._half_band_taps() and the operator is resample_half.
-The filter's constants are taken from there."""
+The filter's constants are taken from there.
+
+The input end uses the same operator: `ingest_pcm` / `load_audio_batch` take the sample bytes of WAV files (audiokit/wav.py)
+to packed mono fp32 rows at the pipeline's rate in one launch per input rate (csrc/pcm_ingest.hip::evt_pcm_ingest_rows)."""
 import math
 from dataclasses import dataclass
 from typing import List
@@ -150,6 +153,84 @@ def resample_pack(x, lens, mul, in_rate, out_rate, out_format, order=None, inter
     if e0 is not None:
         T.t1_elt(e0, "resample_pack_kernel", x.numel() * x.element_size() + data.numel() * data.element_size(), owner)
     return PackedAudio(data, offsets, lengths, int(out_rate), gap)
+
+
+def upload_raw(batch, device):
+    """the staged bytes of an audiokit.wav.RawBatch on the device: one copy from page-locked memory, asynchronous on the
+    current stream"""
+    return batch.raw.to(torch.device(device), non_blocking=True)
+
+
+def ingest_pcm(batch, out_rate, device="cuda:0", raw_dev=None, out=None, offsets=None):
+    """batch: audiokit.wav.RawBatch (the sample bytes of WAV files of any served encoding, channel count and rate in one
+    page-locked buffer) -> PackedAudio at out_rate, float32, gap 0, rows in the batch's order: every recording decoded, mixed
+    down to mono and resampled on the GPU (csrc/pcm_ingest.hip::evt_pcm_ingest_rows; include/evt.h has the operator).  One
+    upload of the buffer, then one launch per distinct input rate.  rate_ratio's MAX_FACTOR rule holds for every input rate
+    of the batch: EvtError otherwise, before anything is uploaded.
+    raw_dev: the buffer on the device where the caller has uploaded it (upload_raw) -- a second call then ingests the same
+    upload at another rate.  out / offsets: a 1-D float32 device tensor and the element at which each row starts in it,
+    where the rows go next to other data (slice_batch); by default a buffer of their own, back to back.
+    An empty batch, or one whose rows all come out empty, touches no device: the PackedAudio then holds an empty CPU tensor
+    (or `out` as it is)."""
+    infos = list(batch.infos)
+    ratios = {rate: rate_ratio(rate, out_rate) for rate in batch.by_rate}
+    lengths = [out_len(i.frames, *ratios[i.rate]) for i in infos]
+    if offsets is None:
+        offsets, total = [], 0
+        for n in lengths:
+            offsets.append(total)
+            total += n
+    else:
+        offsets = [int(v) for v in offsets]
+        if out is None or len(offsets) != len(infos):
+            raise L.EvtError(f"ingest_pcm: offsets go with `out` and number {len(infos)}, one per recording")
+    if out is not None and (out.dtype != torch.float32 or out.dim() != 1 or not out.is_cuda or not out.is_contiguous()
+                            or any(o < 0 or o + n > out.numel() for o, n in zip(offsets, lengths))):
+        raise L.EvtError("ingest_pcm: `out` is a contiguous 1-D float32 device tensor that holds every row at its offset")
+    if not any(lengths):
+        return PackedAudio(torch.empty(0, dtype=torch.float32) if out is None else out, offsets, lengths, int(out_rate), 0)
+    device = torch.device(device) if out is None else out.device
+    with torch.cuda.device(device):
+        if raw_dev is None:
+            raw_dev = upload_raw(batch, device)
+        if raw_dev.dtype != torch.uint8 or raw_dev.dim() != 1 or raw_dev.numel() != batch.raw.numel() or not raw_dev.is_cuda:
+            raise L.EvtError(f"ingest_pcm: raw_dev must be the batch's {batch.raw.numel()} bytes as a uint8 tensor on the GPU")
+        if out is None:
+            out = torch.empty(sum(lengths), dtype=torch.float32, device=device)
+        order = [r for rows in batch.by_rate.values() for r in rows]             # group by group
+        wide = torch.tensor([[batch.byte_off[r] for r in order], [infos[r].frames for r in order],
+                             [offsets[r] for r in order]], dtype=torch.int64).to(device)
+        narrow = torch.tensor([[infos[r].fmt for r in order], [infos[r].channels for r in order]],
+                              dtype=torch.int32).to(device)
+        first = 0
+        for rate, rows in batch.by_rate.items():
+            k, (up, down) = len(rows), ratios[rate]
+            max_frames = max(infos[r].frames for r in rows)
+            if out_len(max_frames, up, down) > 0:
+                table, j_pad = (None, 0) if up == down == 1 else (phase_table(up, down, device), table_shape(up, down)[1])
+                cols = slice(first, first + k)
+                e0 = T.t0()
+                L.check(L.lib().evt_pcm_ingest_rows(L.ptr(raw_dev), raw_dev.numel(), L.ptr(wide[0, cols]), L.ptr(wide[1, cols]),
+                                                    L.ptr(narrow[0, cols]), L.ptr(narrow[1, cols]), k, max_frames, up, down,
+                                                    L.ptr(table), j_pad, L.ptr(out), out.numel(), L.ptr(wide[2, cols]),
+                                                    L.stream_ptr()), "evt_pcm_ingest_rows")
+                if e0 is not None:
+                    T.t1_elt(e0, "pcm_ingest_kernel", sum(infos[r].data_bytes + 4 * lengths[r] for r in rows), None)
+            first += k
+    return PackedAudio(out, offsets, lengths, int(out_rate), 0)
+
+
+def load_audio_batch(paths, out_rate=32000, device="cuda:0"):
+    """The batch form of the reference's load_audio(file, sr) (utils/audio/__init__.py:13-32) and of librosa.load(path,
+    sr=...): WAV files of any served encoding, channel count and rate (audiokit/wav.py) -> PackedAudio of mono float32 rows
+    at out_rate on the device -- probe, stage, ingest_pcm.
+    The boundary: the reference's load_audio runs ffmpeg, whose swr resampler is a different filter that cannot be pinned
+    offline; no sample parity with ffmpeg's output at a changed rate is claimed.  At an unchanged rate and PCM16 the samples
+    are the reference's (x / 32768, the mean of the channels).  Against librosa.load the filter is the same one (resampy's
+    kaiser_best, straight from the file's own rate) with fp32 accumulation in place of float64."""
+    from ..audiokit import wav
+
+    return ingest_pcm(wav.stage(paths), out_rate, device)
 
 
 REF_NFFT = 2048        # the transform of csrc/stft_mel.hip

@@ -417,6 +417,58 @@ int evt_resample_pack_rows(int32_t dtype, const void* x, const int32_t* lens, in
                            int32_t up, int32_t down, const float* table, int32_t J, int32_t out_format, void* out,
                            int64_t out_elems, const int64_t* out_off, int32_t gap, void* stream);
 
+/* The first launch of the audio pipeline: the sample bytes of nrec WAV recordings that share an input rate, decoded, mixed
+ * down to mono and resampled to the pipeline's rate (up / down = out_rate / in_rate, reduced) into one packed fp32 buffer
+ * -- the batch form of the reference's load_audio (utils/audio/__init__.py:13-32: ffmpeg, ac=1, ar=sr) and of the
+ * librosa.load(path, sr=16000) of _set_prompt_semantic (inference/tts.py:411-437), in one launch.  ffmpeg's swr resampler is
+ * another filter: at a changed rate the samples are this operator's, not ffmpeg's.
+ *
+ * raw: raw_len bytes on the device, the recordings' sample bytes (the body of a WAV file's data chunk: interleaved frames,
+ * little-endian).  Recording r has frames[r] frames of channels[r] samples in format fmt[r], its first byte at
+ * raw[byte_off[r]]; byte_off, frames (int64), fmt, channels (int32) and out_off (int64) are device tables of nrec entries.
+ * n_r = min(max(frames[r], 0), max_frames) frames are read; max_frames is the host's upper bound, it sizes the grid.
+ *
+ * The operator, per recording, with C = channels[r] and W the sample's bytes:
+ *   Decode.  Sample s of a frame -> fp32 v, every step exact or ONE round-to-nearest-even (rne_f32):
+ *     EVT_PCM_IN_U8  (W = 1, unsigned)                    v = (s - 128) * 2^-7
+ *     EVT_PCM_IN_S16 (W = 2, signed)                      v = s * 2^-15
+ *     EVT_PCM_IN_S24 (W = 3, signed, sign-extended)       v = s * 2^-23
+ *     EVT_PCM_IN_S32 (W = 4, signed)                      v = rne_f32(s) * 2^-31
+ *     EVT_PCM_IN_F32 (W = 4, IEEE binary32)               v = the value itself
+ *     EVT_PCM_IN_F64 (W = 8, IEEE binary64)               v = rne_f32(value)
+ *   NaN and infinities pass through, nothing is clamped.
+ *   Downmix.  m[i] = fdiv(((v_0 + v_1) + v_2) + ... + v_{C-1}, (float)C) over the C samples of frame i: the additions in
+ *   channel order, each rounded to fp32, the division correctly rounded -- numpy's x.reshape(-1, C).mean(axis=1,
+ *   dtype=float32) for C <= 8.  C = 1: m[i] = v_0, bits unchanged.  For a PCM16 file this is train/dataset.py::read_wav_pcm16
+ *   bit for bit.
+ *   Resample.  The operator of evt_resample_pack_rows above applied to x = m[0 .. n_r), nothing changed: the same table
+ *   [up][J], To_r = (n_r * up) / down outputs, the same four accumulators in the same order and (a0 + a1) + (a2 + a3);
+ *   up == down == 1 is the identity, table may be NULL then and J is ignored.  A recording therefore comes out bit for bit
+ *   as it does alone, and as evt_resample_pack_rows gives for the row m.
+ *   Output.  To_r fp32 values at out[out_off[r] ..]; an element that would fall outside [0, out_elems) is not stored.  With
+ *   out_off the prefix sum of To_r every element of `out` is written.
+ *
+ * No byte outside [byte_off[r], byte_off[r] + n_r * C * W) is read for recording r: a sample is read with a load of its own
+ * size, or byte by byte, never with a wider one.  A recording whose bytes do not lie inside [0, raw_len), whose fmt is not
+ * one of the six codes or whose channels lie outside 1 .. EVT_PCM_IN_MAX_CHANNELS is skipped on the device: its outputs are
+ * not written.  byte_off needs no alignment (an aligned recording is read with fewer loads).  A block takes
+ * EVT_RESAMPLE_TILE consecutive outputs of one recording, counted from its output 0; format and channel count are
+ * block-uniform.  No host synchronisation and no 16-bit type: the same code in both builds.
+ * EVT_EINVAL (nothing launched) for a NULL pointer, raw_len, nrec, max_frames or out_elems <= 0, nrec > 65535, max_frames
+ * >= 2^31, up or down <= 0, a J outside the range of evt_resample_pack_rows, a table not 16-byte aligned or a table or
+ * `out` not aligned to its element.  EVT_OK without a launch when (max_frames * up) / down == 0: no recording has an output. */
+#define EVT_PCM_IN_U8 0
+#define EVT_PCM_IN_S16 1
+#define EVT_PCM_IN_S24 2
+#define EVT_PCM_IN_S32 3
+#define EVT_PCM_IN_F32 4
+#define EVT_PCM_IN_F64 5
+#define EVT_PCM_IN_MAX_CHANNELS 8
+int evt_pcm_ingest_rows(const uint8_t* raw, int64_t raw_len, const int64_t* byte_off, const int64_t* frames,
+                        const int32_t* fmt, const int32_t* channels, int32_t nrec, int64_t max_frames, int32_t up,
+                        int32_t down, const float* table, int32_t J, float* out, int64_t out_elems, const int64_t* out_off,
+                        void* stream);
+
 /* out = leaky_relu(x, slope).  The HiFi-GAN residual unit (modules.py:299-308) keeps an activated copy of its input
  * so that its convolutions and weight gradients take plain operands (LDS-DMA kernels).  16-byte aligned. */
 int evt_leaky_relu(int32_t dtype, const void* x, float slope, void* out, int64_t n, void* stream);
