@@ -406,8 +406,8 @@ def _s2_worker(exp_dir, data_cfg, symbol_to_id, spec_bins, pad_frames, hop, slab
 
 class _ProcPrefetch:
     """read + collate on worker PROCESSES (one GIL each), batches delivered in sampler order; at most `depth` batches are
-    in flight, each in its own shared-memory slot (page-locked in the parent when the consumer is a GPU: the copy to the
-    device is then asynchronous straight from the slot).  The workers are started once per reader and stay
+    in flight, each in its own shared-memory slot (when the consumer is a GPU the parent moves it into the slot's page-locked
+    twin: the copy to the device is then asynchronous).The workers are started once per reader and stay
     (persistent_workers=True there)."""
 
     def __init__(self, reader, workers, depth):
@@ -421,15 +421,12 @@ class _ProcPrefetch:
         text_max = max((len(ids) for _name, ids in ds.items), default=1)
         slot_bytes = bsz * (768 * frames * 4 + (frames + 4) * ds.hop_length * 4 + text_max * 8) + 4096
         self.slabs = [torch.zeros(slot_bytes, dtype=torch.uint8).share_memory_() for _ in range(self.depth)]
-        self.pinned = False
+        # a GPU consumer gets each slot's batch through a page-locked twin of the slot, allocated page-locked once (memory
+        # that exists already -- the shared slots -- cannot be page-locked everywhere): one host copy of the bytes in use,
+        # then non_blocking copies from the twin's views are truly asynchronous
+        self.stage = None
         if reader.device.type == "cuda":
-            try:       # page-lock the slots once: non_blocking copies from their views are then truly asynchronous
-                rt = torch.cuda.cudart()
-                for sl in self.slabs:
-                    rt.cudaHostRegister(sl.data_ptr(), sl.numel(), 0)
-                self.pinned = True
-            except Exception:  # noqa: BLE001 -- unpinned slots still work (the copy is then staged by the runtime)
-                self.pinned = False
+            self.stage = [torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
         ctx = mp.get_context("spawn")          # the parent has a HIP context: never fork it
         self.task_q, self.out_q = ctx.Queue(), ctx.Queue()
         args = (reader._exp_dir, reader._data_cfg, reader._symbol_to_id, reader.spec_bins, reader.pad_frames, ds.hop_length,
@@ -469,7 +466,13 @@ class _ProcPrefetch:
                     held[msg[0]] = msg
                 _seq, slot, metas, ssl_l, spec_shape, spec_l, wav_l, text_l, ok, _err = held.pop(got)
                 got += 1
-                ssl_p, wav_p, text_p = _slot_views(self.slabs[slot], metas)
+                slab = self.slabs[slot]
+                if self.stage is not None:
+                    used = max(off + math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+                               for off, shape, dtype in metas)
+                    slab = self.stage[slot]
+                    slab[:used].copy_(self.slabs[slot][:used])
+                ssl_p, wav_p, text_p = _slot_views(slab, metas)
                 lt = lambda v: torch.tensor(v, dtype=torch.long)
                 yield (ssl_p, lt(ssl_l), spec_shape, lt(spec_l), wav_p, lt(wav_l), text_p, lt(text_l)), ok, slot
                 if isinstance(release, _AutoRelease):
@@ -496,14 +499,6 @@ class _ProcPrefetch:
             if p.is_alive():
                 p.terminate()          # by handle: our own children only
         self.procs = []
-        if self.pinned:
-            try:
-                rt = torch.cuda.cudart()
-                for sl in self.slabs:
-                    rt.cudaHostUnregister(sl.data_ptr())
-            except Exception:  # noqa: BLE001
-                pass
-            self.pinned = False
 
 
 class _AutoRelease(list):
