@@ -999,18 +999,9 @@ int launch_igemm_mt(const ConvP& p, int MT, int NT, int nphase, bool split, hipS
   }
 }
 
-// Generic igemm launch.  A = output channels, B = K-side channels.
-int launch_igemm(int dtype, ConvP p, int A, int B, int nphase, hipStream_t st, bool allow_deep) {
+// Generic igemm launch: the choice of the tile.  A = output channels, B = K-side channels.
+int launch_igemm(int dtype, ConvP p, int A, int B, int nphase, hipStream_t st) {
   if (A % 16 || B % 16) return EVT_ENOTSUP;
-  // specialised paths first; EVT_ENOTSUP from one of them means "not this shape after all": fall through to the generic kernel
-  if (allow_deep && evt_conv::deep_eligible(p, dtype, A, B, nphase)) {
-    const int rc = evt_conv::launch_conv_deep(p, A, B, nphase, st);
-    if (rc != EVT_ENOTSUP) return rc;
-  }
-  if (allow_deep && evt_conv::narrow_eligible(p, dtype, A, B, nphase)) {
-    const int rc = evt_conv::launch_conv_narrow(p, A, B, nphase, st);
-    if (rc != EVT_ENOTSUP) return rc;
-  }
   const int CK = (B % 32 == 0) ? 32 : 16;
   const int MT = (A % 64 == 0) ? 4 : (A % 32 == 0 ? 2 : 1);
   p.Y = A / (16 * MT);
@@ -1160,10 +1151,7 @@ NvP make_nvp(const evt_conv1d_params* c) {
 }
 
 bool igemm_ok(const evt_conv1d_params* c) {
-  if (c->groups != 1) return false;
-  if (c->cin % 16 || c->cout % 16) return false;
-  if (c->stride > 1 && c->dil != 1) return false;
-  return true;
+  return c->groups == 1 && c->cin % 16 == 0 && c->cout % 16 == 0 && (c->stride == 1 || c->dil == 1);
 }
 
 int valid(const evt_conv1d_params* c) {
@@ -1175,6 +1163,171 @@ int valid(const evt_conv1d_params* c) {
   if (c->transposed && (c->groups != 1 || c->dil != 1)) return EVT_ENOTSUP;
   if (evt_conv1d_lout(c) <= 0) return EVT_EINVAL;
   return EVT_OK;
+}
+
+// ---- routes ---------------------------------------------------------------------------------------------------------------
+// Where a pass goes: ONE function per pass says which kernel family takes these parameters, which prepared image it reads
+// and, for the MFMA families, the geometry of their descriptor.  They are host arithmetic over evt_conv1d_params plus one
+// fact per pass that the parameters do not hold (forward: a residual is added; backward-data: dx_add is given); the gate
+// and the saved activation of the backward passes ARE parameters (in_slope != 1, out_act != NONE: the entry points demand
+// x / y then).  The entry points, evt_conv1d_wants_plain_x / _dy and evt_conv1d_route all ask these functions; a ConvP or
+// a WgP geometry is written nowhere else.
+struct ConvRoute {
+  int family;                    // EVT_CONV_*
+  int image;                     // EVT_IMG_*: the prepared image the family reads
+  int out_ch, k_ch, ck;          // DEEP / NARROW / IGEMM: output and K-side channels, channels per chunk,
+  int nphase = 1;                // ... polyphase launches in one grid
+  ConvP p;                       // ... and their descriptor without its pointers (P, Y, U are the launchers')
+};
+
+// The families in front of the implicit GEMM, in their order of precedence: rows16, grouped, cout1 / cin1, naive; a call
+// none of them takes leaves as EVT_CONV_IGEMM.  n_out / k_red: channels of the result and of the reduction; extra: the
+// call's residual / dx_add, which rows16 (like a slope on load or an output activation) does not take.
+int route_front(const evt_conv1d_params* c, int n_out, int k_red, bool extra, bool grouped_ok, bool small_ok, ConvRoute& r) {
+  r = ConvRoute{};
+  const bool fast = c->impl != EVT_IMPL_NAIVE, use_igemm = fast && igemm_ok(c);
+  if (c->impl == EVT_IMPL_IGEMM && !use_igemm) return EVT_ENOTSUP;
+  const int small = (fast && small_ok) ? evt_small_kind(c) : 0;
+  // a handful of rows (a 1x1 layer applied to one vector per item): weight rows on the MFMA's M side (rows_gemm.hip)
+  if (evt_conv::rows16_eligible(c, c->nseq * c->lin, n_out, k_red, extra || c->in_slope != 1.f || c->out_act != EVT_ACT_NONE))
+    r.family = EVT_CONV_ROWS16;
+  else if (fast && grouped_ok && evt_grouped_supported(c)) r.family = EVT_CONV_GROUPED;
+  else if (small != 0) r.family = small == 1 ? EVT_CONV_COUT1 : EVT_CONV_CIN1;
+  else r.family = use_igemm ? EVT_CONV_IGEMM : EVT_CONV_NAIVE;
+  return EVT_OK;
+}
+
+// The index maps of an implicit-GEMM product whose operands are named (r.out_ch, p.Lout, the slopes), and the family that
+// takes it.  direct: the REG image, rows = output channels (Conv1d forward, ConvTranspose1d backward-data); else the
+// transposed product on the ALT image (ConvTranspose1d forward, Conv1d backward-data), polyphase when strided: one phase
+// per residue of the output position, J taps each.  plain: no saved activation multiplies the K-side operand (ConvP::xact,
+// which deep_eligible / narrow_eligible refuse: the route has no pointer to show them, so it is said here).
+void route_igemm(const evt_conv1d_params* c, bool direct, bool plain, ConvRoute& r) {
+  evt_wlayout l; evt_conv1d_layout(c, &l);
+  ConvP& p = r.p;
+  p.nseq = c->nseq; p.s_out = 1; p.Q = p.Lout;                  // (offsets and the phase stride start at 0)
+  if (direct) {
+    r.image = EVT_IMG_REG; r.ck = l.reg_ck; p.KHp = l.reg_kp; p.nchunk = l.reg_nchunk;
+    p.s_in = c->stride; p.dil = c->dil; p.off_in = -c->pad;
+  } else {
+    r.image = EVT_IMG_ALT; r.ck = l.alt_ck; p.KHp = l.alt_kp; p.nchunk = l.alt_nchunk;
+    p.s_in = 1; p.dil = c->dil; p.off_in = c->pad - (c->k - 1) * c->dil;
+    if (c->stride > 1) {                                         // (igemm_ok: dil == 1 here)
+      r.nphase = c->stride;
+      p.off_in = -((c->k + c->stride - 1) / c->stride - 1);
+      p.s_out = c->stride; p.off_out = -c->pad; p.off_out_phase = 1;
+      p.Q = (p.Lout - 1 + c->pad) / c->stride + 1;
+      p.w_phase_stride = (long)r.out_ch * l.alt_nchunk * l.alt_kp * l.alt_ck;
+    }
+  }
+  if (c->impl != EVT_IMPL_AUTO || !plain) return;
+  if (evt_conv::deep_eligible(p, c->dtype, r.out_ch, r.k_ch, r.nphase)) r.family = EVT_CONV_DEEP;
+  else if (evt_conv::narrow_eligible(p, c->dtype, r.out_ch, r.k_ch, r.nphase)) r.family = EVT_CONV_NARROW;
+}
+
+// Forward: the grouped and small kernels add no residual.
+int fwd_route(const evt_conv1d_params* c, bool has_res, ConvRoute* out) {
+  ConvRoute& r = *out;
+  const int rc = route_front(c, c->cout, c->cin, has_res, !has_res, !has_res, r);
+  if (rc || r.family != EVT_CONV_IGEMM) return rc;
+  ConvP& p = r.p;
+  r.out_ch = c->cout; r.k_ch = c->cin;
+  p.Lin = c->lin; p.Lout = evt_conv1d_lout(c); p.Cin = c->cin; p.Cout = c->cout;
+  p.in_slope = c->in_slope; p.xact_slope = 1.f; p.out_act = c->out_act; p.out_slope = c->out_slope; p.gate_slope = 1.f;
+  route_igemm(c, !c->transposed, true, r);
+  return EVT_OK;
+}
+
+// Backward-data: the same product with dy on the K side and, for ConvTranspose1d, dx[i][ci] = sum_t sum_co
+// dy[i*s + t - pad][co] W[ci][co][t] on the REG image.  The grouped kernel has no gate; small_ok: the cout1 / cin1
+// launchers may decline, the caller then routes again without them.
+int bwd_data_route(const evt_conv1d_params* c, bool has_add, bool small_ok, ConvRoute* out) {
+  ConvRoute& r = *out;
+  const int rc = route_front(c, c->cin, c->cout, has_add, c->in_slope == 1.f, small_ok, r);
+  if (r.family == EVT_CONV_ROWS16) r.image = EVT_IMG_ALT;
+  if (rc || r.family != EVT_CONV_IGEMM) return rc;
+  ConvP& p = r.p;
+  r.out_ch = c->cin; r.k_ch = c->cout;
+  p.Lin = evt_conv1d_lout(c); p.Lout = c->lin; p.Cin = c->cout; p.Cout = c->cin;
+  p.in_slope = 1.f; p.xact_kind = c->out_act; p.xact_slope = c->out_slope; p.out_slope = 1.f; p.gate_slope = c->in_slope;
+  route_igemm(c, c->transposed != 0, c->out_act == EVT_ACT_NONE, r);
+  return EVT_OK;
+}
+
+// DEEP / NARROW / IGEMM with the pointers filled in.  launch_conv_deep and launch_conv_narrow return EVT_ENOTSUP exactly
+// when deep_eligible / narrow_eligible refuse the descriptor (deep_kind == 0; narrow's register bound in launch_inst is
+// the last line of narrow_eligible again), which the route has just asked: no second try on the generic tile behind them.
+int launch_conv(int dtype, const ConvRoute& r, hipStream_t st) {
+  if (r.family == EVT_CONV_DEEP) return evt_conv::launch_conv_deep(r.p, r.out_ch, r.k_ch, r.nphase, st);
+  if (r.family == EVT_CONV_NARROW) return evt_conv::launch_conv_narrow(r.p, r.out_ch, r.k_ch, r.nphase, st);
+  return launch_igemm(dtype, r.p, r.out_ch, r.k_ch, r.nphase, st);
+}
+
+int naive_blocks(long total) { return (int)((total + 255) / 256 > 65535 * 8 ? 65535 * 8 : (total + 255) / 256); }
+
+// Weight gradient: the family and the descriptor geometry of the MFMA kernels (A = the q-indexed operand, B = the
+// tap-shifted one).  ONE function for the single entry point and for the grouped one: a member of a group is routed as it
+// would be alone.
+struct WgRoute {
+  int family;        // EVT_WG_*
+  int rc;            // EVT_ENOTSUP: EVT_IMPL_IGEMM asked for a shape that is left to the direct-form kernel
+  bool fuses_bias;   // the family adds dbias itself when one is asked for; else the column-sum kernel runs before it
+  int lout;
+  WgP p;             // GEMM .. TILE: everything but the pointers and the slab record (wg_operands)
+};
+
+WgRoute wg_route(const evt_conv1d_params* c) {
+  WgRoute r{};
+  const int lout = r.lout = evt_conv1d_lout(c);
+  evt_wlayout l; evt_conv1d_layout(c, &l);
+  WgP& p = r.p;
+  p.nseq = c->nseq; p.KH = c->k; p.KHp = l.reg_kp; p.s = c->stride; p.dil = c->dil; p.off = -c->pad;
+  p.a_slope = p.b_slope = p.aact_slope = p.bact_slope = 1.f;
+  if (!c->transposed) {
+    // dW[co][.][t][ci] += dy_eff[q][co] * lrelu(x)[q*s + t*dil - pad][ci]
+    p.aact_kind = c->out_act; p.aact_slope = c->out_slope; p.b_slope = c->in_slope;
+    p.LA = lout; p.CA = c->cout; p.LB = c->lin; p.CB = c->cin; p.Q = lout;
+  } else {
+    // dW[ci][.][t][co] += lrelu(x)[i][ci] * dy_eff[i*s + t - pad][co]
+    p.a_slope = c->in_slope; p.bact_kind = c->out_act; p.bact_slope = c->out_slope;
+    p.LA = c->lin; p.CA = c->cin; p.LB = lout; p.CB = c->cout; p.Q = c->lin;
+  }
+  const bool fast = c->impl != EVT_IMPL_NAIVE;
+  const bool mfma = fast && igemm_ok(c) && l.reg_kp <= 64;
+  // the LDS-DMA kernels take plain operands: no saved activation (WgP::Aact / Bact, pointers the route does not have and
+  // their *_eligible tests refuse) -- said here; the load-side slopes they read from the descriptor themselves
+  const bool dma = mfma && c->impl == EVT_IMPL_AUTO && c->out_act == EVT_ACT_NONE;
+  if (fast && evt_grouped_supported(c)) r.family = EVT_WG_GROUPED;
+  else if (fast && evt_small_kind(c) == 1) r.family = EVT_WG_COUT1;             // the dot-product conv
+  else if (fast && evt_small_kind(c) == 2) r.family = EVT_WG_CIN1;
+  else if (!mfma) r.family = EVT_WG_NAIVE;
+  // dense layers (k = 1, long reductions): the 128 x 128 weight-gradient GEMM tile
+  else if (dma && !c->transposed && evt_conv::wgrad_gemm_eligible(p, c->dtype)) r.family = EVT_WG_GEMM;
+  // stride-1 layers with 3..11 taps and long sequences: one staged window of x serves all taps (wgrad_halo.hip)
+  else if (dma && evt_conv::wgrad_halo_eligible(p, c->dtype)) r.family = EVT_WG_HALO;
+  // wide layers: LDS-DMA GEMM kernel (conv_deep.hip)
+  else if (dma && evt_conv::wgrad_deep_eligible(p, c->dtype)) r.family = EVT_WG_DEEP;
+  // latency-bound mid-size layers: ring-pipelined LDS-DMA kernel
+  else if (dma && evt_conv::wgrad_ring_eligible(p, c->dtype)) r.family = EVT_WG_RING;
+  else r.family = EVT_WG_TILE;                                                  // conv_wgrad_tr, else conv_wgrad
+  // the 16-bit MFMA kernels fuse dbias when their A operand is dy (plain Conv1d); the two small families always do
+  r.fuses_bias = r.family == EVT_WG_COUT1 || r.family == EVT_WG_CIN1 ||
+                 (r.family >= EVT_WG_GEMM && c->dtype == EVT_DT_HALF && !c->transposed);
+  r.rc = (r.family == EVT_WG_NAIVE && c->impl == EVT_IMPL_IGEMM) ? EVT_ENOTSUP : EVT_OK;
+  return r;
+}
+
+// the pointers of a routed weight gradient and the caller's slab record
+void wg_operands(WgP& p, const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
+                 const evt_wgrad_parts* sp, int* used_host) {
+  const void* ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
+  p.dw = dw;
+  if (!c->transposed) { p.A = dy; p.Aact = ysv; p.B = x; }
+  else { p.A = x; p.B = dy; p.Bact = ysv; }
+  if (sp) {
+    p.dw_extra = sp->dw_extra; p.part_stride = sp->part_stride; p.parts = sp->parts; p.prev_used = sp->prev_used;
+    p.db_part = sp->db_part; p.used = sp->used_dev; p.used_host = used_host; p.dirty0 = sp->dirty0 || sp->prev_used > 0;
+  }
 }
 
 }  // namespace
@@ -1190,47 +1343,24 @@ int32_t evt_conv1d_wants_plain_dy(const evt_conv1d_params* c) {
   if (!c || valid(c) != EVT_OK) return 0;
   if (c->impl != EVT_IMPL_AUTO || c->dtype != EVT_DT_HALF || c->transposed || !igemm_ok(c)) return 0;
   if (c->out_act == EVT_ACT_NONE || c->in_slope != 1.f) return 0;
-  // same descriptor geometry evt_conv1d_bwd_data builds (K side = cout, output channels = cin)
-  ConvP p{};
-  p.in_slope = 1.f;
-  p.nseq = c->nseq;
-  p.nchunk = c->cout / 32;
-  int nphase = 1;
-  if (c->stride == 1) p.Q = c->lin;
-  else { nphase = c->stride; p.Q = (c->lin - 1 + c->pad) / c->stride + 1; }
-  if (evt_conv::deep_eligible(p, c->dtype, c->cin, c->cout, nphase)) return 1;
-  {  // the stride-1 narrow kernel takes plain operands too
-    evt_wlayout l; evt_conv1d_layout(c, &l);
-    ConvP q = p;
-    q.s_in = q.s_out = 1; q.off_out = 0; q.KHp = l.alt_kp; q.nchunk = l.alt_nchunk;
-    if (c->stride == 1 && evt_conv::narrow_eligible(q, c->dtype, c->cin, c->cout, 1)) return 1;
-  }
-  // ... or the weight gradient does (A = dy [nseq][lout][cout], B = x)
-  WgP w{};
-  w.nseq = c->nseq; w.KH = w.KHp = c->k; w.Q = w.LA = evt_conv1d_lout(c); w.CA = c->cout; w.CB = c->cin;
-  w.s = c->stride; w.dil = c->dil; w.LB = c->lin;
-  w.a_slope = w.b_slope = 1.f;
-  return (evt_conv::wgrad_deep_eligible(w, c->dtype) || evt_conv::wgrad_halo_eligible(w, c->dtype)) ? 1 : 0;
+  evt_conv1d_params q = *c;             // the backward calls the caller would then make: dy * act' as a plain operand
+  q.out_act = EVT_ACT_NONE;
+  ConvRoute r;                          // (asked with dx_add, as below with a residual)
+  if (bwd_data_route(&q, true, true, &r) == EVT_OK && (r.family == EVT_CONV_DEEP || r.family == EVT_CONV_NARROW)) return 1;
+  const int wf = wg_route(&q).family;   // ... or the weight gradient takes it
+  return (wf == EVT_WG_DEEP || wf == EVT_WG_HALO) ? 1 : 0;
 }
 
 int32_t evt_conv1d_wants_plain_x(const evt_conv1d_params* c) {
   if (!c || valid(c) != EVT_OK) return 0;
   if (c->impl != EVT_IMPL_AUTO || c->dtype != EVT_DT_HALF || c->in_slope == 1.f || !igemm_ok(c)) return 0;
   if (evt_grouped_supported(c) || evt_small_kind(c) != 0) return 0;
-  // same descriptor geometry evt_conv1d_fwd builds, with the load-side activation taken out
-  evt_wlayout l; evt_conv1d_layout(c, &l);
-  const int lout = evt_conv1d_lout(c);
-  ConvP p{};
-  p.in_slope = 1.f;
-  p.nseq = c->nseq;
-  int nphase = 1;
-  if (!c->transposed) { p.nchunk = l.reg_nchunk; p.KHp = l.reg_kp; p.Q = lout; }
-  else {
-    p.nchunk = l.alt_nchunk; p.KHp = l.alt_kp;
-    if (c->stride == 1) p.Q = lout;
-    else { nphase = c->stride; p.Q = (lout - 1 + c->pad) / c->stride + 1; }
-  }
-  return evt_conv::deep_eligible(p, c->dtype, c->cout, c->cin, nphase) ? 1 : 0;
+  evt_conv1d_params q = *c;             // the forward call the caller would then make: the activated input, no slope on load
+  q.in_slope = 1.f;
+  // Asked with a residual: the predicate is not told whether the call adds one and must hold if it does.  Without one, a
+  // k = 1 layer on at most 16 rows then goes to rows16 instead (512 -> 6144 on 5 rows), plain operands all the same.
+  ConvRoute r;
+  return (fwd_route(&q, true, &r) == EVT_OK && r.family == EVT_CONV_DEEP) ? 1 : 0;
 }
 
 int evt_conv1d_layout(const evt_conv1d_params* c, evt_wlayout* o) {
@@ -1258,64 +1388,27 @@ int evt_conv1d_fwd(const evt_conv1d_params* c, const void* x, const void* w_reg,
   if (rc) return rc;
   if (!x || !y) return EVT_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const bool use_igemm = c->impl != EVT_IMPL_NAIVE && igemm_ok(c);
-  if (c->impl == EVT_IMPL_IGEMM && !use_igemm) return EVT_ENOTSUP;
-  const int lout = evt_conv1d_lout(c);
-  evt_wlayout l; evt_conv1d_layout(c, &l);
-  // a handful of rows (a 1x1 layer applied to one vector per item): weight rows on the MFMA's M side (rows_gemm.hip)
-  if (w_reg && evt_conv::rows16_eligible(c, c->nseq * c->lin, c->cout, c->cin,
-                                         res || c->in_slope != 1.f || c->out_act != EVT_ACT_NONE))
-    return evt_conv::launch_rows16(x, w_reg, bias, y, c->nseq * c->lin, c->cout, c->cin, st);
-  evt_set_last_tag("conv_naive_fwd");
-  if (c->impl != EVT_IMPL_NAIVE && !res && evt_grouped_supported(c)) {
-    if (!w_reg) return EVT_EINVAL;
-    evt_set_last_tag("grouped_fwd");
-    return evt_grouped_fwd(c, x, w_reg, bias, y, stream);
-  }
-  if (c->impl != EVT_IMPL_NAIVE && !res && evt_small_kind(c) == 1) {
-    if (!w_reg) return EVT_EINVAL;
-    return evt_cout1_fwd(c, x, w_reg, bias, y, stream);
-  }
-  if (c->impl != EVT_IMPL_NAIVE && !res && evt_small_kind(c) == 2) {
-    if (!w_reg) return EVT_EINVAL;
-    return evt_cin1_fwd(c, x, w_reg, bias, y, stream);
-  }
-  if (!use_igemm) {
-    if (!w_reg) return EVT_EINVAL;
-    NvP p = make_nvp(c);
-    p.x = x; p.w = w_reg; p.bias = bias; p.res = res; p.y = y;
-    const long total = (long)c->nseq * lout * c->cout;
-    const int blocks = (int)((total + 255) / 256 > 65535 * 8 ? 65535 * 8 : (total + 255) / 256);
-    if (c->dtype == EVT_DT_HALF) hipLaunchKernelGGL(conv_naive_fwd<h16_t>, dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(conv_naive_fwd<float>, dim3(blocks), dim3(256), 0, st, p);
-    return evt_check_launch();
-  }
-  const void* w = c->transposed ? w_alt : w_reg;
+  ConvRoute r;
+  rc = fwd_route(c, res != nullptr, &r);
+  if (rc) return rc;
+  const void* w = r.image == EVT_IMG_ALT ? w_alt : w_reg;
   if (!w) return EVT_EINVAL;
-  ConvP p{};
-  p.x = x; p.xact = nullptr; p.w = w; p.bias = bias; p.res = res; p.gate = nullptr; p.y = y;
-  p.nseq = c->nseq; p.Lin = c->lin; p.Lout = lout; p.Cin = c->cin; p.Cout = c->cout;
-  p.in_slope = c->in_slope; p.xact_kind = 0; p.xact_slope = 1.f; p.out_act = c->out_act; p.out_slope = c->out_slope;
-  p.gate_slope = 1.f;
-  int nphase = 1;
-  if (!c->transposed) {
-    p.KHp = l.reg_kp; p.nchunk = l.reg_nchunk;
-    p.s_in = c->stride; p.dil = c->dil; p.off_in = -c->pad;
-    p.s_out = 1; p.off_out = 0; p.off_out_phase = 0; p.Q = lout; p.w_phase_stride = 0;
-  } else {
-    p.KHp = l.alt_kp; p.nchunk = l.alt_nchunk; p.dil = 1; p.s_in = 1;
-    if (c->stride == 1) {
-      p.off_in = c->pad - (c->k - 1); p.s_out = 1; p.off_out = 0; p.off_out_phase = 0; p.Q = lout;
-      p.w_phase_stride = 0;
-    } else {
-      const int J = (c->k + c->stride - 1) / c->stride;
-      nphase = c->stride;
-      p.off_in = -(J - 1); p.s_out = c->stride; p.off_out = -c->pad; p.off_out_phase = 1;
-      p.Q = (lout - 1 + c->pad) / c->stride + 1;
-      p.w_phase_stride = (long)c->cout * l.alt_nchunk * l.alt_kp * l.alt_ck;
+  switch (r.family) {
+    case EVT_CONV_ROWS16: return evt_conv::launch_rows16(x, w, bias, y, c->nseq * c->lin, c->cout, c->cin, st);
+    case EVT_CONV_GROUPED: evt_set_last_tag("grouped_fwd"); return evt_grouped_fwd(c, x, w, bias, y, stream);
+    case EVT_CONV_COUT1: return evt_cout1_fwd(c, x, w, bias, y, stream);
+    case EVT_CONV_CIN1: return evt_cin1_fwd(c, x, w, bias, y, stream);
+    case EVT_CONV_NAIVE: {
+      NvP p = make_nvp(c);
+      p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
+      evt_set_last_tag("conv_naive_fwd");
+      hipLaunchKernelGGL((c->dtype == EVT_DT_HALF ? conv_naive_fwd<h16_t> : conv_naive_fwd<float>),
+                         dim3(naive_blocks((long)c->nseq * p.lout * c->cout)), dim3(256), 0, st, p);
+      return evt_check_launch();
     }
   }
-  return launch_igemm(c->dtype, p, c->cout, c->cin, nphase, st, c->impl == EVT_IMPL_AUTO);
+  r.p.x = x; r.p.w = w; r.p.bias = bias; r.p.res = res; r.p.y = y;
+  return launch_conv(c->dtype, r, st);
 }
 
 int evt_conv1d_bwd_data(const evt_conv1d_params* c, const void* dy, const void* y, const void* w_reg,
@@ -1326,64 +1419,56 @@ int evt_conv1d_bwd_data(const evt_conv1d_params* c, const void* dy, const void* 
   if (c->out_act != EVT_ACT_NONE && !y) return EVT_EINVAL;
   if (c->in_slope != 1.f && !x) return EVT_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const bool use_igemm = c->impl != EVT_IMPL_NAIVE && igemm_ok(c);
-  if (c->impl == EVT_IMPL_IGEMM && !use_igemm) return EVT_ENOTSUP;
-  const int lout = evt_conv1d_lout(c);
-  evt_wlayout l; evt_conv1d_layout(c, &l);
   const void* ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
   const void* gate = c->in_slope != 1.f ? x : nullptr;
-  if (w_alt && evt_conv::rows16_eligible(c, c->nseq * c->lin, c->cin, c->cout, ysv || gate || dx_add))
-    return evt_conv::launch_rows16(dy, w_alt, nullptr, dx, c->nseq * c->lin, c->cin, c->cout, st);
-  evt_set_last_tag("conv_naive_bwd_data");
-  if (c->impl != EVT_IMPL_NAIVE && !gate && evt_grouped_supported(c)) {
+  ConvRoute r;
+  rc = bwd_data_route(c, dx_add != nullptr, true, &r);
+  if (rc) return rc;
+  if (r.family == EVT_CONV_COUT1 || r.family == EVT_CONV_CIN1) {
     if (!w_reg) return EVT_EINVAL;
-    evt_set_last_tag("grouped_bwd_data");
-    return evt_grouped_bwd_data_add(c, dy, y, w_reg, dx_add, dx, stream);
-  }
-  if (c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) != 0) {
-    if (!w_reg) return EVT_EINVAL;
-    rc = evt_small_kind(c) == 1 ? evt_cout1_bwd_data(c, dy, y, w_reg, gate, dx_add, dx, stream)
-                                : evt_cin1_bwd_data(c, dy, y, w_reg, gate, dx_add, dx, stream);
+    rc = r.family == EVT_CONV_COUT1 ? evt_cout1_bwd_data(c, dy, y, w_reg, gate, dx_add, dx, stream)
+                                    : evt_cin1_bwd_data(c, dy, y, w_reg, gate, dx_add, dx, stream);
     if (rc != EVT_ENOTSUP) return rc;
+    // the small launcher declined (its LDS bound): the route behind it, which refuses nothing the first one took
+    bwd_data_route(c, dx_add != nullptr, false, &r);
   }
-  if (!use_igemm) {
-    if (!w_reg) return EVT_EINVAL;
-    NvP p = make_nvp(c);
-    p.x = dy; p.y_in = ysv; p.w = w_reg; p.gate = gate; p.res = dx_add; p.y = dx;
-    const long total = (long)c->nseq * c->lin * c->cin;
-    const int blocks = (int)((total + 255) / 256 > 65535 * 8 ? 65535 * 8 : (total + 255) / 256);
-    if (c->dtype == EVT_DT_HALF) hipLaunchKernelGGL(conv_naive_bwd_data<h16_t>, dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(conv_naive_bwd_data<float>, dim3(blocks), dim3(256), 0, st, p);
-    return evt_check_launch();
-  }
-  const void* w = c->transposed ? w_reg : w_alt;
+  const void* w = r.image == EVT_IMG_ALT ? w_alt : w_reg;
   if (!w) return EVT_EINVAL;
-  ConvP p{};
-  p.x = dy; p.xact = ysv; p.w = w; p.bias = nullptr; p.res = dx_add; p.gate = gate; p.y = dx;
-  p.nseq = c->nseq; p.Lin = lout; p.Lout = c->lin; p.Cin = c->cout; p.Cout = c->cin;
-  p.in_slope = 1.f; p.xact_kind = c->out_act; p.xact_slope = c->out_slope; p.out_act = EVT_ACT_NONE;
-  p.out_slope = 1.f; p.gate_slope = c->in_slope;
-  int nphase = 1;
-  if (!c->transposed) {
-    p.KHp = l.alt_kp; p.nchunk = l.alt_nchunk;
-    if (c->stride == 1) {
-      p.s_in = 1; p.dil = c->dil; p.off_in = c->pad - (c->k - 1) * c->dil;
-      p.s_out = 1; p.off_out = 0; p.off_out_phase = 0; p.Q = c->lin; p.w_phase_stride = 0;
-    } else {
-      const int J = (c->k + c->stride - 1) / c->stride;
-      nphase = c->stride;
-      p.s_in = 1; p.dil = 1; p.off_in = -(J - 1);
-      p.s_out = c->stride; p.off_out = -c->pad; p.off_out_phase = 1;
-      p.Q = (c->lin - 1 + c->pad) / c->stride + 1;
-      p.w_phase_stride = (long)c->cin * l.alt_nchunk * l.alt_kp * l.alt_ck;
+  switch (r.family) {
+    case EVT_CONV_ROWS16: return evt_conv::launch_rows16(dy, w, nullptr, dx, c->nseq * c->lin, c->cin, c->cout, st);
+    case EVT_CONV_GROUPED: evt_set_last_tag("grouped_bwd_data"); return evt_grouped_bwd_data_add(c, dy, y, w, dx_add, dx, stream);
+    case EVT_CONV_NAIVE: {
+      NvP p = make_nvp(c);
+      p.x = dy; p.y_in = ysv; p.w = w; p.gate = gate; p.res = dx_add; p.y = dx;
+      evt_set_last_tag("conv_naive_bwd_data");
+      hipLaunchKernelGGL((c->dtype == EVT_DT_HALF ? conv_naive_bwd_data<h16_t> : conv_naive_bwd_data<float>),
+                         dim3(naive_blocks((long)c->nseq * c->lin * c->cin)), dim3(256), 0, st, p);
+      return evt_check_launch();
     }
-  } else {
-    // dx[i][ci] = sum_t sum_co dy[i*s + t - pad][co] W[ci][co][t]  (REG image, rows = ci)
-    p.KHp = l.reg_kp; p.nchunk = l.reg_nchunk;
-    p.s_in = c->stride; p.dil = 1; p.off_in = -c->pad;
-    p.s_out = 1; p.off_out = 0; p.off_out_phase = 0; p.Q = c->lin; p.w_phase_stride = 0;
   }
-  return launch_igemm(c->dtype, p, c->cin, c->cout, nphase, st, c->impl == EVT_IMPL_AUTO);
+  r.p.x = dy; r.p.xact = ysv; r.p.w = w; r.p.res = dx_add; r.p.gate = gate; r.p.y = dx;
+  return launch_conv(c->dtype, r, st);
+}
+
+int evt_conv1d_route(const evt_conv1d_params* c, int32_t pass, int32_t fused, evt_conv_route* o) {
+  int rc = valid(c);
+  if (rc) return rc;
+  if (!o || pass < EVT_PASS_FWD || pass > EVT_PASS_BWD_WEIGHT) return EVT_EINVAL;
+  *o = evt_conv_route{};
+  if (pass == EVT_PASS_BWD_WEIGHT) {
+    const WgRoute r = wg_route(c);       // (the gradient image has the REG geometry: image stays EVT_IMG_REG)
+    o->family = r.family; o->fuses_bias = r.fuses_bias; o->khp = r.p.KHp; o->dil = r.p.dil; o->q = r.p.Q;
+    o->la = r.p.LA; o->lb = r.p.LB; o->ca = r.p.CA; o->cb = r.p.CB; o->s = r.p.s; o->off = r.p.off;
+    return r.rc;
+  }
+  ConvRoute r;
+  rc = pass == EVT_PASS_FWD ? fwd_route(c, (fused & EVT_FUSED_RES) != 0, &r)
+                            : bwd_data_route(c, (fused & EVT_FUSED_ADD) != 0, true, &r);
+  const ConvP& p = r.p;
+  o->family = r.family; o->image = r.image; o->out_ch = r.out_ch; o->k_ch = r.k_ch; o->nphase = r.nphase; o->ck = r.ck;
+  o->nchunk = p.nchunk; o->khp = p.KHp; o->s_in = p.s_in; o->dil = p.dil; o->off_in = p.off_in; o->s_out = p.s_out;
+  o->off_out = p.off_out; o->off_out_phase = p.off_out_phase; o->q = p.Q; o->w_phase_stride = p.w_phase_stride;
+  return rc;
 }
 
 int evt_conv1d_bwd_weight(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
@@ -1407,74 +1492,18 @@ static int wg_check_args(const evt_conv1d_params* c, const void* x, const void* 
   return 0;
 }
 
-// Where a weight gradient goes: the descriptor of the MFMA kernels and the family that takes it.  ONE function for the
-// single entry point and for the grouped one: a member of a group runs the kernel it would run alone.
-struct WgRoute {
-  WgP p;
-  int lout;
-  const void* ysv;
-  bool grouped, igemm_path, gemm_w, halo_w, deep_w, ring_w;
-};
-
-static WgRoute wg_route(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
-                        const evt_wgrad_parts* sp, int* used_host) {
-  WgRoute r{};
-  const int lout = r.lout = evt_conv1d_lout(c);
-  const void* ysv = r.ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
-  evt_wlayout l; evt_conv1d_layout(c, &l);
-  const bool grouped = r.grouped = c->impl != EVT_IMPL_NAIVE && evt_grouped_supported(c);
-  const bool igemm_path = r.igemm_path = !grouped && c->impl != EVT_IMPL_NAIVE && igemm_ok(c) && l.reg_kp <= 64;
-  // descriptor of the MFMA weight-gradient kernels
-  WgP& p = r.p;
-  p.dw = dw; p.nseq = c->nseq; p.KH = c->k; p.KHp = l.reg_kp; p.s = c->stride; p.dil = c->dil; p.off = -c->pad;
-  if (!c->transposed) {
-    // dW[co][.][t][ci] += dy_eff[q][co] * lrelu(x)[q*s + t*dil - pad][ci]
-    p.A = dy; p.Aact = ysv; p.aact_kind = c->out_act; p.aact_slope = c->out_slope; p.a_slope = 1.f;
-    p.B = x; p.Bact = nullptr; p.bact_kind = 0; p.bact_slope = 1.f; p.b_slope = c->in_slope;
-    p.LA = lout; p.CA = c->cout; p.LB = c->lin; p.CB = c->cin; p.Q = lout;
-  } else {
-    // dW[ci][.][t][co] += lrelu(x)[i][ci] * dy_eff[i*s + t - pad][co]
-    p.A = x; p.Aact = nullptr; p.aact_kind = 0; p.aact_slope = 1.f; p.a_slope = c->in_slope;
-    p.B = dy; p.Bact = ysv; p.bact_kind = c->out_act; p.bact_slope = c->out_slope; p.b_slope = 1.f;
-    p.LA = c->lin; p.CA = c->cin; p.LB = lout; p.CB = c->cout; p.Q = c->lin;
-  }
-  p.dbias = nullptr;
-  if (sp) {
-    p.dw_extra = sp->dw_extra; p.part_stride = sp->part_stride; p.parts = sp->parts; p.prev_used = sp->prev_used;
-    p.db_part = sp->db_part; p.used = sp->used_dev; p.used_host = used_host; p.dirty0 = sp->dirty0 || sp->prev_used > 0;
-  }
-  // wide layers with plain operands: LDS-DMA GEMM kernel (conv_deep.hip); its dbias comes from the column-sum kernel
-  // dense layers (k = 1, long reductions): the 128 x 128 weight-gradient GEMM tile
-  const bool gemm_w = r.gemm_w = igemm_path && c->impl == EVT_IMPL_AUTO && !c->transposed && evt_conv::wgrad_gemm_eligible(p, c->dtype);
-  // stride-1 layers with 3..11 taps and long sequences: one staged window of x serves all taps (wgrad_halo.hip)
-  const bool halo_w = r.halo_w = !gemm_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_halo_eligible(p, c->dtype);
-  const bool deep_w = r.deep_w = !gemm_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_deep_eligible(p, c->dtype);
-  // latency-bound mid-size layers: ring-pipelined LDS-DMA kernel (fuses dbias when A is dy)
-  r.ring_w = !deep_w && !halo_w && igemm_path && c->impl == EVT_IMPL_AUTO && evt_conv::wgrad_ring_eligible(p, c->dtype);
-  return r;
-}
-
-// dbias is fused into the 16-bit MFMA weight-gradient kernels when their A operand is dy (plain Conv1d)
-static bool wg_fuses_bias_igemm(const evt_conv1d_params* c, const WgRoute& r, const float* dbias) {
-  return dbias && r.igemm_path && c->dtype == EVT_DT_HALF && !c->transposed;
-}
-
 int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const void* dy, const void* y, float* dw,
                                 float* dbias, evt_wgrad_parts* sp, void* stream) {
   int rc = wg_check_args(c, x, dy, y, dw, sp);
   if (rc) return rc;
   int used_host = 0;
   hipStream_t st = (hipStream_t)stream;
-  WgRoute route = wg_route(c, x, dy, y, dw, sp, &used_host);
+  WgRoute route = wg_route(c);
   WgP& p = route.p;
+  wg_operands(p, c, x, dy, y, dw, sp, &used_host);
   const int lout = route.lout;
-  const void* ysv = route.ysv;
-  const bool grouped = route.grouped, igemm_path = route.igemm_path, gemm_w = route.gemm_w, halo_w = route.halo_w,
-             deep_w = route.deep_w, ring_w = route.ring_w;
-  // dbias is fused into the bf16 MFMA weight-gradient kernel when its A operand is dy (plain Conv1d)
-  const bool cin1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 2;   // fuses dbias as well
-  const bool cout1 = !grouped && c->impl != EVT_IMPL_NAIVE && evt_small_kind(c) == 1;  // and so does the dot-product conv
-  const bool fuse_bias = dbias && ((igemm_path && c->dtype == EVT_DT_HALF && !c->transposed) || cin1 || cout1);
+  const void* ysv = c->out_act != EVT_ACT_NONE ? y : nullptr;
+  const bool fuse_bias = dbias && route.fuses_bias;
   float* ws = sp ? sp->ws : nullptr;
   const long ws_floats = sp ? (long)sp->ws_floats : 0;
   if (dbias && !fuse_bias) {
@@ -1511,47 +1540,43 @@ int evt_conv1d_bwd_weight_parts(const evt_conv1d_params* c, const void* x, const
       if (rc) return rc;
     }
   }
-  evt_set_last_tag("conv_naive_bwd_weight");
-  if (grouped) {
-    evt_set_last_tag("grouped_bwd_weight");
-    return evt_grouped_bwd_weight(c, x, dy, y, dw, stream);
+  p.dbias = fuse_bias ? dbias : nullptr;
+  switch (route.family) {
+    case EVT_WG_GROUPED: evt_set_last_tag("grouped_bwd_weight"); return evt_grouped_bwd_weight(c, x, dy, y, dw, stream);
+    case EVT_WG_COUT1: return evt_cout1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
+    case EVT_WG_CIN1: return evt_cin1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
+    case EVT_WG_NAIVE: {
+      if (route.rc) return route.rc;
+      NvP p = make_nvp(c);
+      p.x = x; p.res = dy; p.y_in = ysv; p.dw = dw;
+      const int d1n = c->transposed ? c->cout : c->cin / c->groups;
+      const int d0n = c->transposed ? c->cin : c->cout;
+      const long elems = (long)d0n * d1n * c->k;
+      const long pos = (long)c->nseq * (c->transposed ? c->lin : lout);
+      long split = (4096 + elems - 1) / elems;
+      const long maxsplit = (pos + 2047) / 2048;
+      if (split > maxsplit) split = maxsplit;
+      if (split < 1) split = 1;
+      p.nsplit = (int)split;
+      evt_set_last_tag("conv_naive_bwd_weight");
+      hipLaunchKernelGGL((c->dtype == EVT_DT_HALF ? conv_naive_bwd_weight<h16_t> : conv_naive_bwd_weight<float>),
+                         dim3((unsigned)elems, p.nsplit), dim3(256), 0, st, p);
+      return evt_check_launch();
+    }
+    case EVT_WG_GEMM:
+      p.parts = 0;                                     // no slab mode: the s1 dense layers accumulate into the arena
+      return evt_conv::launch_wgrad_gemm(p, st);
+    case EVT_WG_HALO:
+    case EVT_WG_DEEP:
+    case EVT_WG_RING:
+      if (!p.dbias) p.db_part = nullptr;
+      rc = route.family == EVT_WG_HALO ? evt_conv::launch_wgrad_halo(p, st)
+         : route.family == EVT_WG_DEEP ? evt_conv::launch_wgrad_deep(p, st) : evt_conv::launch_wgrad_ring(p, st);
+      if (sp) sp->used = used_host;
+      return rc;
   }
-  if (cout1) return evt_cout1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
-  if (cin1) return evt_cin1_bwd_weight(c, x, dy, y, dw, dbias, ws, ws_floats, stream);
-  const bool use_igemm = igemm_path;
-  if (c->impl == EVT_IMPL_IGEMM && !use_igemm) return EVT_ENOTSUP;
-  if (!use_igemm) {
-    NvP p = make_nvp(c);
-    p.x = x; p.res = dy; p.y_in = ysv; p.dw = dw;
-    const int d1n = c->transposed ? c->cout : c->cin / c->groups;
-    const int d0n = c->transposed ? c->cin : c->cout;
-    const long elems = (long)d0n * d1n * c->k;
-    const long pos = (long)c->nseq * (c->transposed ? c->lin : lout);
-    long split = (4096 + elems - 1) / elems;
-    const long maxsplit = (pos + 2047) / 2048;
-    if (split > maxsplit) split = maxsplit;
-    if (split < 1) split = 1;
-    p.nsplit = (int)split;
-    if (c->dtype == EVT_DT_HALF)
-      hipLaunchKernelGGL(conv_naive_bwd_weight<h16_t>, dim3((unsigned)elems, p.nsplit), dim3(256), 0, st, p);
-    else
-      hipLaunchKernelGGL(conv_naive_bwd_weight<float>, dim3((unsigned)elems, p.nsplit), dim3(256), 0, st, p);
-    return evt_check_launch();
-  }
-  if (gemm_w) {
-    p.dbias = fuse_bias ? dbias : nullptr;
-    p.parts = 0;                                     // no slab mode: the s1 dense layers accumulate into the arena
-    return evt_conv::launch_wgrad_gemm(p, st);
-  }
-  if (halo_w || deep_w || ring_w) {
-    p.dbias = fuse_bias ? dbias : nullptr;
-    if (!p.dbias) p.db_part = nullptr;
-    rc = halo_w ? evt_conv::launch_wgrad_halo(p, st) : (deep_w ? evt_conv::launch_wgrad_deep(p, st) : evt_conv::launch_wgrad_ring(p, st));
-    if (sp) sp->used = used_host;
-    return rc;
-  }
+  // EVT_WG_TILE: conv_wgrad_tr (16-bit), and conv_wgrad where its tile does not fit or the type is fp32
   if (c->dtype == EVT_DT_HALF) {
-    p.dbias = fuse_bias ? dbias : nullptr;
     p.ws = ws; p.ws_floats = ws_floats;
     if (p.parts < 2) p.parts = 0;                  // one slab = no split possible: scratch rows (or atomics) instead
     rc = launch_wgrad_tr(p, st);
@@ -1629,9 +1654,12 @@ int evt_conv1d_bwd_weight_group(const evt_wgrad_member* members, int32_t n, void
   for (int i = 0; i < n; ++i) {
     const evt_wgrad_member& m = members[i];
     int used_host = 0;
-    WgRoute r = wg_route(m.p, m.x, m.dy, m.y, m.dw, m.sp, &used_host);
+    WgRoute r = wg_route(m.p);
+    wg_operands(r.p, m.p, m.x, m.dy, m.y, m.dw, m.sp, &used_host);
+    // (a dense layer that wgrad_gemm takes alone has always joined the ring group where the ring kernel takes it too)
+    const bool ring = r.family == EVT_WG_RING || (r.family == EVT_WG_GEMM && evt_conv::wgrad_ring_eligible(r.p, m.p->dtype));
     // a bias gradient that the kernel does not fuse takes a launch of its own: the single path knows how
-    const bool together = r.ring_w && (!m.dbias || wg_fuses_bias_igemm(m.p, r, m.dbias));
+    const bool together = ring && (!m.dbias || r.fuses_bias);
     WgBucket* b = nullptr;
     if (together) {
       const evt_conv::WgRingShape sh = evt_conv::wgrad_ring_shape(r.p);

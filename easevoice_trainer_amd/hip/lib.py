@@ -64,6 +64,25 @@ class WLayout(C.Structure):
     ]
 
 
+class ConvRoute(C.Structure):
+    """evt_conv_route: what evt_conv1d_route says of one pass (family, image, descriptor geometry)"""
+    _fields_ = [
+        ("family", C.c_int32), ("image", C.c_int32), ("out_ch", C.c_int32), ("k_ch", C.c_int32), ("nphase", C.c_int32),
+        ("ck", C.c_int32), ("nchunk", C.c_int32), ("khp", C.c_int32),
+        ("s_in", C.c_int32), ("dil", C.c_int32), ("off_in", C.c_int32),
+        ("s_out", C.c_int32), ("off_out", C.c_int32), ("off_out_phase", C.c_int32),
+        ("q", C.c_int32), ("fuses_bias", C.c_int32), ("w_phase_stride", C.c_int64),
+        ("la", C.c_int32), ("lb", C.c_int32), ("ca", C.c_int32), ("cb", C.c_int32), ("s", C.c_int32), ("off", C.c_int32),
+    ]
+
+
+PASS_FWD, PASS_BWD_DATA, PASS_BWD_WEIGHT = 0, 1, 2
+FUSED_RES, FUSED_ADD = 1, 2
+IMG_REG, IMG_ALT = 0, 1
+CONV_FAMILIES = ("ROWS16", "GROUPED", "COUT1", "CIN1", "NAIVE", "DEEP", "NARROW", "IGEMM")        # EVT_CONV_*, by value
+WG_FAMILIES = ("GROUPED", "COUT1", "CIN1", "NAIVE", "GEMM", "HALO", "DEEP", "RING", "TILE")        # EVT_WG_*
+
+
 class WPrepItem(C.Structure):
     _fields_ = [
         ("v", C.c_void_p), ("g", C.c_void_p), ("reg", C.c_void_p), ("alt", C.c_void_p),

@@ -96,17 +96,21 @@ typedef struct evt_conv1d_params {
 } evt_conv1d_params;
 
 /* output length for these hyper-parameters (torch semantics) */
-/* 1 when the backward of this conv runs on the LDS-DMA GEMM path (conv_deep), which takes dy with the output
- * activation's derivative already applied (evt_dact_mul) and out_act = EVT_ACT_NONE in the backward calls; else 0. */
+int32_t evt_conv1d_lout(const evt_conv1d_params* p);
+
+/* 1 when a backward pass of this conv (out_act != NONE) would run on a kernel that takes plain operands -- backward-data
+ * on the LDS-DMA GEMM path (conv_deep) or the narrow kernel, or the weight gradient on wgrad_deep / wgrad_halo -- if it
+ * were handed dy with the output activation's derivative already applied: the caller then applies evt_dact_mul once and
+ * makes both backward calls with out_act = EVT_ACT_NONE.  Else 0.  The answer is the route (evt_conv1d_route) of those
+ * calls. */
 int32_t evt_conv1d_wants_plain_dy(const evt_conv1d_params* c);
 
 /* 1 when the FORWARD of this conv (in_slope != 1: leaky-relu on load, the HiFi-GAN upsamplers of models.py:457-460) would
  * run on the LDS-DMA GEMM path if it were handed the activated input: the caller then applies evt_leaky_relu once,
  * calls forward and weight gradient with in_slope = 1 on the activated tensor, and backward-data with in_slope and the
- * activated tensor as `x` (leaky-relu keeps the sign, the derivative is the same).  Else 0. */
+ * activated tensor as `x` (leaky-relu keeps the sign, the derivative is the same).  Else 0.  The answer is the forward
+ * route of that call. */
 int32_t evt_conv1d_wants_plain_x(const evt_conv1d_params* c);
-
-int32_t evt_conv1d_lout(const evt_conv1d_params* p);
 
 /* Prepared-weight layouts.  The parameter tensor is W[d0][d1][k] (Conv1d: d0=cout, d1=cin/g;
  * ConvTranspose1d: d0=cin, d1=cout).  Two GEMM-ready images are derived from it:
@@ -122,6 +126,57 @@ typedef struct evt_wlayout {
   int64_t reg_elems, alt_elems;
 } evt_wlayout;
 int evt_conv1d_layout(const evt_conv1d_params* p, evt_wlayout* out);
+
+/* Where a pass of these parameters goes, on the host alone (no device, no pointers, no stream): the kernel family, the
+ * prepared image it reads and the geometry of its launch descriptor.  It is what evt_conv1d_fwd / _bwd_data / _bwd_weight
+ * do with the same parameters: they and this query call one routing function per pass (csrc/conv1d.hip).
+ * `fused` holds the facts a call adds to the parameters: EVT_FUSED_RES (forward: `res` is given), EVT_FUSED_ADD
+ * (backward-data: `dx_add` is given); the gate and the saved activation of the backward passes are the parameters'
+ * in_slope != 1 and out_act != NONE.  Returns what the entry point would return before it launches (EVT_ENOTSUP for
+ * EVT_IMPL_IGEMM on a shape the MFMA kernels do not take).
+ * Forward / backward-data families, in their order of precedence: ROWS16, GROUPED, COUT1, CIN1, NAIVE, then for the
+ * implicit-GEMM shapes DEEP (conv_deep | conv_deep32 | conv_ring), NARROW, IGEMM; the geometry fields are filled for the
+ * last three and 0 otherwise.  (A COUT1 / CIN1 backward-data launcher may still decline on its LDS bound; the entry point
+ * then takes the route without the two.)  Weight gradient: GROUPED, COUT1, CIN1, NAIVE, GEMM, HALO, DEEP, RING, TILE
+ * (conv_wgrad_tr, and conv_wgrad where that tile does not fit or the type is fp32); from GEMM on, the descriptor
+ * dW[a][chunk(b)][tap][cc] += sum_q A[q][a] * B[q * s + tap * dil + off][b] is returned in la .. off, khp, dil and q. */
+#define EVT_PASS_FWD 0
+#define EVT_PASS_BWD_DATA 1
+#define EVT_PASS_BWD_WEIGHT 2
+#define EVT_FUSED_RES 1
+#define EVT_FUSED_ADD 2
+#define EVT_IMG_REG 0
+#define EVT_IMG_ALT 1
+#define EVT_CONV_ROWS16 0
+#define EVT_CONV_GROUPED 1
+#define EVT_CONV_COUT1 2
+#define EVT_CONV_CIN1 3
+#define EVT_CONV_NAIVE 4
+#define EVT_CONV_DEEP 5
+#define EVT_CONV_NARROW 6
+#define EVT_CONV_IGEMM 7
+#define EVT_WG_GROUPED 0
+#define EVT_WG_COUT1 1
+#define EVT_WG_CIN1 2
+#define EVT_WG_NAIVE 3
+#define EVT_WG_GEMM 4 /* from here on: the MFMA kernels */
+#define EVT_WG_HALO 5
+#define EVT_WG_DEEP 6
+#define EVT_WG_RING 7
+#define EVT_WG_TILE 8
+typedef struct evt_conv_route {
+  int32_t family;                          /* EVT_CONV_* (forward, backward-data) or EVT_WG_* (weight gradient) */
+  int32_t image;                           /* EVT_IMG_* */
+  int32_t out_ch, k_ch, nphase;            /* output channels, K-side channels, polyphase launches in one grid */
+  int32_t ck, nchunk, khp;                 /* of the image: channels per chunk, chunks, taps (zero padded) */
+  int32_t s_in, dil, off_in;               /* K-side row of (q, tap) = q * s_in + tap * dil + off_in */
+  int32_t s_out, off_out, off_out_phase;   /* output row of (q, phase) = q * s_out + off_out + phase * off_out_phase */
+  int32_t q;                               /* q per sequence */
+  int32_t fuses_bias;                      /* weight gradient: the family adds dbias itself */
+  int64_t w_phase_stride;                  /* elements between the phases of the image */
+  int32_t la, lb, ca, cb, s, off;          /* weight gradient: rows and channels of A and B, stride, offset */
+} evt_conv_route;
+int evt_conv1d_route(const evt_conv1d_params* c, int32_t pass, int32_t fused, evt_conv_route* out);
 
 /* Multi-tensor weight preparation: one launch for a whole model.
  * Replaces torch.nn.utils.weight_norm's per-forward w = g * v / ||v|| (dims 1,2 per d0 row;

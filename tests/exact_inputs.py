@@ -453,6 +453,21 @@ def conv_fusions(case):
     return FUSIONS
 
 
+DT = dict(bf16=torch.bfloat16, f16=torch.float16, f32=torch.float32)       # the dtype names of conv_runs()
+IMPL = dict(auto=0, naive=1)                                               # ... and the impl names: EVT_IMPL_*
+
+
+def conv_params(case, dn, impl, in_slope, out_act, out_slope):
+    """the evt_conv1d_params of one call of a conv run: what the slot of the run's module hands the library (hip/bank.py::
+    ConvSlot.params; tests/test_exact_int_gpu.py::run_conv asserts that the two are the same bytes).  dn / impl as in
+    conv_runs(); the library that serves DT[dn] must be the selected one (hip.lib.set_half)"""
+    from easevoice_trainer_amd.hip import lib as L
+
+    cin, cout, k, stride, pad, dil, groups, transposed, wn, lin, nseq = case
+    return L.ConvParams(L.dt_code(DT[dn]), nseq, lin, cin, cout, k, stride, pad, dil, groups, 1 if transposed else 0,
+                        in_slope, out_act, out_slope, IMPL[impl])
+
+
 # residual units: (C, k, d, L) -- the existing tests' ragged lengths plus tile +- 1 (64-position tiles).  The fused kernels
 # take L >= 64 (resunit.hip::job_ok, resunit_wide.hip::wide_ok): L = 63 is res_unit's composition of single launches.
 RESUNIT_CASES = sorted({(C, k, d, L) for C in (16, 32, 64, 128, 256) for (k, d, L) in

@@ -1,6 +1,6 @@
 """CPU check of the conv kernels' ADDRESSING: a numpy emulation of the prepared-weight images
-(wn_fold_kernel's reg_idx/alt_idx) and of conv_igemm / conv_wgrad's index maps, driven by the same
-launch geometry the C++ host code derives, compared with the CPU oracle.  It pins the derivations
+(wn_fold_kernel's reg_idx/alt_idx) and of conv_igemm / conv_wgrad's index maps, driven by the launch
+geometry the C++ host code derives (evt_conv1d_layout, evt_conv1d_route), compared with the CPU oracle.  It pins the derivations
 (tap flip, polyphase split, offsets) without a GPU; the HIP kernels themselves are tested with -m gpu.
 """
 import ctypes as C
@@ -87,43 +87,44 @@ def test_igemm_index_math(case, dt):
     reg, alt = make_images(w.numpy(), lay)
     xn = x.detach().numpy().transpose(0, 2, 1)
     dyn = dy.numpy().transpose(0, 2, 1)
-    J = (k + stride - 1) // stride
+    # The launch geometry is the library's own: evt_conv1d_route is the function the entry points ask before they launch.
+    # Every case here has cin % 16 == cout % 16 == 0, groups == 1, k > 1 and no dilated stride, so none lands on the rows16,
+    # grouped, small or direct-form kernels, which do not read this geometry: the families asserted are the ones that do.
+    assert cin % 16 == 0 and cout % 16 == 0 and k > 1 and (stride == 1 or dil == 1)
+    p = L.ConvParams(dt, nseq, Lin, cin, cout, k, stride, pad, dil, 1, int(transposed), 1.0, 0, 1.0, 0)
+
+    def route(which):
+        r = L.ConvRoute()
+        assert L.lib().evt_conv1d_route(C.byref(p), which, 0, C.byref(r)) == 0
+        return r
+
+    def emulate(r, xk, Lo):
+        assert L.CONV_FAMILIES[r.family] in ("IGEMM", "DEEP", "NARROW")
+        img = reg if r.image == L.IMG_REG else alt
+        return igemm_emulate(xk, img, r.out_ch, r.k_ch, r.ck, r.nchunk, r.khp, r.nphase, r.w_phase_stride, r.s_in, r.dil,
+                             r.off_in, r.s_out, r.off_out, r.off_out_phase, r.q, Lo)
 
     # ---- forward (evt_conv1d_fwd) ----
-    if not transposed:
-        y = igemm_emulate(xn, reg, cout, cin, lay.reg_ck, lay.reg_nchunk, lay.reg_kp, 1, 0, stride, dil, -pad, 1, 0, 0,
-                          Lout, Lout)
-    elif stride == 1:
-        y = igemm_emulate(xn, alt, cout, cin, lay.alt_ck, lay.alt_nchunk, lay.alt_kp, 1, 0, 1, 1, pad - (k - 1), 1, 0,
-                          0, Lout, Lout)
-    else:
-        y = igemm_emulate(xn, alt, cout, cin, lay.alt_ck, lay.alt_nchunk, lay.alt_kp, stride, 0, 1, 1, -(J - 1),
-                          stride, -pad, 1, (Lout - 1 + pad) // stride + 1, Lout)
+    y = emulate(route(L.PASS_FWD), xn, Lout)
     np.testing.assert_allclose(y, y_ref.detach().numpy().transpose(0, 2, 1), atol=1e-9)
 
     # ---- backward-data (evt_conv1d_bwd_data) ----
-    if not transposed:
-        if stride == 1:
-            dx = igemm_emulate(dyn, alt, cin, cout, lay.alt_ck, lay.alt_nchunk, lay.alt_kp, 1, 0, 1, dil,
-                               pad - (k - 1) * dil, 1, 0, 0, Lin, Lin)
-        else:
-            dx = igemm_emulate(dyn, alt, cin, cout, lay.alt_ck, lay.alt_nchunk, lay.alt_kp, stride, 0, 1, 1, -(J - 1),
-                               stride, -pad, 1, (Lin - 1 + pad) // stride + 1, Lin)
-    else:
-        dx = igemm_emulate(dyn, reg, cin, cout, lay.reg_ck, lay.reg_nchunk, lay.reg_kp, 1, 0, stride, 1, -pad, 1, 0, 0,
-                           Lin, Lin)
+    dx = emulate(route(L.PASS_BWD_DATA), dyn, Lin)
     np.testing.assert_allclose(dx, dx_ref.numpy().transpose(0, 2, 1), atol=1e-9)
 
-    # ---- backward-weight (conv_wgrad): dW[a][chunk][t][cc] += A[q][a] * B[q*s + t*dil - pad][b] ----
+    # ---- backward-weight (conv_wgrad): dW[a][chunk][t][cc] += A[q][a] * B[q*s + t*dil + off][b] ----
     wl = w.clone().requires_grad_(True)
     y2 = O.conv_block(x.detach(), wl, stride=stride, pad=pad, dil=dil, transposed=transposed)
     (dw_ref,) = torch.autograd.grad(y2, wl, dy)
     Aop, Bop = (dyn, xn) if not transposed else (xn, dyn)
     CA, CB = Aop.shape[2], Bop.shape[2]
+    g = route(L.PASS_BWD_WEIGHT)
+    assert L.WG_FAMILIES[g.family] in ("GEMM", "HALO", "DEEP", "RING", "TILE")          # the kernels that read a WgP
+    assert (g.la, g.ca, g.lb, g.cb, g.khp) == (Aop.shape[1], CA, Bop.shape[1], CB, lay.reg_kp)
     dW = np.zeros((CA, lay.reg_nchunk, lay.reg_kp, lay.reg_ck))
-    for q in range(Aop.shape[1]):
+    for q in range(g.q):
         for t in range(k):
-            r = q * stride + t * dil - pad
+            r = q * g.s + t * g.dil + g.off
             if 0 <= r < Bop.shape[1]:
                 dW[:, :, t, :] += np.einsum("sa,snc->anc", Aop[:, q, :], Bop[:, r, :].reshape(nseq, lay.reg_nchunk, lay.reg_ck))
     got = dW[:, :, :k, :].transpose(0, 1, 3, 2).reshape(CA, CB, k)

@@ -32,8 +32,7 @@ import exact_inputs as X
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 TAGS_PATH = os.path.join(HERE, "golden", "exact_int_tags.json")
-DT = dict(bf16=torch.bfloat16, f16=torch.float16, f32=torch.float32)
-IMPL = dict(auto=0, naive=1)
+DT, IMPL = X.DT, X.IMPL
 RECORD = os.environ.get("EXACT_INT_RECORD")          # a path: write the observed tags there instead of asserting them
 _observed = {}
 
@@ -119,6 +118,9 @@ def run_conv(gpu, case, fusion, dn, impl, inp, ref, trace=True, weight_grads=Tru
     bank.build_tables()
     bank.fold()
     ctx = f"[case={case} fusion={fusion['name']} dtype={dn} impl={impl}]"
+    # the parameters tests/test_conv_route_cpu.py routes without a GPU are the ones this run hands the library
+    cfg = (fusion["in_slope"], fusion["out_act"], fusion["out_slope"])
+    assert bytes(m._slot.params(case[10], case[9], *cfg)) == bytes(X.conv_params(case, dn, impl, *cfg)), ctx
 
     def body():
         y, dx, dres = _conv_pass(gpu, bank, mods, m, inp, fusion, dtype, inp["dy"])
