@@ -83,6 +83,10 @@ template <> __device__ __forceinline__ h16_t from_f<h16_t>(float v) { return f2h
 
 __device__ __forceinline__ float lrelu_f(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// GELU, erf form (transformers' "gelu"): the one function behind evt_gelu_rows_fwd, the HuBERT front end and the epilogue of
+// evt_pos_conv_rows, so that a fused and an unfused pass give the same bits
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
 // derivative factor of an activation, expressed through the activation's OUTPUT value `ya`
 // (lrelu with slope>0 keeps the sign, tanh' = 1 - tanh^2)
 __device__ __forceinline__ float dact_from_out(int kind, float ya, float slope) {

@@ -20,8 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-
 // out[b][t][c] = gelu(x[b][t][c] + bias[c]) for t < t_out <= t_in (rows t >= t_out of the input are dropped)
 template <typename T>
 __global__ void gelu_rows_kernel(const T* x, const float* bias, T* out, long nseq, int t_in, int t_out, int C) {

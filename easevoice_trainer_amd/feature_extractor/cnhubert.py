@@ -11,8 +11,9 @@ state_dict loads as is (`load_hf_state_dict`); channels-last [B, T, C] rows; eve
                       GroupNorm(512, 512) + GELU after the first (evt_channel_norm_gelu_fwd), GELU after the others
   feature projection  LayerNorm(512) (evt_add_layernorm_fwd) -> Linear 512 -> 768 (1x1 convolution)
   positional conv     grouped convolution 768 -> 768, k = 128, 16 groups, padding 64 (weight-norm over the tap axis, folded
-                      once at load time), bias + drop-last-frame + GELU in one launch (evt_gelu_rows_fwd), residual +
-                      LayerNorm (evt_add_layernorm_fwd)
+                      once at load time) + bias + drop-last-frame + GELU in ONE launch on the rows' own frames
+                      (evt_pos_conv_rows, csrc/pos_conv.hip: per group a GEMM frames x 48 x 6144 on the MFMA, the weight
+                      packed once into fragment order), residual + LayerNorm (evt_add_layernorm_fwd)
   12 encoder layers   packed q | k | v projection + attention core (evt_mha_fwd through hip/enc.py::rel_self_attention,
                       window None), out projection, LayerNorm(x + attn), Linear 768 -> 3072, GELU, Linear 3072 -> 768,
                       LayerNorm(x + ffn)
@@ -28,7 +29,7 @@ from torch import nn
 from ..hip import lib as L
 from ..hip.conv import EvtConv1d, mask_tail
 from ..hip.enc import new_site, rel_self_attention
-from ..hip.feat import add_layernorm, channel_norm_gelu, gelu_rows, hubert_front_rows
+from ..hip.feat import add_layernorm, channel_norm_gelu, gelu_rows, hubert_front_rows, pos_conv_image, pos_conv_rows
 from ..module.attentions import linear_rows
 from ..runtime import ModelRuntime
 
@@ -95,13 +96,22 @@ class _PosConv(nn.Module):
 
     def __init__(self, hidden, k, groups):
         super().__init__()
-        self.conv = EvtConv1d(hidden, hidden, k, padding=k // 2, groups=groups, bias=True)
+        self.conv = EvtConv1d(hidden, hidden, k, padding=k // 2, groups=groups, bias=True)     # the parameter holder
         self.k = k
+        self._image = None
 
-    def forward(self, x):
-        # the convolution without its bias epilogue; bias, the dropped last frame of an even kernel and GELU in one launch
-        y = self.conv(x)
-        return gelu_rows(y, None, y.size(1) - (1 if self.k % 2 == 0 else 0))
+    def forward(self, x, lens=None):
+        """x [B, T, C] (+ frame counts int32 [B] of a ragged batch) -> gelu(conv(x) + bias) with the last frame of an even
+        kernel dropped, per row over the row's own frames: ONE launch (hip/feat.py::pos_conv_rows).  The fragment-order image
+        of the weight is packed on first use and again when the parameters were replaced or written (a reloaded
+        checkpoint) or the dtype changed: torch's version counters, as SynthesizerTrn.extract_latent_rows."""
+        w, b = self.conv.weight, self.conv.bias
+        stamp = (w.data_ptr(), w._version, b.data_ptr(), b._version, x.dtype)
+        if self._image is None or self._image[0] != stamp:
+            b32 = b.detach().float().contiguous()
+            self._image = (stamp, pos_conv_image(w.detach().float().contiguous(), self.conv.groups, x.dtype),
+                           b32 if b32.data_ptr() % 16 == 0 else b32.clone())
+        return pos_conv_rows(x.contiguous(), lens, self._image[1], self._image[2], self.conv.groups, self.k)
 
 
 class _Attention(nn.Module):
@@ -151,7 +161,7 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList(_EncoderLayer(hidden, heads, inner, eps) for _ in range(layers))
 
     def forward(self, x, lens):
-        x = self.layer_norm(x, self.pos_conv_embed(x))
+        x = self.layer_norm(x, self.pos_conv_embed(x, lens))
         for layer in self.layers:
             x = layer(x, lens)
         return x

@@ -1,5 +1,5 @@
-"""Bindings of the feature extractors' own launches (csrc/feat_ops.hip) and the LayerNorm entry point they share with the s1
-blocks.  Inference only: nothing here records an autograd graph."""
+"""Bindings of the feature extractors' own launches (csrc/feat_ops.hip, csrc/pos_conv.hip, csrc/semantic.hip) and the
+LayerNorm entry point they share with the s1 blocks.  Inference only: nothing here records an autograd graph."""
 import torch
 
 from . import lib as L
@@ -207,6 +207,66 @@ def semantic_codes_rows(hs, frames, proj_image, bias, embed, ee=None):
         proj_image.data_ptr(), bias.data_ptr(), embed.data_ptr(), ee.data_ptr(), codes.data_ptr() if total else None, total,
         L.stream_ptr()), "evt_semantic_codes_rows")
     return codes, offsets
+
+
+POS_CONV_TILE = 256       # EVT_POS_CONV_TILE: frames per block, counted from a row's frame 0
+POS_CONV_CG = (16, 32, 48, 64)
+
+
+def _pos_conv_shape(what, C, groups, k):
+    """the shapes evt_pos_conv_pack / evt_pos_conv_rows serve, refused here before a launch"""
+    C, groups, k = int(C), int(groups), int(k)
+    cg = C // groups if groups > 0 and C % groups == 0 else 0
+    if cg not in POS_CONV_CG or not 2 <= k <= 128 or (k * cg) % 32:
+        raise L.EvtError(f"{what}: {C} channels in {groups} groups with k = {k} are not served "
+                         f"(channels per group in {POS_CONV_CG}, 2 <= k <= 128, k * cg a multiple of 32)")
+    return cg
+
+
+def pos_conv_image(weight, groups, dtype):
+    """weight [C, C / groups, k] fp32 on the GPU (the folded weight of the grouped convolution) -> the image
+    evt_pos_conv_rows reads: C * (C / groups) * k elements of dtype in MFMA fragment order (evt_pos_conv_pack; one launch,
+    once per loaded checkpoint)"""
+    if (not torch.is_tensor(weight) or weight.dim() != 3 or weight.dtype != torch.float32 or not weight.is_cuda
+            or not weight.is_contiguous() or weight.data_ptr() % 16):
+        raise L.EvtError("pos_conv_image: a contiguous, 16-byte aligned float32 weight [C, C / groups, k] on the GPU expected")
+    C, cg, k = weight.shape
+    if _pos_conv_shape("pos_conv_image", C, groups, k) != cg:
+        raise L.EvtError(f"pos_conv_image: weight {tuple(weight.shape)} is not that of {groups} groups")
+    image = torch.empty(C * cg * k, dtype=dtype, device=weight.device)
+    L.check(L.lib().evt_pos_conv_pack(L.dt_code(dtype), weight.data_ptr(), C, int(groups), k, image.data_ptr(),
+                                      L.stream_ptr()), "evt_pos_conv_pack")
+    return image
+
+
+def pos_conv_rows(x, lens, image, bias, groups, k, gelu=True):
+    """x [nseq, T, C] rows (fp32 or the build's 16-bit type), lens int32 [nseq] on the GPU or None (every row full), image
+    from `pos_conv_image` of x's dtype, bias fp32 [C] or None -> [nseq, T, C]: the grouped same-length convolution (padding
+    k // 2, the last frame of an even k dropped) per row over the row's own frames + bias (+ GELU), zeros behind them, ONE
+    launch (evt_pos_conv_rows; include/evt.h has the definition).  x is not read at or behind a row's length; a row comes
+    out bit for bit as it does alone."""
+    if not torch.is_tensor(x) or x.dim() != 3 or not x.is_cuda or not x.is_contiguous() or x.size(0) < 1 or x.size(1) < 1:
+        raise L.EvtError("pos_conv_rows: contiguous rows [nseq, T, C] on the GPU expected")
+    nseq, T, C = x.shape
+    cg = _pos_conv_shape("pos_conv_rows", C, groups, k)
+    if nseq > 65535:
+        raise L.EvtError(f"pos_conv_rows: {nseq} rows, at most 65535 are served")
+    if lens is not None:
+        L.check_lens("pos_conv_rows", x, lens)
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise L.EvtError("pos_conv_rows is inference only: run it under torch.no_grad()")
+    if (not torch.is_tensor(image) or image.dtype != x.dtype or image.device != x.device or image.numel() != C * cg * int(k)
+            or not image.is_contiguous() or image.data_ptr() % 16):
+        raise L.EvtError(f"pos_conv_rows: image must be pos_conv_image's {C * cg * int(k)} elements of {x.dtype} on {x.device}")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or bias.device != x.device
+                             or bias.numel() != C or not bias.is_contiguous() or bias.data_ptr() % 16):
+        raise L.EvtError(f"pos_conv_rows: bias must be contiguous, 16-byte aligned float32 [{C}] on {x.device}")
+    out = torch.empty_like(x)
+    L.check(L.lib().evt_pos_conv_rows(
+        L.dt_of(x), x.data_ptr(), None if lens is None else lens.data_ptr(), nseq, T, C, int(groups), int(k),
+        image.data_ptr(), None if bias is None else bias.data_ptr(), 1 if gelu else 0, out.data_ptr(), L.stream_ptr()),
+        "evt_pos_conv_rows")
+    return out
 
 
 def add_layernorm(x, r, gamma, beta, eps):

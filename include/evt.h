@@ -1250,6 +1250,35 @@ int evt_semantic_codes_rows(int32_t dtype, const void* hs, const int32_t* frames
                             const float* bias, const float* embed, const float* ee, int64_t* codes, int64_t total,
                             void* stream);
 
+/* HuBERT's positional convolution (HubertPositionalConvEmbedding: a grouped Conv1d C -> C with a long kernel, padding k / 2,
+ * the last frame of an even kernel dropped, GELU) on a RAGGED batch of channels-last rows, bias and GELU in the epilogue:
+ * one launch, forward only.  Per group the layer is a GEMM with M = frames, N = cg = C / G, K = k * cg, on the MFMA.
+ *
+ * evt_pos_conv_pack: w fp32 [C][cg][k] (the folded weight) -> image, C * cg * k elements of dtype (fp32 kept, or rounded once
+ *   to the build's 16-bit type), in fragment order [G][k * cg / 32 K steps][cg / 16 column tiles][64 lanes][8]:
+ *     image[(((g * KS + ks) * NT + ct) * 64 + 16 q + j) * 8 + i] = w[g * cg + 16 ct + j][kk % cg][kk / cg],
+ *     kk = 32 ks + 8 q + i   (K index = tap * cg + channel; j < 16, q < 4, i < 8).
+ *   One launch; run once per loaded checkpoint.
+ * evt_pos_conv_rows: x, out [nseq][T][C] of dtype; lens device int32 [nseq] or NULL (every row full); row s has
+ *   n_s = min(max(lens[s], 0), T) live frames; bias fp32 [C] or NULL; act 0 none, 1 GELU (erf form, evt_gelu_rows_fwd's).
+ *     out[s][t][g cg + o] = act(bias[g cg + o] + sum_{tap < k} sum_{c < cg} x[s][t + tap - k / 2][g cg + c] * w[g cg + o][c][tap])
+ *                                                                                              t <  n_s, rounded once
+ *     out[s][t][:]        = 0                                                                  n_s <= t < T
+ *   with x taken as zero outside [0, n_s): for even k torch's Conv1d(padding = k / 2) with the last frame dropped, for odd k
+ *   the same-length convolution.  Every element of out is written; x is never read at or behind frame n_s of a row.
+ * Summation order: a block owns EVT_POS_CONV_TILE frames of one (row, group), counted from the row's frame 0; it walks K in
+ * ascending steps of 32 (no split-K, no atomics), fp32 accumulation on the MFMA (mfma_f32_16x16x32 of the 16-bit type;
+ * mfma_f32_16x16x4f32, true fp32, eight per step, lane quarter q supplying kk = 32 ks + 8 q + i in the i-th), then bias, then
+ * act, in fp32.  Neither nseq nor T enters: a row's live frames are bit for bit those of nseq = 1 with any T >= n_s.
+ * No host synchronisation: legal in a captured graph.
+ * EVT_EINVAL (nothing launched) for a NULL pointer other than lens / bias, nseq, T, C, G or k <= 0, nseq > 65535, x, out,
+ * image, w or bias not 16-byte aligned; EVT_ENOTSUP for a dtype the build does not serve and for shapes outside
+ * C % G == 0, cg in {16, 32, 48, 64}, 2 <= k <= 128, (k * cg) % 32 == 0, act in {0, 1}. */
+#define EVT_POS_CONV_TILE 256
+int evt_pos_conv_pack(int32_t dtype, const float* w, int32_t C, int32_t G, int32_t k, void* image, void* stream);
+int evt_pos_conv_rows(int32_t dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t T, int32_t C, int32_t G,
+                      int32_t k, const void* image, const float* bias, int32_t act, void* out, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
