@@ -14,8 +14,8 @@ state_dict loads as is (`load_hf_state_dict`); channels-last [B, T, C] rows; eve
                       once at load time) + bias + drop-last-frame + GELU in ONE launch on the rows' own frames
                       (evt_pos_conv_rows, csrc/pos_conv.hip: per group a GEMM frames x 48 x 6144 on the MFMA, the weight
                       packed once into fragment order), residual + LayerNorm (evt_add_layernorm_fwd)
-  12 encoder layers   packed q | k | v projection + attention core (evt_mha_fwd through hip/enc.py::rel_self_attention,
-                      window None), out projection, LayerNorm(x + attn), Linear 768 -> 3072, GELU, Linear 3072 -> 768,
+  12 encoder layers   packed q | k | v projection + attention core (hip/enc.py::rel_self_attention, window None: in
+                      float32 evt_mha_rows_f32, the fp32 MFMA flash kernel; in 16 bit evt_mha_fwd), out projection, LayerNorm(x + attn), Linear 768 -> 3072, GELU, Linear 3072 -> 768,
                       LayerNorm(x + ffn)
 A RAGGED batch of clips goes through `HubertModel.forward_rows` (`CNHubert.last_hidden_state_batch` / `.batch`): the first
 convolution, its GroupNorm over each row's own frames and GELU in evt_hubert_front_rows, tails zeroed in front of the
@@ -124,7 +124,7 @@ class _Attention(nn.Module):
 
     def forward(self, x, lens):
         o = rel_self_attention(x, self.q_proj, self.k_proj, self.v_proj, None, None, lens, self.num_heads, None, 0.0,
-                               self._site)
+                               self._site, rows_kernel=True)
         return self.out_proj(o)
 
 

@@ -9,7 +9,8 @@ The encoder is restated module for module with the checkpoint's parameter names 
 `bert.encoder.layer.N.attention.self.{query,key,value}`, `.attention.output.{dense,LayerNorm}`, `.intermediate.dense`,
 `.output.{dense,LayerNorm}`), so `load_state_dict(checkpoint, strict=False)` fills it; the masked-LM head (`cls.*`) and the
 layers above the one that is read are not built.  Rows are [B, T, C]; per layer: three 1x1-convolution projections + the
-attention core (hip/enc.py::rel_self_attention, window None, key padding by lengths), the output projection,
+attention core (hip/enc.py::rel_self_attention, window None, key padding by lengths; in float32 the core is
+evt_mha_rows_f32, the fp32 MFMA flash kernel), the output projection,
 LayerNorm(x + attn) (evt_add_layernorm_fwd), Linear -> GELU (evt_gelu_rows_fwd) -> Linear, LayerNorm(x + ffn).  The
 embedding sum (word + position + token type) is a gather and its LayerNorm one launch.  Inference only.
 
@@ -63,7 +64,8 @@ class _SelfAttention(nn.Module):
         self._site = new_site()
 
     def forward(self, x, lens):
-        return rel_self_attention(x, self.query, self.key, self.value, None, None, lens, self.heads, None, 0.0, self._site)
+        return rel_self_attention(x, self.query, self.key, self.value, None, None, lens, self.heads, None, 0.0, self._site,
+                                  rows_kernel=True)
 
 
 class _SelfOutput(nn.Module):

@@ -304,14 +304,56 @@ class RelSelfAttnFn(torch.autograd.Function):
         return dx, None, demb[0], demb[1], None, None, None, None, None, None, None
 
 
-def rel_self_attention(x, conv_q, conv_k, conv_v, emb_k, emb_v, lens, n_heads, window, p, site, packed=None, scale=None):
+def attn_rows_route(dtype, window, p, D, grad_enabled):
+    """whether a self-attention asked for with rows_kernel=True runs its core on evt_mha_rows_f32 (csrc/mha_rows.hip, the
+    fp32 MFMA flash kernel of the feature extractors): float32, no relative window, no dropout, a head width the kernel
+    serves, and no autograd graph to record (it has no backward).  Everything else stays on evt_mha_fwd.  No threshold on
+    the row width: the kernel measured faster than evt_mha_fwd's fp32 core at every shape the extractors send
+    (profiles/mha_rows_stage.json: 2.8x - 10.3x on HuBERT's clips, 1.5x on BERT sentences in groups of 1, 1.4x on those of at
+    most 64 tokens), and a threshold on the padded width would give one sentence two kernels depending on its group."""
+    from .feat import MHA_ROWS_D
+
+    return dtype == torch.float32 and window is None and p == 0 and D in MHA_ROWS_D and not grad_enabled
+
+
+def _self_attention_rows(x, slots, lens, n_heads, scale):
+    """the projections exactly as RelSelfAttnFn.forward runs them (one packed GEMM or three launches into the planes of one
+    buffer), the core on evt_mha_rows_f32: no lse, no autograd node"""
+    from . import conv as HC
+    from .feat import mha_rows_launch
+
+    B, T, _ = x.shape
+    packed = len(slots) == 1
+    Cc = slots[0].module.cout // 3 if packed else slots[0].module.cout
+    if x.dtype != slots[0].bank.dtype or not x.is_contiguous() or Cc % n_heads:
+        raise L.EvtError(f"self-attention: contiguous {slots[0].bank.dtype} [B, T, C] expected, got {tuple(x.shape)} {x.dtype}")
+    if lens is not None:
+        L.check_lens("self-attention", x, lens)
+    if packed:
+        qkv = torch.empty((B, T, 3 * Cc), dtype=x.dtype, device=x.device)
+        HC._fwd(slots[0], x, None, 1.0, L.ACT_NONE, 1.0, out=qkv)
+        ld, step = 3 * Cc, Cc * x.element_size()
+    else:
+        qkv = torch.empty((3, B, T, Cc), dtype=x.dtype, device=x.device)
+        for i, s in enumerate(slots):
+            HC._fwd(s, x, None, 1.0, L.ACT_NONE, 1.0, out=qkv[i])
+        ld, step = Cc, B * T * Cc * x.element_size()
+    base = qkv.data_ptr()
+    return mha_rows_launch(base, base + step, base + 2 * step, lens, lens, B, T, T, n_heads, Cc // n_heads, ld, ld, scale, x.device)
+
+
+def rel_self_attention(x, conv_q, conv_k, conv_v, emb_k, emb_v, lens, n_heads, window, p, site, packed=None, scale=None,
+                       rows_kernel=False):
     """packed: hip/bank.py::PackedConv of the three projections (one launch each way) or None (three); window None: no
-    relative positions (emb_k / emb_v ignored); scale None: 1/sqrt(head width)"""
+    relative positions (emb_k / emb_v ignored); scale None: 1/sqrt(head width); rows_kernel: the feature extractors' opt-in
+    to evt_mha_rows_f32 where `attn_rows_route` allows it"""
     slots = (packed._slot,) if packed is not None and packed._slot is not None else (conv_q._slot, conv_k._slot, conv_v._slot)
     if any(s is None for s in slots):
         raise L.EvtError("rel_self_attention before WeightBank.attach(); there is no eager fallback")
     if scale is None:
         scale = (conv_q.cout // n_heads) ** -0.5
+    if rows_kernel and attn_rows_route(x.dtype, window, p, conv_q.cout // n_heads, torch.is_grad_enabled()):
+        return _self_attention_rows(x, slots, lens, int(n_heads), float(scale))
     return RelSelfAttnFn.apply(x, slots[0].bank.anchor, emb_k, emb_v, lens, slots, int(n_heads), window, float(p),
                                int(site), float(scale))
 

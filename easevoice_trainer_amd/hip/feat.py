@@ -1,5 +1,8 @@
-"""Bindings of the feature extractors' own launches (csrc/feat_ops.hip, csrc/pos_conv.hip, csrc/semantic.hip) and the
-LayerNorm entry point they share with the s1 blocks.  Inference only: nothing here records an autograd graph."""
+"""Bindings of the feature extractors' own launches (csrc/feat_ops.hip, csrc/pos_conv.hip, csrc/semantic.hip,
+csrc/mha_rows.hip) and the LayerNorm entry point they share with the s1 blocks.  Inference only: nothing here records an
+autograd graph."""
+import ctypes as C
+
 import torch
 
 from . import lib as L
@@ -266,6 +269,59 @@ def pos_conv_rows(x, lens, image, bias, groups, k, gelu=True):
         L.dt_of(x), x.data_ptr(), None if lens is None else lens.data_ptr(), nseq, T, C, int(groups), int(k),
         image.data_ptr(), None if bias is None else bias.data_ptr(), 1 if gelu else 0, out.data_ptr(), L.stream_ptr()),
         "evt_pos_conv_rows")
+    return out
+
+
+MHA_ROWS_QUERY_TILE = 64  # EVT_MHA_ROWS_QUERY_TILE: queries per block, counted from a row's query 0
+MHA_ROWS_KEY_TILE = 32    # EVT_MHA_ROWS_KEY_TILE: keys per step of the online softmax, counted from a row's key 0
+MHA_ROWS_D = (32, 64)
+
+
+def _mha_rows_operand(name, t, B):
+    """a strided fp32 view [B, T, >= H * D] the C ABI can address: unit channel stride, rows a 16-byte multiple apart,
+    item b at b * T rows"""
+    if (not torch.is_tensor(t) or t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or t.size(0) != B or t.size(1) < 1
+            or t.stride(2) != 1 or (B > 1 and t.stride(0) != t.size(1) * t.stride(1))):
+        raise L.EvtError(f"mha_rows_f32: {name} must be a float32 [B, T, H * D] view on the GPU with unit channel stride and "
+                         "items T rows apart")
+    if t.stride(1) % 4 or t.data_ptr() % 16:
+        raise L.EvtError(f"mha_rows_f32: {name} rows must be 16-byte aligned and a 16-byte multiple apart")
+
+
+def mha_rows_f32(q, k, v, lens_q, lens_k, n_heads, scale):
+    """q [B, Tq, H * D], k / v [B, Tk, H * D]: strided float32 views (slices of one packed [q | k | v] projection or three
+    planes; k and v with one row stride), lens_q / lens_k int32 [B] on the GPU or None (all rows live) -> contiguous
+    [B, Tq, H * D]: softmax(scale * q k^T) v per head over each item's live keys, zeros for the query rows at or behind
+    lens_q[b] and for items without a live key.  ONE launch of evt_mha_rows_f32 (include/evt.h has the definition): fp32
+    MFMA, D in MHA_ROWS_D, nothing at or behind a row's length read, a row bit for bit as it comes out alone."""
+    if not torch.is_tensor(q) or q.dim() != 3:
+        raise L.EvtError("mha_rows_f32: q [B, Tq, H * D] expected")
+    B, Tq, Cc = q.shape
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _mha_rows_operand(name, t, B)
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise L.EvtError("mha_rows_f32 is inference only: run it under torch.no_grad()")
+    n_heads = int(n_heads)
+    D = Cc // n_heads if n_heads > 0 and Cc % n_heads == 0 else 0
+    if D not in MHA_ROWS_D or k.size(2) != Cc or v.shape != k.shape or v.stride(1) != k.stride(1) or B > 65535:
+        raise L.EvtError(f"mha_rows_f32: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} with {n_heads} heads are not "
+                         f"served (head width in {MHA_ROWS_D}, k and v alike)")
+    if lens_q is not None:
+        L.check_lens("mha_rows_f32", q, lens_q)
+    if lens_k is not None:
+        L.check_lens("mha_rows_f32", k, lens_k)
+    return mha_rows_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), lens_q, lens_k, B, Tq, k.size(1), n_heads, D, q.stride(1),
+                           k.stride(1), scale, q.device)
+
+
+def mha_rows_launch(qp, kp, vp, lens_q, lens_k, B, Tq, Tk, n_heads, D, ldq, ldk, scale, device):
+    """the launch of `mha_rows_f32` on device addresses whose shapes the caller has established (hip/enc.py's route on the
+    projection buffer it has just written): the output's allocation and the call, nothing else on the host"""
+    out = torch.empty(B, Tq, n_heads * D, dtype=torch.float32, device=device)
+    prm = L.MhaParams(L.DT_F32, B, n_heads, D, Tq, Tk, -1, 1, ldq, ldk, n_heads * D, float(scale), 0.0, 0, 0, None)
+    L.check(L.lib().evt_mha_rows_f32(
+        C.byref(prm), qp, kp, vp, None if lens_q is None else lens_q.data_ptr(), None if lens_k is None else lens_k.data_ptr(),
+        out.data_ptr(), L.stream_ptr()), "evt_mha_rows_f32")
     return out
 
 

@@ -896,6 +896,26 @@ int evt_mha_fwd(const evt_mha_params* p, const void* q, const void* k, const voi
 int evt_mha_bwd(const evt_mha_params* p, const void* q, const void* k, const void* v, const void* o, const void* d_o,
                 const float* lse, const float* emb_k, const float* emb_v, const int32_t* lens_q, const int32_t* lens_k,
                 void* dq, void* dk, void* dv, float* demb_k, float* demb_v, float* delta_ws, void* stream);
+/* The fp32 attention core of the feature extractors (HuBERT's and BERT's self-attention, which the reference runs in
+ * float32) on RAGGED rows, forward only, ONE launch on mfma_f32_16x16x4f32 (true fp32 products; csrc/mha_rows.hip):
+ *   out[b][i][h D + d] = sum_{j < lens_k[b]} softmax_j(scale * q_i . k_j) v_j[d]      i <  lens_q[b]
+ *   out[b][i][:]       = 0                                                            lens_q[b] <= i < Tq, or lens_k[b] == 0
+ * Of evt_mha_params it reads dtype (EVT_DT_F32), B, H, D (32 or 64), Tq, Tk, ldq, ldk, ldo, scale; window must be < 0 and
+ * dropout_p 0.  q, k, v, out are row-strided as for evt_mha_fwd (slices of one packed [q | k | v] projection or three
+ * planes; Tq != Tk with their own lengths is cross-attention).  lens_q / lens_k device int32 [B] (clamped to 0 .. Tq / Tk)
+ * or NULL (= all rows live).  Every element of out is written; q, k and v are never read at or behind a row's length
+ * (dead key rows are zeros in LDS and their scores -inf by a select, so NaN there changes no bit).
+ * Summation order: a block owns EVT_MHA_ROWS_QUERY_TILE queries of one (b, h) counted from the row's query 0 and walks the
+ * key tiles of EVT_MHA_ROWS_KEY_TILE keys in ascending order from key 0, online softmax in fp32 (exp2 with log2(e) folded
+ * into the scale).  Neither B, Tq nor Tk enters: a row's live queries are bit for bit those of B = 1 with Tq = lens_q[b],
+ * Tk = lens_k[b].  No workspace, no host synchronisation: legal in a captured graph.
+ * EVT_EINVAL (nothing launched) for a NULL pointer other than lens_q / lens_k, dtype != EVT_DT_F32, window >= 0,
+ * dropout_p != 0, D outside {32, 64}, B, H, Tq or Tk <= 0, B or H > 65535, a stride below H * D or not a 16-byte multiple,
+ * q, k, v or out not 16-byte aligned, scale <= 0 or NaN. */
+#define EVT_MHA_ROWS_QUERY_TILE 64
+#define EVT_MHA_ROWS_KEY_TILE 32
+int evt_mha_rows_f32(const evt_mha_params* p, const void* q, const void* k, const void* v, const int32_t* lens_q,
+                     const int32_t* lens_k, void* out, void* stream);
 
 /* Cross-entropy, reduction="sum" (t2s_model.py:486-489): logits [rows][V] (any dtype), targets int64.
  * loss[0] += sum_r (lse_r - logit[r][t_r]); dlogits = (softmax - onehot) * dloss[0]; top-k hit counts for
