@@ -17,6 +17,9 @@ state_dict loads as is (`load_hf_state_dict`); channels-last [B, T, C] rows; eve
   12 encoder layers   packed q | k | v projection + attention core (hip/enc.py::rel_self_attention, window None: in
                       float32 evt_mha_rows_f32, the fp32 MFMA flash kernel; in 16 bit evt_mha_fwd), out projection, LayerNorm(x + attn), Linear 768 -> 3072, GELU, Linear 3072 -> 768,
                       LayerNorm(x + ffn)
+In float32 the six strided convolutions behind the first (with their GELU) and every Linear run on evt_gemm_rows_f32
+(csrc/gemm_rows.hip, hip/enc.py::gemm_rows_route: a convolution without padding is a GEMM on overlapping rows of the
+channels-last buffer); the 16-bit passes keep evt_conv1d_fwd and evt_gelu_rows_fwd.
 A RAGGED batch of clips goes through `HubertModel.forward_rows` (`CNHubert.last_hidden_state_batch` / `.batch`): the first
 convolution, its GroupNorm over each row's own frames and GELU in evt_hubert_front_rows, tails zeroed in front of the
 positional convolution, frame counts as key lengths -- row b is what the clip gives alone.
@@ -28,8 +31,9 @@ from torch import nn
 
 from ..hip import lib as L
 from ..hip.conv import EvtConv1d, mask_tail
-from ..hip.enc import new_site, rel_self_attention
-from ..hip.feat import add_layernorm, channel_norm_gelu, gelu_rows, hubert_front_rows, pos_conv_image, pos_conv_rows
+from ..hip.enc import dense_rows, gemm_rows_route, new_site, rel_self_attention
+from ..hip.feat import (GEMM_ROWS_ACT_GELU, add_layernorm, channel_norm_gelu, conv_rows_weight, gelu_rows, gemm_rows_launch,
+                        hubert_front_rows, pos_conv_image, pos_conv_rows)
 from ..module.attentions import linear_rows
 from ..runtime import ModelRuntime
 
@@ -59,8 +63,24 @@ class _ConvLayer(nn.Module):
         super().__init__()
         self.conv = EvtConv1d(cin, cout, k, stride=stride, bias=False)
         self.layer_norm = _LN(cout, 1e-5) if group_norm else None
+        self._rows_w = None
 
-    def forward(self, x):
+    def forward(self, x, lens=None):
+        """x [B, T, cin] (+ the frame counts int32 [B] this layer leaves of a ragged batch).  The layers without a norm run,
+        where `gemm_rows_route` allows, as ONE launch of evt_gemm_rows_f32 with GELU fused: the im2col row of a frame is
+        the run of k * cin floats at frame * stride * cin of the channels-last input, the weight [cout, k * cin] tap-major
+        is permuted once and again when the parameter was replaced or written (torch's version counter, as _PosConv)"""
+        c = self.conv
+        if self.layer_norm is None and x.dim() == 3 and x.size(1) >= c.k and gemm_rows_route(
+                x.dtype, c.cout, c.k * c.cin, c.stride * c.cin, torch.is_grad_enabled()):
+            w = c.weight
+            stamp = (w.data_ptr(), w._version)
+            if self._rows_w is None or self._rows_w[0] != stamp:
+                self._rows_w = (stamp, conv_rows_weight(w))
+            x = x.contiguous()
+            B, T, cin = x.shape
+            return gemm_rows_launch(x.data_ptr(), lens, self._rows_w[1].data_ptr(), None, B, c.lout(T), c.cout, c.k * cin,
+                                    T * cin, c.stride * cin, GEMM_ROWS_ACT_GELU, x.device)
         y = self.conv(x)
         if self.layer_norm is not None:
             return channel_norm_gelu(y, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
@@ -87,7 +107,7 @@ class _FeatureProjection(nn.Module):
         self.projection = linear_rows(cin, hidden)
 
     def forward(self, x):
-        return self.projection(self.layer_norm(x))
+        return dense_rows(self.projection, self.layer_norm(x))
 
 
 class _PosConv(nn.Module):
@@ -125,7 +145,7 @@ class _Attention(nn.Module):
     def forward(self, x, lens):
         o = rel_self_attention(x, self.q_proj, self.k_proj, self.v_proj, None, None, lens, self.num_heads, None, 0.0,
                                self._site, rows_kernel=True)
-        return self.out_proj(o)
+        return dense_rows(self.out_proj, o)
 
 
 class _FeedForward(nn.Module):
@@ -135,7 +155,7 @@ class _FeedForward(nn.Module):
         self.output_dense = linear_rows(inner, hidden)
 
     def forward(self, x):
-        return self.output_dense(gelu_rows(self.intermediate_dense(x)))
+        return dense_rows(self.output_dense, dense_rows(self.intermediate_dense, x, gelu=True))
 
 
 class _EncoderLayer(nn.Module):
@@ -246,8 +266,9 @@ class HubertModel(nn.Module):
         first = self.feature_extractor.conv_layers[0]
         x = hubert_front_rows(wav, lens, first.conv.weight.data.view(CONV_DIM[0], CONV_KERNEL[0]), first.layer_norm.weight.data,
                               first.layer_norm.bias.data, first.layer_norm.eps, rt.dtype)
-        for layer in self.feature_extractor.conv_layers[1:]:
-            x = layer(x)
+        per_layer = torch.tensor([self.layer_frames(n) for n in n_samples], dtype=torch.int32).t().contiguous().to(rt.device)
+        for i, layer in enumerate(self.feature_extractor.conv_layers[1:], 1):
+            x = layer(x, per_layer[i])             # each layer's own frame counts: nothing behind a row's frames is read
         x = self.feature_projection(x)
         frame_lens = [self.layer_frames(n)[-1] for n in n_samples]
         flens = torch.tensor(frame_lens, dtype=torch.int32).to(rt.device)

@@ -11,7 +11,8 @@ The encoder is restated module for module with the checkpoint's parameter names 
 layers above the one that is read are not built.  Rows are [B, T, C]; per layer: three 1x1-convolution projections + the
 attention core (hip/enc.py::rel_self_attention, window None, key padding by lengths; in float32 the core is
 evt_mha_rows_f32, the fp32 MFMA flash kernel), the output projection,
-LayerNorm(x + attn) (evt_add_layernorm_fwd), Linear -> GELU (evt_gelu_rows_fwd) -> Linear, LayerNorm(x + ffn).  The
+LayerNorm(x + attn) (evt_add_layernorm_fwd), Linear -> GELU (evt_gelu_rows_fwd) -> Linear, LayerNorm(x + ffn); in float32
+every Linear is one launch of evt_gemm_rows_f32 (hip/enc.py::dense_rows, the fp32 MFMA GEMM with bias and GELU fused).  The
 embedding sum (word + position + token type) is a gather and its LayerNorm one launch.  Inference only.
 
 Ragged groups of sentences (`BertFeatures.hidden_rows`, `phone_level_features_batch`) run the same layers on right-padded
@@ -23,8 +24,8 @@ import torch
 from torch import nn
 
 from ..hip import lib as L
-from ..hip.enc import new_site, rel_self_attention
-from ..hip.feat import add_layernorm, gelu_rows
+from ..hip.enc import dense_rows, new_site, rel_self_attention
+from ..hip.feat import add_layernorm
 from ..module.attentions import linear_rows
 from ..runtime import ModelRuntime
 
@@ -75,7 +76,7 @@ class _SelfOutput(nn.Module):
         self.LayerNorm = _LayerNorm(hidden, eps)
 
     def forward(self, h, x):
-        return self.LayerNorm(x, self.dense(h))
+        return self.LayerNorm(x, dense_rows(self.dense, h))
 
 
 class _Attention(nn.Module):
@@ -94,7 +95,7 @@ class _Intermediate(nn.Module):
         self.dense = linear_rows(hidden, inner)
 
     def forward(self, x):
-        return gelu_rows(self.dense(x))
+        return dense_rows(self.dense, x, gelu=True)
 
 
 class _Layer(nn.Module):

@@ -8,6 +8,7 @@ import itertools
 
 import torch
 
+from . import feat as HF
 from . import lib as L
 
 _RNG = {}
@@ -316,9 +317,60 @@ def attn_rows_route(dtype, window, p, D, grad_enabled):
     return dtype == torch.float32 and window is None and p == 0 and D in MHA_ROWS_D and not grad_enabled
 
 
+def gemm_rows_route(dtype, N, K, lda, grad_enabled):
+    """whether a dense layer (lda = K) or a strided no-padding convolution (lda = stride * cin, K = k * cin) of the feature
+    extractors runs on evt_gemm_rows_f32 (csrc/gemm_rows.hip, the fp32 MFMA GEMM on overlapping rows with bias and GELU
+    fused): float32, whole 16-wide tiles of N and K, rows a 16-byte multiple apart, and no autograd graph to record (it has
+    no backward).  Everything else stays on evt_conv1d_fwd (+ evt_gelu_rows_fwd).  No threshold on the row count, for the
+    reason `attn_rows_route` gives: the kernel picks its tile from the launch's block count and sums every row in one
+    order, so a clip or sentence gets the same bits alone and in any group -- a threshold here would hand it to two
+    kernels with two summation orders."""
+    return dtype == torch.float32 and HF.gemm_rows_shape(N, K, lda) and not grad_enabled
+
+
+def _rows_operands(m):
+    """(weight address, bias address) of a k = 1 projection module for evt_gemm_rows_f32: the fp32 parameter itself -- an
+    nn.Linear weight [cout, cin] (or a 1x1 convolution's [cout, cin, 1]) is the kernel's [N][K] matrix as stored"""
+    w, b = m.weight.data, (m.bias.data if m.bias is not None else None)
+    if (w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() % 16
+            or (b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.data_ptr() % 16))):
+        raise L.EvtError("dense rows: contiguous, 16-byte aligned float32 parameters expected (ModelRuntime's arena gives them)")
+    return w.data_ptr(), None if b is None else b.data_ptr()
+
+
+def _is_dense(m):
+    return m.k == 1 and m.groups == 1 and not m.transposed and not m.weight_norm and m.cin == m.weight.size(1)
+
+
+def dense_rows(layer, x, gelu=False, out=None):
+    """a `linear_rows` layer of the feature extractors on x [B, T, cin] (+ GELU): where `gemm_rows_route` allows, ONE launch
+    of evt_gemm_rows_f32 on the flat B * T rows with the layer's own fp32 parameters, every row live (values on padded rows
+    stay what the layer makes of them); otherwise the layer's convolution launch and evt_gelu_rows_fwd, as before"""
+    if x.dtype != torch.float32 and out is None:        # the 16-bit passes: nothing but this comparison is added to them
+        y = layer(x)
+        return HF.gelu_rows(y) if gelu else y
+    if (x.dim() == 3 and _is_dense(layer) and x.size(2) == layer.cin
+            and gemm_rows_route(x.dtype, layer.cout, layer.cin, layer.cin, torch.is_grad_enabled())):
+        x = x.contiguous()
+        B, T, K = x.shape
+        wp, bp = _rows_operands(layer)
+        if out is None:
+            out = torch.empty(B, T, layer.cout, dtype=torch.float32, device=x.device)
+        return HF.gemm_rows_launch(x.data_ptr(), None, wp, bp, 1, B * T, layer.cout, K, B * T * K, K,
+                                   HF.GEMM_ROWS_ACT_GELU if gelu else HF.GEMM_ROWS_ACT_NONE, x.device, out=out)
+    if out is not None:
+        from . import conv as HC
+
+        y = HC._fwd(layer._slot, x, None, 1.0, L.ACT_NONE, 1.0, out=out)
+    else:
+        y = layer(x)
+    return HF.gelu_rows(y) if gelu else y
+
+
 def _self_attention_rows(x, slots, lens, n_heads, scale):
-    """the projections exactly as RelSelfAttnFn.forward runs them (one packed GEMM or three launches into the planes of one
-    buffer), the core on evt_mha_rows_f32: no lse, no autograd node"""
+    """the projections as RelSelfAttnFn.forward lays them out (one packed GEMM or three launches into the planes of one
+    buffer; the three through `dense_rows`, i.e. evt_gemm_rows_f32 where `gemm_rows_route` allows), the core on
+    evt_mha_rows_f32: no lse, no autograd node"""
     from . import conv as HC
     from .feat import mha_rows_launch
 
@@ -336,7 +388,7 @@ def _self_attention_rows(x, slots, lens, n_heads, scale):
     else:
         qkv = torch.empty((3, B, T, Cc), dtype=x.dtype, device=x.device)
         for i, s in enumerate(slots):
-            HC._fwd(s, x, None, 1.0, L.ACT_NONE, 1.0, out=qkv[i])
+            dense_rows(s.module, x, out=qkv[i])
         ld, step = Cc, B * T * Cc * x.element_size()
     base = qkv.data_ptr()
     return mha_rows_launch(base, base + step, base + 2 * step, lens, lens, B, T, T, n_heads, Cc // n_heads, ld, ld, scale, x.device)

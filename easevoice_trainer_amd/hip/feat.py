@@ -1,11 +1,12 @@
 """Bindings of the feature extractors' own launches (csrc/feat_ops.hip, csrc/pos_conv.hip, csrc/semantic.hip,
-csrc/mha_rows.hip) and the LayerNorm entry point they share with the s1 blocks.  Inference only: nothing here records an
+csrc/mha_rows.hip, csrc/gemm_rows.hip) and the LayerNorm entry point they share with the s1 blocks.  Inference only: nothing here records an
 autograd graph."""
 import ctypes as C
 
 import torch
 
 from . import lib as L
+from . import trace as T
 
 
 def gelu_rows(x, bias=None, t_out=None):
@@ -322,6 +323,86 @@ def mha_rows_launch(qp, kp, vp, lens_q, lens_k, B, Tq, Tk, n_heads, D, ldq, ldk,
     L.check(L.lib().evt_mha_rows_f32(
         C.byref(prm), qp, kp, vp, None if lens_q is None else lens_q.data_ptr(), None if lens_k is None else lens_k.data_ptr(),
         out.data_ptr(), L.stream_ptr()), "evt_mha_rows_f32")
+    return out
+
+
+GEMM_ROWS_TILE_M = 128    # EVT_GEMM_ROWS_TILE_M: rows per block of the large tile, counted from an item's row 0
+GEMM_ROWS_TILE_N = 128    # EVT_GEMM_ROWS_TILE_N
+GEMM_ROWS_TILE_K = 32     # EVT_GEMM_ROWS_TILE_K: floats of K per LDS chunk
+GEMM_ROWS_ACT_NONE, GEMM_ROWS_ACT_GELU = 0, 1
+
+
+def gemm_rows_shape(N, K, lda):
+    """the shapes evt_gemm_rows_f32 serves (csrc/gemm_rows.hip): whole 16-wide MFMA tiles of columns and of K, rows a
+    16-byte multiple apart"""
+    return N > 0 and K > 0 and lda > 0 and N % 16 == 0 and K % 16 == 0 and lda % 4 == 0
+
+
+def conv_rows_weight(weight):
+    """a convolution weight [cout, cin, k] -> the fp32 matrix [cout, k * cin] evt_gemm_rows_f32 multiplies with the rows
+    of a channels-last buffer: column tap * cin + c (one permute per loaded checkpoint)"""
+    if not torch.is_tensor(weight) or weight.dim() != 3:
+        raise L.EvtError("conv_rows_weight: a convolution weight [cout, cin, k] expected")
+    cout, cin, k = weight.shape
+    return weight.detach().float().permute(0, 2, 1).reshape(cout, k * cin).contiguous()
+
+
+def gemm_rows_f32(x, lens, w, bias, act, rows=None, lda=None, out=None):
+    """x: contiguous float32 items [nseq, ...] on the GPU (item b = the floats x[b]), lens int32 [nseq] on the GPU or None
+    (every row live), w float32 [N, K], bias float32 [N] or None, act GEMM_ROWS_ACT_NONE / _GELU -> [nseq, rows, N]:
+        y[b, m] = act(x[b].flatten()[m * lda: m * lda + K] @ w.T + bias) for m < lens[b], zeros behind,
+    ONE launch of evt_gemm_rows_f32 (include/evt.h has the definition).  lda defaults to K (a dense layer over [nseq, T, K]);
+    for a channels-last [nseq, T, cin] buffer lda = stride * cin with w = conv_rows_weight(weight) is the convolution without
+    padding, rows overlapping.  rows defaults to all that fit an item; out: an optional destination, every element of which
+    is written.  Nothing at or behind row lens[b] of an item is read;
+    a row comes out bit for bit as it does alone."""
+    if not torch.is_tensor(x) or x.dim() < 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise L.EvtError("gemm_rows_f32: contiguous float32 items [nseq, ...] expected")
+    if not torch.is_tensor(w) or w.dim() != 2 or w.dtype != torch.float32 or w.device != x.device or not w.is_contiguous():
+        raise L.EvtError(f"gemm_rows_f32: w must be a contiguous float32 matrix [N, K] on {x.device}")
+    N, K = w.shape
+    nseq, item = x.size(0), x[0].numel()
+    lda = K if lda is None else int(lda)
+    if not gemm_rows_shape(N, K, lda) or item % 4 or not 1 <= nseq <= 65535:
+        raise L.EvtError(f"gemm_rows_f32: {nseq} items of {item} floats, rows {lda} apart, with w {tuple(w.shape)} are not served "
+                         "(N and K multiples of 16, lda and the item multiples of 4, at most 65535 items)")
+    fit = (item - K) // lda + 1 if item >= K else 0
+    rows = fit if rows is None else int(rows)
+    if not 1 <= rows <= fit:
+        raise L.EvtError(f"gemm_rows_f32: {rows} rows of {K} floats, {lda} apart, do not fit an item of {item}")
+    if x.data_ptr() % 16 or w.data_ptr() % 16:
+        raise L.EvtError("gemm_rows_f32: x and w must be 16-byte aligned")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or bias.device != x.device
+                             or bias.numel() != N or not bias.is_contiguous() or bias.data_ptr() % 16):
+        raise L.EvtError(f"gemm_rows_f32: bias must be contiguous, 16-byte aligned float32 [{N}] on {x.device}")
+    if int(act) not in (GEMM_ROWS_ACT_NONE, GEMM_ROWS_ACT_GELU):
+        raise L.EvtError(f"gemm_rows_f32: act {act!r} is neither GEMM_ROWS_ACT_NONE nor GEMM_ROWS_ACT_GELU")
+    if lens is not None:
+        L.check_lens("gemm_rows_f32", x, lens)
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad)):
+        raise L.EvtError("gemm_rows_f32 is inference only: run it under torch.no_grad()")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != x.device
+                            or tuple(out.shape) != (nseq, rows, N) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise L.EvtError(f"gemm_rows_f32: out must be contiguous, 16-byte aligned float32 {(nseq, rows, N)} on {x.device}")
+    if not x.is_cuda:                                   # last: the checks above are the same for tensors anywhere
+        raise L.EvtError("gemm_rows_f32: the items must be on the GPU; there is no CPU path")
+    return gemm_rows_launch(x.data_ptr(), lens, w.data_ptr(), None if bias is None else bias.data_ptr(), nseq, rows, N, K, item,
+                            lda, int(act), x.device, out=out)
+
+
+def gemm_rows_launch(xp, lens, wp, bp, nseq, rows, N, K, x_item, lda, act, device, out=None):
+    """the launch of `gemm_rows_f32` on device addresses whose shapes the caller has established (the extractors' layers on
+    their own parameters): the output's allocation (or `out`, a contiguous float32 [nseq, rows, N] destination such as one
+    plane of a q | k | v buffer) and the call, nothing else on the host"""
+    if out is None:
+        out = torch.empty(nseq, rows, N, dtype=torch.float32, device=device)
+    prm = L.GemmRowsParams(nseq, rows, N, K, x_item, lda, act, 0)
+    e0 = T.t0()
+    L.check(L.lib().evt_gemm_rows_f32(C.byref(prm), xp, None if lens is None else lens.data_ptr(), wp, bp, out.data_ptr(),
+                                      L.stream_ptr()), "evt_gemm_rows_f32")
+    if e0 is not None:                                  # a traced run (hip/trace.py): every row counted as live
+        T.t1(e0, None, "fwd", 2 * nseq * rows * N * K, 4 * (nseq * x_item + N * K + nseq * rows * N),
+             f"rows {K}>{N} lda{lda} n{nseq} L{rows}", None)
     return out
 
 

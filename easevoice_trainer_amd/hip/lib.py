@@ -174,6 +174,12 @@ class MhaParams(C.Structure):
                 ("site", C.c_uint32), ("pad_", C.c_uint32), ("seed_dev", C.c_void_p)]
 
 
+class GemmRowsParams(C.Structure):
+    """evt_gemm_rows_params (include/evt.h)"""
+    _fields_ = [("nseq", C.c_int32), ("rows", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("x_item", C.c_int64),
+                ("lda", C.c_int64), ("act", C.c_int32), ("pad_", C.c_int32)]
+
+
 _libs = {}                   # half dtype -> loaded library
 _half = torch.bfloat16       # the 16-bit type of the library lib() returns
 

@@ -1299,6 +1299,41 @@ int evt_pos_conv_pack(int32_t dtype, const float* w, int32_t C, int32_t G, int32
 int evt_pos_conv_rows(int32_t dtype, const void* x, const int32_t* lens, int32_t nseq, int32_t T, int32_t C, int32_t G,
                       int32_t k, const void* image, const float* bias, int32_t act, void* out, void* stream);
 
+/* The fp32 GEMMs of the feature extractors (the nn.Linear layers of HuBERT and BERT, HuBERT's k = 3 / k = 2, stride 2
+ * convolutions, which the reference runs in float32) on rows that may OVERLAP, forward only, ONE launch on
+ * mfma_f32_16x16x4f32 (true fp32 products; csrc/gemm_rows.hip).  For item b < nseq and row m < rows:
+ *   y[b][m][n] = act(sum_{k < K} x[b * x_item + m * lda + k] * w[n][k] + bias[n])      m <  n_b
+ *   y[b][m][:] = 0                                                                     n_b <= m < rows
+ * with n_b = min(max(lens[b], 0), rows) (lens device int32 [nseq], or NULL: every row live).  x fp32, w fp32 [N][K]
+ * row-major (an nn.Linear weight as stored), bias fp32 [N] or NULL, y fp32 [nseq][rows][N] contiguous; x_item and lda in
+ * floats.  lda = K is a dense layer.  In a channels-last [T][cin] item lda = stride * cin and K = k * cin make row m the
+ * im2col row of a convolution without padding, w its weight [cout][cin][k] permuted to [cout][k * cin] (tap-major): nothing
+ * is staged as im2col, overlapping rows are read twice.  The caller guarantees (rows - 1) * lda + K <= the floats of an item.
+ * Live row m reads exactly its K floats; nothing at or behind row n_b of an item is read (NaN there changes no bit), and
+ * every element of y is written.
+ * Summation order: chunks of EVT_GEMM_ROWS_TILE_K k in ascending order from k = 0, in a chunk two slabs of 16 k, in a slab
+ * four MFMAs of which the j-th takes k = 16 slab + 4 q + j from lane quarter q; then bias, then act, in fp32.  No split-K.
+ * The launch runs on tiles of EVT_GEMM_ROWS_TILE_M x EVT_GEMM_ROWS_TILE_N, or of 64 x 64 when that grid would have fewer
+ * than 256 blocks; both walk K alike, and neither nseq, rows nor the tile enters a sum: a row is bit for bit the row of
+ * nseq = 1 with rows = n_b.  No workspace, no host synchronisation: legal in a captured graph.
+ * EVT_EINVAL (nothing launched) for a NULL pointer other than lens / bias, nseq, rows, N, K or lda <= 0, x_item < 0, x, w, y
+ * or bias not 16-byte aligned; EVT_ENOTSUP for K % 16, N % 16, lda % 4, x_item % 4, nseq > 65535, rows > 64 * 65535 or an
+ * act outside the two below: the caller keeps its old route. */
+#define EVT_GEMM_ROWS_TILE_M 128
+#define EVT_GEMM_ROWS_TILE_N 128
+#define EVT_GEMM_ROWS_TILE_K 32
+#define EVT_GEMM_ROWS_ACT_NONE 0
+#define EVT_GEMM_ROWS_ACT_GELU 1 /* erf form, evt_gelu_rows_fwd's */
+typedef struct evt_gemm_rows_params {
+  int32_t nseq, rows;      /* items; output rows per item */
+  int32_t N, K;            /* output columns; floats per row of x and of w */
+  int64_t x_item, lda;     /* floats between items of x; floats between the starts of consecutive rows of an item */
+  int32_t act;             /* EVT_GEMM_ROWS_ACT_* */
+  int32_t pad_;
+} evt_gemm_rows_params;
+int evt_gemm_rows_f32(const evt_gemm_rows_params* p, const void* x, const int32_t* lens, const void* w, const float* bias,
+                      void* y, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
