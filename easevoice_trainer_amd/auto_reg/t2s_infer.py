@@ -85,8 +85,7 @@ class _Session:
         E, nl, V = model.model_dim, model.num_layers, model.vocab_size
         self.E, self.H, self.nl, self.V = E, model.num_head, nl, V
         z = self._zeros
-        self.kc = z(nl, B, Lmax, E, dt=dtype)
-        self.vc = z(nl, B, Lmax, E, dt=dtype)
+        self._alloc_cache()
         self.xa, self.xb = z(B, E), z(B, E)
         self.qkv, self.att, self.t, self.u = z(B, 3 * E), z(B, E), z(B, E), z(B, E)
         self.hid = z(B, 4 * E)
@@ -97,6 +96,10 @@ class _Session:
 
     def _zeros(self, *s, dt=torch.float32):
         return torch.zeros(*s, dtype=dt, device=self.device)
+
+    def _alloc_cache(self):
+        self.kc = self._zeros(self.nl, self.B, self.Lmax, self.E, dt=self.dtype)
+        self.vc = self._zeros(self.nl, self.B, self.Lmax, self.E, dt=self.dtype)
 
     def _gemv(self, w, bias, a, r, g, b, eps, x_out, y, relu=0):
         N, K = w.shape
@@ -204,6 +207,8 @@ ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 
 
 SAMPLE_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty")
+KV_DTYPES = (None, "mxfp8")      # cache formats of a stream session: the session dtype, or 33 bytes per head row
+MX_BLOCK = 32                    # the head width an MXFP8 cache serves: one scale byte per 32 codes
 
 
 # what decode_stream yields when log-probabilities or several candidates per request were asked for: candidate c of
@@ -232,9 +237,13 @@ class StreamSession(_Session):
     rstate[b] (csrc/s1_decode_stream.hip).  Cache slab of a slot: [0, Xmax) the text, padded and masked by x_lens[b];
     [Xmax, Xmax + ylen[b] + steps) the audio.  All per-row state is device memory, so admitting a text into a free slot
     changes no launch argument; that includes the row's top_k / top_p / temperature / repetition_penalty (row_sample[b]),
-    so the graph is captured once per (vocabulary-level parameters, noise table) and serves every parameter set."""
+    so the graph is captured once per (vocabulary-level parameters, noise table) and serves every parameter set.
+    kv_dtype="mxfp8" (KV_DTYPES) keeps the cache as MXFP8 bytes, head-major (csrc/s1_decode_mx8.hip, the format in
+    include/evt.h): per layer kq / vq uint8 [B][H][Lmax][32] codes and ks / vs uint8 [B][H][Lmax] scales instead of kc / vc,
+    33 bytes per head row whatever the session's dtype (qkv and the attention output are fp32 in every mode)."""
 
-    def __init__(self, model, B, Xmax, Lmax, ymax, dtype, device):
+    def __init__(self, model, B, Xmax, Lmax, ymax, dtype, device, kv_dtype=None):
+        self.kv_dtype = kv_dtype
         super().__init__(model, B, Lmax, ymax, dtype, device)
         self.Xmax = Xmax
         z = self._zeros
@@ -252,11 +261,34 @@ class StreamSession(_Session):
         self.state.zero_()                 # every slot idle
         self.stop.fill_(-1)
 
+    def _alloc_cache(self):
+        if self.kv_dtype is None:
+            return super()._alloc_cache()
+        self.kc = self.vc = None
+        D = self.E // self.H
+        self.kq, self.vq = (self._zeros(self.nl, self.B, self.H, self.Lmax, D, dt=torch.uint8) for _ in range(2))
+        self.ks, self.vs = (self._zeros(self.nl, self.B, self.H, self.Lmax, dt=torch.uint8) for _ in range(2))
+
     # ---- launches ----
     def _attn(self, i):
+        if self.kv_dtype is not None:
+            L.check(L.lib().evt_dec_attn_rows_mx8(L.ptr(self.qkv), L.ptr(self.kq[i]), L.ptr(self.ks[i]), L.ptr(self.vq[i]),
+                                                  L.ptr(self.vs[i]), L.ptr(self.rstate), L.ptr(self.att), self.B, self.H,
+                                                  self.E // self.H, self.Lmax, L.ptr(self.x_lens), self.Xmax,
+                                                  L.stream_ptr()), "evt_dec_attn_rows_mx8")
+            return
         L.check(L.lib().evt_dec_attn_rows(L.dt_of(self.kc), L.ptr(self.qkv), L.ptr(self.kc[i]), L.ptr(self.vc[i]),
                                           L.ptr(self.rstate), L.ptr(self.att), self.B, self.H, self.E // self.H,
                                           self.Lmax, L.ptr(self.x_lens), self.Xmax, L.stream_ptr()), "evt_dec_attn_rows")
+
+    def _pack_prompt(self, i, qkv, kv_map):
+        """keys and values of layer i's prompt pass qkv [k][S][3E] into the MXFP8 cache through the row map
+        (dst_row, src_row, n_pos), int32 device vectors: one launch for K and V and every slot"""
+        dst, src, n_pos = kv_map
+        L.check(L.lib().evt_kv_pack_mx8_rows(L.dt_of(qkv), L.ptr(qkv), L.ptr(dst), L.ptr(src), L.ptr(n_pos),
+                                             L.ptr(self.kq[i]), L.ptr(self.ks[i]), L.ptr(self.vq[i]), L.ptr(self.vs[i]),
+                                             dst.numel(), qkv.size(0), qkv.size(1), self.B, self.H, self.E // self.H,
+                                             self.Lmax, L.stream_ptr()), "evt_kv_pack_mx8_rows")
 
     def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
@@ -468,37 +500,46 @@ class T2SInfer:
         return self._held(lambda Lmax, ymax: DecodeSession(self.model, B, Lmax, ymax, dtype, device),
                           B, Lneed, yneed, dtype, device, lru=B > self.MAX_ROWS)
 
-    def stream_session(self, B, Xmax, Lneed, yneed, dtype, device):
+    def stream_session(self, B, Xmax, Lneed, yneed, dtype, device, kv_dtype=None):
         """the session cache of session(): capacities rounded to 512, stream sessions share the wide-session LRU.  A
         session of more than WIDE_ROWS slots (decode_stream(wide=True)) is refused when its key/value cache,
         2 * layers * B * Lmax * E * itemsize bytes (12.9 GB of bf16 at B = 128, Lmax = 2048), would need more than half
         of the free device memory: before anything is allocated, and with the figures in the message.  Free memory is
         what the device reports plus what torch's allocator holds unused, counted after the least recently used session
-        has made room (a refused session therefore still costs that one; it is made again when asked for)"""
+        has made room (a refused session therefore still costs that one; it is made again when asked for).  With
+        kv_dtype="mxfp8" the cache counts 2 * layers * B * Lmax * H * 33 bytes (6.6 GB at B = 128, Lmax = 2048) and the
+        session is a different entry of the cache from the one without"""
         def admit(Lmax):
             if B <= self.WIDE_ROWS or torch.device(device).type != "cuda":
                 return
             m = self.model
-            need = 2 * m.num_layers * B * Lmax * m.model_dim * torch.empty((), dtype=dtype).element_size()
+            if kv_dtype is None:
+                need = 2 * m.num_layers * B * Lmax * m.model_dim * torch.empty((), dtype=dtype).element_size()
+            else:
+                need = 2 * m.num_layers * B * Lmax * m.num_head * (MX_BLOCK + 1)
             free = (torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device)
                     - torch.cuda.memory_allocated(device))
             if 2 * need > free:
                 raise L.EvtError(f"a stream session of {B} slots and {Lmax} cache positions needs {need} bytes of "
                                  f"key/value cache, more than half of the {free} bytes free on {device}")
 
-        return self._held(lambda Lmax, ymax: StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device),
-                          B, Lneed, yneed, dtype, device, "stream", Xmax, admit=admit)
+        if kv_dtype is None:      # the call and the key that such a session always had
+            return self._held(lambda Lmax, ymax: StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device),
+                              B, Lneed, yneed, dtype, device, "stream", Xmax, admit=admit)
+        return self._held(lambda Lmax, ymax: StreamSession(self.model, B, Xmax, Lmax, ymax, dtype, device, kv_dtype),
+                          B, Lneed, yneed, dtype, device, "stream", Xmax, kv_dtype, admit=admit)
 
     MAX_ROWS = 4        # rows of a session on the kernels of csrc/s1_decode.hip (kMaxB); also the seed group of a row
     WIDE_ROWS = 32      # rows of a wide session (csrc/s1_decode_rows.hip); larger batches run in groups of 32
     WIDE_SESSIONS = 2   # wide sessions kept at once
     STREAM_ROWS = 128   # slots of a stream session opened with wide=True: four row groups of evt_dec_gemm_rows
 
-    def _prompt_pass(self, S, W, xs, berts, prompts, y_lens, x_len, rows, spread=lambda t: t):
+    def _prompt_pass(self, S, W, xs, berts, prompts, y_lens, x_len, rows, spread=lambda t: t, kv_map=None):
         """the prompt pass (t2s_model.py:575-660 / 775-825, T2SBlock.process_prompt) of k texts: xs k id vectors, berts
         k x [1024, n], prompts [k, P] (padded to a common length, y_lens the true ones) or None; every text is padded to
         x_len positions, masked as keys.  The keys/values of the k rows go into rows `rows` of S's cache, through
-        `spread` when one prompt row serves several cache rows.  Returns the activations after the last block
+        `spread` when one prompt row serves several cache rows; into an MXFP8 cache they go through kv_map instead, the
+        same assignment as a device row map (StreamSession._pack_prompt).  Returns the activations after the last block
         [k, x_len + P, E] and the two length vectors on the device."""
         m = self.model
         dev, cd = S.device, S.dtype
@@ -520,8 +561,11 @@ class T2SInfer:
         for i, lyr in enumerate(m.h.layers):
             w = W.layers[i]
             qkv = dense(xy, lyr.self_attn.in_proj_weight)
-            S.kc[i, rows, :src_len] = spread(qkv[..., S.E:2 * S.E])
-            S.vc[i, rows, :src_len] = spread(qkv[..., 2 * S.E:])
+            if kv_map is not None:
+                S._pack_prompt(i, qkv.contiguous(), kv_map)
+            else:
+                S.kc[i, rows, :src_len] = spread(qkv[..., S.E:2 * S.E])
+                S.vc[i, rows, :src_len] = spread(qkv[..., 2 * S.E:])
             o = PrefixLMAttentionFn.apply(qkv, xl, yl, x_len, S.H, 0.0, 0)
             sa = dense(o.contiguous(), lyr.self_attn.out_proj.weight)
             xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
@@ -670,7 +714,7 @@ class T2SInfer:
 
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
                       early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
-                      control=None, n=1, logprobs=False, forced=False, wide=False):
+                      control=None, n=1, logprobs=False, forced=False, wide=False, kv_dtype=None):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
         (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
         content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
@@ -727,9 +771,21 @@ class T2SInfer:
         dimension, and a row's tokens do not depend on the number of slots.  It is asked for, not silently given,
         because the session's cache grows with the slots: 2 * layers * slots * Lmax * E * itemsize bytes, 12.9 GB in
         bf16 and 25.8 GB in fp32 at 128 slots and Lmax = 2048, and WIDE_SESSIONS of them are kept.  A session of more
-        than 32 slots that would need more than half of the free device memory is refused with an EvtError."""
+        than 32 slots that would need more than half of the free device memory is refused with an EvtError.
+
+        kv_dtype="mxfp8" keeps the session's key/value cache in MXFP8 (32 e4m3 codes and one power-of-two scale byte per
+        head row, head-major: csrc/s1_decode_mx8.hip): 33 bytes per head row instead of 64 (bf16) or 128 (fp32), whatever
+        the weights' dtype -- 2 * layers * slots * Lmax * heads * 33 bytes.  Opt-in: the cached keys and values are
+        rounded to 4 significant bits, so the tokens are NOT those of the default cache (a row still is, bit for bit, the
+        row alone, whatever the slots and the other requests).  Needs a head width of 32; any other value than None or
+        "mxfp8" raises EvtError."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
+        if kv_dtype not in KV_DTYPES:
+            raise L.EvtError(f"kv_dtype = {kv_dtype!r} is not one of {KV_DTYPES}")
+        if kv_dtype is not None and self.model.model_dim != MX_BLOCK * self.model.num_head:
+            raise L.EvtError(f"kv_dtype = {kv_dtype!r} needs a head width of {MX_BLOCK}, the model's is "
+                             f"{self.model.model_dim // self.model.num_head}")
         most = self.STREAM_ROWS if wide else self.WIDE_ROWS
         if not 1 <= int(slots) <= most:
             raise L.EvtError(f"slots must be 1..{most}, got {slots}")
@@ -757,16 +813,16 @@ class T2SInfer:
             cap = (int(max_text_len), int(max_prompt_len), parse.cap_steps)
             it = (parse(r, q) for r, q in enumerate(requests))
         return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
-                            max(1, int(poll)), control, logprobs, rich, forced)
+                            max(1, int(poll)), control, logprobs, rich, forced, kv_dtype)
 
-    def score_stream(self, requests, tokens, slots=32, append_eos=False, wide=False, **sampling):
+    def score_stream(self, requests, tokens, slots=32, append_eos=False, wide=False, kv_dtype=None, **sampling):
         """Log-probabilities of GIVEN tokens: request r = (x, bert, prompt[, opt]) is forced over all of tokens[r] (a 1-D
         integer vector; append_eos=True adds EOS behind it), limited to exactly that many steps, with logprobs=True.
         Yields (r, logprobs) in completion order, logprobs fp32 [f, 2]: per given token the model's log-probability and
         the log of the probability the sampler would have drawn it from under the request's sampling values (-inf where
         the sampler cuts the token).  No noise value can change a forced row, so `seed` / `noise` do not matter; the
-        other keywords are decode_stream's.  A thin wrapper over decode_stream: the sequence is scored by the decode
-        steps themselves, one token per step, with the sampler's own arithmetic."""
+        other keywords are decode_stream's (kv_dtype: the session's cache format).  A thin wrapper over decode_stream:
+        the sequence is scored by the decode steps themselves, one token per step, with the sampler's own arithmetic."""
         eos = self.model.EOS
 
         def forced_requests():
@@ -784,7 +840,7 @@ class T2SInfer:
 
         lazy = not isinstance(requests, (list, tuple))
         reqs = forced_requests() if lazy else list(forced_requests())
-        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, **sampling):
+        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, kv_dtype=kv_dtype, **sampling):
             yield o.request, o.logprobs
 
     @staticmethod
@@ -795,7 +851,7 @@ class T2SInfer:
 
     @torch.no_grad()
     def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs=False,
-                     forced=False):
+                     forced=False, kv_dtype=None):
         """session, weights, sampling parameters and the captured step graph; every slot idle"""
         m = self.model
         cd = m.cd
@@ -809,7 +865,7 @@ class T2SInfer:
                 cands, noise = noise.size(2), noise.flatten(1, 2)
             noise_rows = 1 if noise.dim() == 2 else noise.size(1)
             assert noise.size(-1) == m.vocab_size
-        S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev)
+        S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev, kv_dtype)
         S.reset()
         S.lp_on, S.noise_cands, S.force_on = bool(logprobs), cands, bool(forced)
         if S.lp_on and S.logp is None:
@@ -854,8 +910,13 @@ class T2SInfer:
         else:
             src_t = torch.tensor([i for i, _c, _q in per], dtype=torch.long, device=dev)
             spread = lambda t: t[src_t]
+        kv_map = None
+        if S.kv_dtype is not None:      # slot <- prompt row, over the text and the row's own prompt
+            kv_map = tuple(torch.tensor(v, dtype=torch.int32, device=dev)
+                           for v in ([s for sl, _q in batch for s in sl], [i for i, _c, _q in per],
+                                     [Xmax + y_lens[i] for i, _c, _q in per]))
         xy, xl, yl = self._prompt_pass(S, W, [q.x for _s, q in batch], [q.bert for _s, q in batch], pr, y_lens, Xmax,
-                                       slots_t, spread)
+                                       slots_t, spread, kv_map)
         # ---- row state ----
         # noise column: none for a [steps][V] table, the request's for [steps][R][V]; `noise` arrives with a candidate
         # dimension flattened ([steps][R * C][V], _stream_open), C = S.noise_cands: column r * C + c
@@ -888,7 +949,7 @@ class T2SInfer:
         S._sample_embed(W, sp, noise, pe, 0, S.mask)
 
     def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None,
-                logprobs=False, rich=False, forced=False):
+                logprobs=False, rich=False, forced=False, kv_dtype=None):
         G, draws = self.MAX_ROWS, []
 
         def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
@@ -932,7 +993,7 @@ class T2SInfer:
                 dev = batch[0][1].x.device
                 if S is None:
                     S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
-                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced)
+                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced, kv_dtype)
                 cuda = torch.device(dev).type == "cuda"
                 if cuda:
                     torch.cuda.synchronize(dev)
@@ -995,7 +1056,7 @@ class T2SInfer:
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
                                        early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,
-                                       poll=8, logprobs=False, wide=False, **kwargs):
+                                       poll=8, logprobs=False, wide=False, kv_dtype=None, **kwargs):
         """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
         the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
         of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths.
@@ -1003,7 +1064,7 @@ class T2SInfer:
         one value per text.  logprobs=True returns (ys, idxs, lps), lps[r] the fp32 [steps, 2] log-probabilities of text
         r as decode_stream hands them out.  `slots` is first clamped to the number of texts (no slot would stay idle),
         then checked by decode_stream: 1..32, with wide=True 1..128 -- so a larger value passes when there are no more
-        texts than that, as slots=33 always did."""
+        texts than that, as slots=33 always did.  kv_dtype: decode_stream's (the session's cache format)."""
         if prompts is None:
             if logprobs:
                 raise L.EvtError("logprobs needs prompts (the refilled session)")
@@ -1026,7 +1087,7 @@ class T2SInfer:
             reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(R)]
         ys, idxs, lps = [None] * len(reqs), [None] * len(reqs), [None] * len(reqs)
         for o in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed, poll=poll,
-                                    logprobs=logprobs, wide=wide, **base):
+                                    logprobs=logprobs, wide=wide, kv_dtype=kv_dtype, **base):
             ys[o[0]], idxs[o[0]] = o[1], o[2]
             if logprobs:
                 lps[o[0]] = o.logprobs

@@ -1034,6 +1034,31 @@ int evt_dec_advance(int32_t* ctr, int32_t dpos, void* stream);
  * evt_dec_attn, so a row equals a one-row evt_dec_attn call at its position bit for bit. */
 int evt_dec_attn_rows(int32_t cdtype, const float* qkv, void* kcache, void* vcache, const int32_t* rstate, float* out,
                       int32_t B, int32_t H, int32_t D, int32_t Lmax, const int32_t* x_lens, int32_t x_len, void* stream);
+/* The MXFP8 key/value cache of a stream session (csrc/s1_decode_mx8.hip), D = 32 only (any other D: EVT_ENOTSUP).  A head
+ * row of 32 values v[0..31], widened exactly to fp32, is stored as 32 code bytes (OCP e4m3fn) and one scale byte s:
+ *   any element NaN or +-Inf:  s = 0xFF, every code 0; every element of the row dequantises to NaN;
+ *   a = max |v_d| == 0:        s = 0, code_d = 0x00 / 0x80 by the sign of v_d;
+ *   otherwise a = m * 2^x with m in [0.5, 1):  e = x - 9 if m <= 0.875 else x - 8 (a * 2^-e lies in (224, 448]), clamped
+ *     to [-127, 127]; s = e + 127; code_d = round-to-nearest-even e4m3fn of v_d * 2^-e, the scaling an exact ldexp.
+ * value = e4m3fn(code_d) * 2^(s - 127), exact in fp32.  Per layer, keys and values each are two buffers, head-major:
+ * codes uint8 [B][H][Lmax][32] and scales uint8 [B][H][Lmax].
+ * evt_kv_pack_mx8_rows writes the keys and values of a prompt pass into such a cache, K and V in one launch.  qkv:
+ * [k][S][3 * H * 32] in dtype (EVT_DT_F32 or the build's 16-bit type), the layer's packed projections.  The row map is
+ * device memory, int32 [n] each: entry m copies positions 0 .. min(n_pos[m], S, Lmax) - 1 of source row src_row[m] to
+ * cache row dst_row[m] (a source may serve several cache rows); an entry with a row outside [0, k) / [0, B) writes
+ * nothing.  No other byte of the four buffers is touched. */
+int evt_kv_pack_mx8_rows(int32_t dtype, const void* qkv, const int32_t* dst_row, const int32_t* src_row,
+                         const int32_t* n_pos, uint8_t* kcodes, uint8_t* kscales, uint8_t* vcodes, uint8_t* vscales,
+                         int32_t n, int32_t k, int32_t S, int32_t B, int32_t H, int32_t D, int32_t Lmax, void* stream);
+/* evt_dec_attn_rows on that cache (no cdtype: qkv and out are fp32, the cache is bytes): a RUNNING row with POS in
+ * [0, Lmax) quantises its new key and value, appends codes and scale bytes at POS, and attends over positions 0..POS
+ * except the padding x_lens[b] <= j < x_len, the new token taking part as its DEQUANTISED value; every other row is
+ * skipped, cache and out[b] untouched.  All sums are fp32 in an order fixed by the row's own POS, so a row's output and
+ * appended bytes are those of the row alone.  A head row with scale byte 0xFF among the attended keys or values makes
+ * that head's 32 outputs NaN.  Lmax * 4 bytes of LDS hold the scores: Lmax > 10240 is EVT_ENOTSUP. */
+int evt_dec_attn_rows_mx8(const float* qkv, uint8_t* kcodes, uint8_t* kscales, uint8_t* vcodes, uint8_t* vscales,
+                          const int32_t* rstate, float* out, int32_t B, int32_t H, int32_t D, int32_t Lmax,
+                          const int32_t* x_lens, int32_t x_len, void* stream);
 /* One launch for the end of a step of all B rows: the sampling of evt_dec_sample_rows with IDX / YCOUNT / YLEN of the
  * row (no_eos_steps against the row's own IDX; built-in noise keyed by row_seed[b] and the row's IDX; an injected table
  * read at [IDX][rstate[b][NOISE]]), the append to y[b], x[b] = emb[token] * x_scale + alpha[0] * pe[YLEN + IDX], and

@@ -21,6 +21,7 @@ admission sections), whose JSON line earlier profiles were recorded with; `--slo
     python tools/bench_s1_decode.py [--tokens 512] [--x-len 96] [--prompt 128] [--dtype bf16] [--rows 4 20 32]
     python tools/bench_s1_decode.py --stream [--stream-n 96]
     python tools/bench_s1_decode.py --stream --stream-n 512 --slots 32 64 96 128      (see run_slots)
+    python tools/bench_s1_decode.py --stream --stream-n 512 --slots 32 64 96 128 --kv-dtype both      (MXFP8 cache alternated)
     python tools/bench_s1_decode.py --stream --mixed 4      (per-request sampling parameters, see run_mixed)
     python tools/bench_s1_decode.py --stream --candidates 4 --logprobs      (see run_candidates)
     python tools/bench_s1_decode.py --stream --force 64      (forced first tokens of every request, see run_force)
@@ -223,45 +224,71 @@ def run_slots(args, m, dev, x, bert, prompts):
     lives, xs, berts, pr, noise, kw, _g = _stream_workload(args, dev, x, bert, prompts)
     N, poll = args.stream_n, kw["poll"]
     infer = m._infer()
-    infer.WIDE_SESSIONS = max(infer.WIDE_SESSIONS, len(args.slots))
+    # --kv-dtype: the session's cache format; "both" alternates the session dtype's cache and the MXFP8 cache in every pass
+    kvs = {"none": [None], "mxfp8": ["mxfp8"], "both": [None, "mxfp8"]}[args.kv_dtype]
+    infer.WIDE_SESSIONS = max(infer.WIDE_SESSIONS, len(args.slots) * len(kvs))
     reqs = [(xs[r], berts[r], pr[r]) for r in range(N)]
     useful = sum(lives)
-    runs, first = {S: [] for S in args.slots}, None
-    identical = True
+    runs, first = {(kv, S): [] for kv in kvs for S in args.slots}, {}
+    identical, cache_bytes = True, {}
     for rep in range(args.reps + 1):
-        for S in args.slots:                   # alternated: every slot count sees the same state of the device
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            ys = [None] * N
-            for r, y, _i in m.decode_stream(reqs, slots=S, wide=S > 32, noise=noise, **kw):
-                ys[r] = y
-            torch.cuda.synchronize()
-            t = time.perf_counter() - t0
-            st = infer.stream_stats
-            assert [y.numel() for y in ys] == [args.prompt + s for s in lives], S
-            if first is None:
-                first = ys
-            elif not all(torch.equal(a, b) for a, b in zip(first, ys)):
-                identical = False
-            runs[S].append(dict(seconds=t, steps=st["steps"], prefill_s=sum(st["prefill_s"]), admissions=st["admissions"],
-                                captured=bool(st["graph_captured"])))
-    out = {}
-    for S, v in runs.items():
+        for S in args.slots:                   # alternated: every slot count and cache sees the same state of the device
+            for kv in kvs:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ys = [None] * N
+                for r, y, _i in m.decode_stream(reqs, slots=S, wide=S > 32, noise=noise, kv_dtype=kv, **kw):
+                    ys[r] = y
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+                st = infer.stream_stats
+                assert [y.numel() for y in ys] == [args.prompt + s for s in lives], (S, kv)
+                if kv not in first:
+                    first[kv] = ys
+                elif not all(torch.equal(a, b) for a, b in zip(first[kv], ys)):
+                    identical = False
+                sess = infer._sessions[infer._wide[-1]]
+                cache_bytes[kv, S] = sum(b.numel() * b.element_size() for b in
+                                         ((sess.kc, sess.vc) if kv is None else (sess.kq, sess.ks, sess.vq, sess.vs)))
+                runs[kv, S].append(dict(seconds=t, steps=st["steps"], prefill_s=sum(st["prefill_s"]),
+                                        admissions=st["admissions"], captured=bool(st["graph_captured"])))
+    outs = {kv: {} for kv in kvs}
+    for (kv, S), v in runs.items():
         timed = v[1:]
         med = sorted(timed, key=lambda e: e["seconds"])[len(timed) // 2]
         t, pre = med["seconds"], med["prefill_s"]
-        out[str(S)] = dict(seconds=round(t, 4), steps=med["steps"], useful_tokens=useful,
-                           tokens_per_s=round(useful / t, 1), us_per_step=round(1e6 * (t - pre) / med["steps"], 1),
-                           admissions=med["admissions"], prefill_share=round(pre / t, 4),
-                           seconds_all_runs=[round(e["seconds"], 4) for e in timed],
-                           graph_captures_timed_passes=sum(e["captured"] for e in timed))
-    base = out[str(args.slots[0])]["tokens_per_s"]
-    for S in args.slots[1:]:
-        out[str(S)]["tokens_per_s_over_first"] = round(out[str(S)]["tokens_per_s"] / base, 3)
+        outs[kv][str(S)] = dict(seconds=round(t, 4), steps=med["steps"], useful_tokens=useful,
+                                tokens_per_s=round(useful / t, 1), us_per_step=round(1e6 * (t - pre) / med["steps"], 1),
+                                admissions=med["admissions"], prefill_share=round(pre / t, 4),
+                                seconds_all_runs=[round(e["seconds"], 4) for e in timed],
+                                graph_captures_timed_passes=sum(e["captured"] for e in timed))
+        if args.kv_dtype != "none":
+            outs[kv][str(S)]["cache_bytes"] = cache_bytes[kv, S]
+    for out in outs.values():
+        base = out[str(args.slots[0])]["tokens_per_s"]
+        for S in args.slots[1:]:
+            out[str(S)]["tokens_per_s_over_first"] = round(out[str(S)]["tokens_per_s"] / base, 3)
+    extra = {} if args.kv_dtype == "none" else dict(kv_dtype=args.kv_dtype)
+    if len(kvs) == 2:
+        extra["slots_mxfp8"] = outs["mxfp8"]
+        for S in args.slots:
+            outs["mxfp8"][str(S)]["tokens_per_s_over_16bit"] = round(outs["mxfp8"][str(S)]["tokens_per_s"]
+                                                                     / outs[None][str(S)]["tokens_per_s"], 3)
+        extra["texts_with_the_16bit_cache_tokens"] = sum(torch.equal(a, b) for a, b in zip(first[None], first["mxfp8"]))
+        # the model's log-probabilities of the 16-bit cache's own tokens under both caches (score_stream), first 64 texts
+        n = min(N, 64)
+        toks = [first[None][r][args.prompt:].cpu() for r in range(n)]
+        lp = {kv: dict(m.score_stream(reqs[:n], toks, slots=32, kv_dtype=kv, top_k=kw["top_k"], top_p=kw["top_p"],
+                                      repetition_penalty=kw["repetition_penalty"])) for kv in kvs}
+        d = torch.cat([(lp["mxfp8"][r][:, 0] - lp[None][r][:, 0]).abs().cpu() for r in range(n)])
+        extra["model_logprob_abs_delta"] = dict(texts=n, tokens=d.numel(), mean=round(float(d.mean()), 5),
+                                                max=round(float(d.max()), 5))
+        extra["note"] = ("random-init model: no claim about trained checkpoints or audio quality is made")
     print(json.dumps(dict(workload=f"s1 decode stream, {N} texts living 64..512 steps, x_len<={args.x_len}, "
                                    f"prompt={args.prompt}, {args.dtype}, poll {poll}, slots {args.slots} alternated, "
                                    f"median of {args.reps}; us_per_step excludes the prompt passes, prefill_share is "
-                                   "their share of the seconds", identical_tokens=identical, slots=out)), flush=True)
+                                   "their share of the seconds", identical_tokens=identical, slots=outs[kvs[0]], **extra)),
+          flush=True)
     assert identical, "the slot counts did not produce identical tokens"
 
 
@@ -377,6 +404,10 @@ def main():
                     help="with --stream: the refilled session alone at each of these slot counts (1..128, wide=True above "
                          "32), alternated, with identical tokens asserted (nothing else); default: the comparison with "
                          "infer_panel_batch_infer at 32 slots")
+    ap.add_argument("--kv-dtype", default="none", choices=["none", "mxfp8", "both"],
+                    help="with --stream --slots: the sessions' cache format (decode_stream's kv_dtype); both = the session "
+                         "dtype's cache and the MXFP8 cache alternated in every pass, with the cache bytes, the texts that "
+                         "decode to the same tokens and |delta log-prob| of score_stream under both")
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="with --stream: request r samples with parameter set r %% N; one session holding all sets "
                          "against N uniform streams run one after the other (nothing else)")
