@@ -27,7 +27,8 @@ The reference reads two device scalars per token (the EOS tests of :846) and rea
 How the module is laid out: _Session owns what every session has -- the buffers, the launch chain of a token step and the
 capture of its graph; DecodeSession (shared counters) and StreamSession (per-row counters) add their state, their attention
 and their end-of-step launch.  T2SInfer has ONE prompt pass (_prompt_pass: _decode runs it for all rows of a call, _admit
-for the slots of an admission) and ONE session cache (_held, behind session / stream_session).  A request of a stream is
+for the slots of an admission; a stream opened with prompt_pass="packed" admits through _prompt_pass_packed, the same pass on an
+unpadded token axis) and ONE session cache (_held, behind session / stream_session).  A request of a stream is
 parsed once, by _RequestParser, into a Request record that _fits, _stream and _admit read by field name."""
 import collections
 import ctypes as C
@@ -209,6 +210,27 @@ ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 SAMPLE_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty")
 KV_DTYPES = (None, "mxfp8")      # cache formats of a stream session: the session dtype, or 33 bytes per head row
 MX_BLOCK = 32                    # the head width an MXFP8 cache serves: one scale byte per 32 codes
+PROMPT_PASSES = (None, "packed")  # prompt passes of a stream session: the padded rectangle, or the packed token axis
+PACKED_QUERY_TILE = 64           # EVT_ATTN_PACKED_QUERY_TILE: queries per block, counted from a sequence's own row 0
+KV_FMT_SLAB, KV_FMT_MX8 = 0, 1   # EVT_KV_FMT_*
+
+
+def packed_layout(x_lens, y_lens, slots):
+    """The descriptors of one packed prompt pass (csrc/attn_packed.hip), lists of ints in, lists of ints out: sequence s has
+    x_lens[s] text rows, then y_lens[s] prompt rows, and feeds the cache slots slots[s] (a list).  Returns
+    (tok0, tiles, dst_off, dst_slot): tok0[s] the sequence's first packed row (the rows follow each other without padding);
+    tiles the flattened [nt][2] list of (sequence, first local query), one tile per PACKED_QUERY_TILE rows counted from the
+    sequence's own row 0, so that a sequence has the same tiles in any pack; dst_off [k + 1] / dst_slot the CSR row map
+    sequence -> slots.  The total number of rows is tok0[-1] + x_lens[-1] + y_lens[-1]."""
+    tok0, tiles, dst_off, dst_slot, t = [], [], [0], [], 0
+    for s, (xl, yl, sl) in enumerate(zip(x_lens, y_lens, slots)):
+        tok0.append(t)
+        for q0 in range(0, xl + yl, PACKED_QUERY_TILE):
+            tiles += [s, q0]
+        dst_slot += [int(v) for v in sl]
+        dst_off.append(len(dst_slot))
+        t += xl + yl
+    return tok0, tiles, dst_off, dst_slot
 
 
 # what decode_stream yields when log-probabilities or several candidates per request were asked for: candidate c of
@@ -256,6 +278,7 @@ class StreamSession(_Session):
         self.logp, self.lp_on = None, False                       # [B][ymax][2] of a logprobs=True stream, made on demand
         self.force_on = False                                     # a stream with forced requests: the _f sampler launch
         self.noise_cands = 1                                      # C of an injected [steps][R][C][V] noise table
+        self.prompt_pass = None                                   # "packed": admissions run T2SInfer._prompt_pass_packed
 
     def reset(self):
         self.state.zero_()                 # every slot idle
@@ -289,6 +312,20 @@ class StreamSession(_Session):
                                              L.ptr(self.kq[i]), L.ptr(self.ks[i]), L.ptr(self.vq[i]), L.ptr(self.vs[i]),
                                              dst.numel(), qkv.size(0), qkv.size(1), self.B, self.H, self.E // self.H,
                                              self.Lmax, L.stream_ptr()), "evt_kv_pack_mx8_rows")
+
+    def _attn_packed(self, i, qkv, out, desc, k, nt, n_dst):
+        """layer i of a packed prompt pass: the prefix-LM attention of qkv [T][3E] into out [T][E] and the layer's keys and
+        values into this session's cache, whichever its format, in ONE launch (csrc/attn_packed.hip).  desc: the int32
+        device vectors (tok0, x_lens, y_lens, tiles, dst_off, dst_slot) of packed_layout"""
+        if self.kv_dtype is None:
+            fmt, cdt, cache = KV_FMT_SLAB, L.dt_of(self.kc), (self.kc[i], self.vc[i], None, None)
+        else:
+            fmt, cdt, cache = KV_FMT_MX8, 0, (self.kq[i], self.vq[i], self.ks[i], self.vs[i])
+        tok0, xl, yl, tiles, dst_off, dst_slot = desc
+        L.check(L.lib().evt_attn_prefixlm_packed_fwd(
+            L.dt_of(qkv), L.ptr(qkv), L.ptr(out), L.ptr(tok0), L.ptr(xl), L.ptr(yl), L.ptr(tiles), L.ptr(dst_off),
+            L.ptr(dst_slot), fmt, cdt, L.ptr(cache[0]), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cache[3]), qkv.size(0), k, nt,
+            n_dst, self.H, self.E // self.H, self.B, self.Lmax, self.Xmax, L.stream_ptr()), "evt_attn_prefixlm_packed_fwd")
 
     def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
@@ -573,6 +610,46 @@ class T2SInfer:
             xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
         return xy, xl, yl
 
+    def _prompt_pass_packed(self, S, W, xs, berts, prompts, slots):
+        """_prompt_pass of k texts on a PACKED token axis (a stream opened with prompt_pass="packed"): xs, berts as there,
+        prompts k 1-D token vectors of their own lengths, slots[s] the cache slots sequence s fills (its candidates).  The
+        embeddings of every sequence -- its text, then its prompt -- follow each other WITHOUT padding in xy [1][T][E],
+        T = sum of the lengths: the six GEMMs and the two LayerNorms of a layer run over T rows instead of
+        k * (Xmax + longest prompt), and the attention launch (StreamSession._attn_packed) writes the layer's keys and
+        values into the cache of either format itself -- no indexed assignment, no pack launch.  The descriptors come from
+        packed_layout and are uploaded once.  The cache positions x_lens[s] <= j < Xmax of a slot, which _prompt_pass fills
+        with the padding's keys, are left as they were: the step masks them.  Returns the activations of every
+        sequence's last row [k, E] (step 0 reads them) and the text lengths on the device."""
+        m = self.model
+        dev, cd = S.device, S.dtype
+        dense = self.dense(cd, dev)
+        parts, x_lens, y_lens = [], [int(x.numel()) for x in xs], [int(p.numel()) for p in prompts]
+        for x, bert, pr in zip(xs, berts, prompts):
+            x, bert = x.to(dev), bert.to(dev)
+            xe = m.ar_text_embedding(x.unsqueeze(0))
+            xe = xe + dense(bert.transpose(0, 1).unsqueeze(0).to(cd).contiguous(), m.bert_proj.weight).to(xe.dtype)
+            parts.append(m.ar_text_position(xe).squeeze(0))
+            if pr.numel():
+                parts.append(m.ar_audio_position(m.ar_audio_embedding(pr.to(dev).long().unsqueeze(0))).squeeze(0))
+        xy = torch.cat(parts, dim=0).unsqueeze(0).to(cd).contiguous()
+        T = xy.size(1)
+        tok0, tiles, dst_off, dst_slot = packed_layout(x_lens, y_lens, slots)
+        fields = (tok0, x_lens, y_lens, tiles, dst_off, dst_slot or [-1])     # one upload; an empty map keeps a valid pointer
+        flat = torch.tensor([v for f in fields for v in f], dtype=torch.int32).to(dev)
+        desc = flat.split([len(f) for f in fields])
+        k, nt, n_dst = len(xs), len(tiles) // 2, len(dst_slot)
+        for i, lyr in enumerate(m.h.layers):
+            w = W.layers[i]
+            qkv = dense(xy, lyr.self_attn.in_proj_weight).contiguous()
+            o = torch.empty_like(xy)
+            S._attn_packed(i, qkv[0], o[0], desc, k, nt, n_dst)
+            sa = dense(o, lyr.self_attn.out_proj.weight)
+            xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
+            ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
+            xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
+        last = torch.tensor([t + a + b - 1 for t, a, b in zip(tok0, x_lens, y_lens)], dtype=torch.long).to(dev)
+        return xy[0, last], desc[1]
+
     @torch.no_grad()
     def _decode(self, xs, berts, prompts, no_eos_steps, top_k, top_p, early_stop_num, temperature, repetition_penalty,
                 noise=None, seed=None, poll=8):
@@ -714,7 +791,7 @@ class T2SInfer:
 
     def decode_stream(self, requests, slots=32, top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35,
                       early_stop_num=-1, noise=None, seed=None, poll=8, max_text_len=None, max_prompt_len=None,
-                      control=None, n=1, logprobs=False, forced=False, wide=False, kv_dtype=None):
+                      control=None, n=1, logprobs=False, forced=False, wide=False, kv_dtype=None, prompt_pass=None):
         """Continuous batching of infer_panel_batch_infer's decoding.  requests: an iterable of (x, bert, prompt) or
         (x, bert, prompt, opt) -- x a 1-D id vector, bert [1024, n], prompt a 1-D token vector; prompts may differ in
         content and length.  opt is the request's early_stop_num, or a dict with keys out of top_k, top_p, temperature,
@@ -778,13 +855,25 @@ class T2SInfer:
         the weights' dtype -- 2 * layers * slots * Lmax * heads * 33 bytes.  Opt-in: the cached keys and values are
         rounded to 4 significant bits, so the tokens are NOT those of the default cache (a row still is, bit for bit, the
         row alone, whatever the slots and the other requests).  Needs a head width of 32; any other value than None or
-        "mxfp8" raises EvtError."""
+        "mxfp8" raises EvtError.
+
+        prompt_pass="packed" runs every admission's prompt pass on a packed token axis (_prompt_pass_packed,
+        csrc/attn_packed.hip): the texts and prompts of the admitted requests follow each other without padding, so the
+        linear layers and LayerNorms see the live rows only, and the attention launch writes the cache (either format).
+        Opt-in: sums run in another order than in the padded pass, so log-probabilities differ in the last bits (a row
+        still is the row alone).  It composes with every other keyword; needs a head width of 32; any other value than
+        None or "packed" raises EvtError."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
         if kv_dtype not in KV_DTYPES:
             raise L.EvtError(f"kv_dtype = {kv_dtype!r} is not one of {KV_DTYPES}")
         if kv_dtype is not None and self.model.model_dim != MX_BLOCK * self.model.num_head:
             raise L.EvtError(f"kv_dtype = {kv_dtype!r} needs a head width of {MX_BLOCK}, the model's is "
+                             f"{self.model.model_dim // self.model.num_head}")
+        if prompt_pass not in PROMPT_PASSES:
+            raise L.EvtError(f"prompt_pass = {prompt_pass!r} is not one of {PROMPT_PASSES}")
+        if prompt_pass is not None and self.model.model_dim != MX_BLOCK * self.model.num_head:
+            raise L.EvtError(f"prompt_pass = {prompt_pass!r} needs a head width of {MX_BLOCK}, the model's is "
                              f"{self.model.model_dim // self.model.num_head}")
         most = self.STREAM_ROWS if wide else self.WIDE_ROWS
         if not 1 <= int(slots) <= most:
@@ -813,16 +902,18 @@ class T2SInfer:
             cap = (int(max_text_len), int(max_prompt_len), parse.cap_steps)
             it = (parse(r, q) for r, q in enumerate(requests))
         return self._stream(it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed,
-                            max(1, int(poll)), control, logprobs, rich, forced, kv_dtype)
+                            max(1, int(poll)), control, logprobs, rich, forced, kv_dtype, prompt_pass)
 
-    def score_stream(self, requests, tokens, slots=32, append_eos=False, wide=False, kv_dtype=None, **sampling):
+    def score_stream(self, requests, tokens, slots=32, append_eos=False, wide=False, kv_dtype=None, prompt_pass=None,
+                     **sampling):
         """Log-probabilities of GIVEN tokens: request r = (x, bert, prompt[, opt]) is forced over all of tokens[r] (a 1-D
         integer vector; append_eos=True adds EOS behind it), limited to exactly that many steps, with logprobs=True.
         Yields (r, logprobs) in completion order, logprobs fp32 [f, 2]: per given token the model's log-probability and
         the log of the probability the sampler would have drawn it from under the request's sampling values (-inf where
         the sampler cuts the token).  No noise value can change a forced row, so `seed` / `noise` do not matter; the
-        other keywords are decode_stream's (kv_dtype: the session's cache format).  A thin wrapper over decode_stream:
-        the sequence is scored by the decode steps themselves, one token per step, with the sampler's own arithmetic."""
+        other keywords are decode_stream's (kv_dtype: the session's cache format; prompt_pass: its prompt pass).  A thin
+        wrapper over decode_stream: the sequence is scored by the decode steps themselves, one token per step, with the
+        sampler's own arithmetic."""
         eos = self.model.EOS
 
         def forced_requests():
@@ -840,7 +931,8 @@ class T2SInfer:
 
         lazy = not isinstance(requests, (list, tuple))
         reqs = forced_requests() if lazy else list(forced_requests())
-        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, kv_dtype=kv_dtype, **sampling):
+        for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, kv_dtype=kv_dtype,
+                                    prompt_pass=prompt_pass, **sampling):
             yield o.request, o.logprobs
 
     @staticmethod
@@ -851,7 +943,7 @@ class T2SInfer:
 
     @torch.no_grad()
     def _stream_open(self, cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs=False,
-                     forced=False, kv_dtype=None):
+                     forced=False, kv_dtype=None, prompt_pass=None):
         """session, weights, sampling parameters and the captured step graph; every slot idle"""
         m = self.model
         cd = m.cd
@@ -868,6 +960,7 @@ class T2SInfer:
         S = self.stream_session(slots, Xmax, Xmax + Pmax + n_max + 1, Pmax + n_max + 1, cd, dev, kv_dtype)
         S.reset()
         S.lp_on, S.noise_cands, S.force_on = bool(logprobs), cands, bool(forced)
+        S.prompt_pass = prompt_pass      # read by _admit alone: the step graph does not depend on it
         if S.lp_on and S.logp is None:
             S.logp = torch.zeros(S.B, S.ymax, 2, dtype=torch.float32, device=dev)
         sp = L.SampleParams(S.V, m.EOS, int(top_k) if top_k is not None else 0, 1, S.ymax, float(top_p),
@@ -896,7 +989,10 @@ class T2SInfer:
         """batch: [(slots, Request)], `slots` the n slots of the request's candidates in candidate order.  The prompt
         pass for these requests only, ONE row per request (texts padded to Xmax, prompts to the longest of them); each
         row's keys/values go into the cache slabs of all its slots, then the row state of every slot and step 0 for
-        those slots: logits of the last prompt position and a masked sample."""
+        those slots: logits of the last prompt position and a masked sample.  A session whose stream asked for
+        prompt_pass="packed" runs _prompt_pass_packed instead: no padding anywhere, the cache written by the attention
+        launch.  The padded pass writes padding into the slab positions x_lens[b] <= j < Xmax of a slot; the packed one
+        leaves them as they were, which the step allows: it masks exactly those positions."""
         dev = S.device
         Xmax, k = S.Xmax, len(batch)
         y_lens = [int(q.prompt.numel()) for _s, q in batch]
@@ -911,12 +1007,18 @@ class T2SInfer:
             src_t = torch.tensor([i for i, _c, _q in per], dtype=torch.long, device=dev)
             spread = lambda t: t[src_t]
         kv_map = None
-        if S.kv_dtype is not None:      # slot <- prompt row, over the text and the row's own prompt
+        packed = S.prompt_pass == "packed"
+        if S.kv_dtype is not None and not packed:      # slot <- prompt row, over the text and the row's own prompt
             kv_map = tuple(torch.tensor(v, dtype=torch.int32, device=dev)
                            for v in ([s for sl, _q in batch for s in sl], [i for i, _c, _q in per],
                                      [Xmax + y_lens[i] for i, _c, _q in per]))
-        xy, xl, yl = self._prompt_pass(S, W, [q.x for _s, q in batch], [q.bert for _s, q in batch], pr, y_lens, Xmax,
-                                       slots_t, spread, kv_map)
+        if packed:
+            last, xl = self._prompt_pass_packed(S, W, [q.x for _s, q in batch], [q.bert for _s, q in batch],
+                                                [q.prompt for _s, q in batch], [sl for sl, _q in batch])
+        else:
+            xy, xl, yl = self._prompt_pass(S, W, [q.x for _s, q in batch], [q.bert for _s, q in batch], pr, y_lens, Xmax,
+                                           slots_t, spread, kv_map)
+            last = xy[torch.arange(k, device=dev), Xmax + yl.long() - 1]
         # ---- row state ----
         # noise column: none for a [steps][V] table, the request's for [steps][R][V]; `noise` arrives with a candidate
         # dimension flattened ([steps][R * C][V], _stream_open), C = S.noise_cands: column r * C + c
@@ -944,12 +1046,12 @@ class T2SInfer:
         S.mask.zero_()
         S.mask[slots_t] = 1
         # ---- step 0 of the admitted rows (the other rows' xb / logits are dead between two steps) ----
-        S.xb[slots_t] = spread(xy[torch.arange(k, device=dev), Xmax + yl.long() - 1].float())
+        S.xb[slots_t] = spread(last.float())
         S._gemv(W.wpred, None, S.xb, None, None, None, 0.0, None, S.logits)
         S._sample_embed(W, sp, noise, pe, 0, S.mask)
 
     def _stream(self, it, cap, slots, top_k, top_p, temperature, repetition_penalty, noise, seed, poll, control=None,
-                logprobs=False, rich=False, forced=False, kv_dtype=None):
+                logprobs=False, rich=False, forced=False, kv_dtype=None, prompt_pass=None):
         G, draws = self.MAX_ROWS, []
 
         def seeds(r):          # (seed, lane) of request r: group r // 4 seeded seed + 4 * (r // 4), or its own draw
@@ -993,7 +1095,8 @@ class T2SInfer:
                 dev = batch[0][1].x.device
                 if S is None:
                     S, W, sp, pe, noise, use_graph, stats["graph_captured"] = self._stream_open(
-                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced, kv_dtype)
+                        cap, slots, dev, top_k, top_p, temperature, repetition_penalty, noise, logprobs, forced, kv_dtype,
+                        prompt_pass)
                 cuda = torch.device(dev).type == "cuda"
                 if cuda:
                     torch.cuda.synchronize(dev)
@@ -1056,7 +1159,7 @@ class T2SInfer:
 
     def infer_panel_batch_infer_refill(self, x, x_lens, prompts, bert_feature, slots=32, top_k=-100, top_p=100,
                                        early_stop_num=-1, temperature=1.0, repetition_penalty=1.35, noise=None, seed=None,
-                                       poll=8, logprobs=False, wide=False, kv_dtype=None, **kwargs):
+                                       poll=8, logprobs=False, wide=False, kv_dtype=None, prompt_pass=None, **kwargs):
         """infer_panel_batch_infer on a refilled session: the same arguments and the same (ys, idxs) in input order, but
         the texts go through `slots` rows of ONE session, a finished row's slot taking the next text, instead of groups
         of 32 that each wait for their slowest row.  prompts: [R, P] or a list of 1-D token vectors of any lengths.
@@ -1064,7 +1167,8 @@ class T2SInfer:
         one value per text.  logprobs=True returns (ys, idxs, lps), lps[r] the fp32 [steps, 2] log-probabilities of text
         r as decode_stream hands them out.  `slots` is first clamped to the number of texts (no slot would stay idle),
         then checked by decode_stream: 1..32, with wide=True 1..128 -- so a larger value passes when there are no more
-        texts than that, as slots=33 always did.  kv_dtype: decode_stream's (the session's cache format)."""
+        texts than that, as slots=33 always did.  kv_dtype, prompt_pass: decode_stream's (the session's cache format and its
+        prompt pass)."""
         if prompts is None:
             if logprobs:
                 raise L.EvtError("logprobs needs prompts (the refilled session)")
@@ -1087,7 +1191,7 @@ class T2SInfer:
             reqs = [(x[r], bert_feature[r], prompts[r]) for r in range(R)]
         ys, idxs, lps = [None] * len(reqs), [None] * len(reqs), [None] * len(reqs)
         for o in self.decode_stream(reqs, slots=min(int(slots), max(1, len(reqs))), noise=noise, seed=seed, poll=poll,
-                                    logprobs=logprobs, wide=wide, kv_dtype=kv_dtype, **base):
+                                    logprobs=logprobs, wide=wide, kv_dtype=kv_dtype, prompt_pass=prompt_pass, **base):
             ys[o[0]], idxs[o[0]] = o[1], o[2]
             if logprobs:
                 lps[o[0]] = o.logprobs

@@ -15,6 +15,7 @@
 //     dK^T += Q^T dS.  No score tile ever goes through LDS or HBM, nothing is accumulated with atomics.
 // The fp32 kernels (one thread per row) are the parity path: exact-order fp32, no MFMA.
 #include "evt_common.h"
+#include "attn_frag.h"
 #include "../../include/evt.h"
 #include <type_traits>
 
@@ -66,31 +67,10 @@ __device__ __forceinline__ bool visible(int qi, int kj, int x_len, int xl, int y
   return qi < x_len ? (kj < x_len) : (kj <= qi);
 }
 
-// two ds_read_b64_tr_b16 (transposing 16-bit LDS reads) -> one MFMA A fragment.  The builtin (not inline asm) lets the
-// compiler track the LDS counter, so all fragment reads of a key sub-block are in flight behind ONE wait.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ h16x8 tr2(const h16_t* p0, const h16_t* p1) {
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  union { struct { s16x4 lo, hi; } h; h16x8 v; } r;
-  r.h.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
-  r.h.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p1));
-  return r.v;
-}
-
-__device__ __forceinline__ h16x8 pack8(const float* p) {
-  union { h16x8 v; h16_t e[8]; } r;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.e[i] = f2h(p[i]);
-  return r.v;
-}
-
-__device__ __forceinline__ h16x8 ld8(const h16_t* p) { return *reinterpret_cast<const h16x8*>(p); }
+// tr2, pack8, ld8, slot32: attn_frag.h (shared with the packed forward kernel of attn_packed.hip)
 
 constexpr int D = 32;
 constexpr int PITCH = D + 8;   // LDS row pitch in elements (80 B: 16-byte aligned, not a power of two)
-
-// k-slot e of lane group g inside a 32-wide block: e<4 -> g*4+e ; e>=4 -> 16 + g*4 + (e-4)
-__device__ __forceinline__ int slot32(int g, int e) { return e < 4 ? g * 4 + e : 16 + g * 4 + (e - 4); }
 
 // ---------------------------------------------------------------------------------------------------------
 // tile classification (wave-uniform): a 16-query x 32-key (or 32-query x 16-key) tile is

@@ -121,7 +121,7 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
                       top_k=5, top_p=1, temperature=1.0, repetition_penalty=1.35, speed_factor=1.0, slots=32,
                       decode_kwargs=None, sample_kwargs=None, fragment_sampling=None, control=None, candidates=1,
                       choose=None, wide=False, s2_batch=1, fragment_speed=None, out_rate=None, out_format=None,
-                      fragment_style=None, kv_dtype=None):
+                      fragment_style=None, kv_dtype=None, prompt_pass=None):
     """synthesize_fragments handing the fragments out one by one (the model-side core of TTS.run's return_fragment
     mode): a generator of (index, waveform) in the order in which the fragments' semantic tokens are complete.  The
     fragments decode in a refilled s1 session of up to `slots` rows (decode_stream: more fragments than slots wait for a
@@ -163,9 +163,12 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     r.  refer_specs may then be empty; a group goes through decode_batch(refer=None, style=<the group's rows stacked>),
     whose rows may all differ, a fragment decoded alone through decode(refer=None, style=...).
     kv_dtype: None, or "mxfp8" for decode_stream's MXFP8 key/value cache (about half the cache bytes of bf16; the tokens
-    are then not those of the default cache)."""
+    are then not those of the default cache).  prompt_pass: None, or "packed" for decode_stream's packed prompt pass (no
+    padded rows in an admission)."""
     model, dev = t2s.model, t2s.device
-    cache = {} if kv_dtype is None else {"kv_dtype": kv_dtype}      # the keyword reaches decode_stream only when asked for
+    cache = {} if kv_dtype is None else {"kv_dtype": kv_dtype}      # the keywords reach decode_stream only when asked for
+    if prompt_pass is not None:
+        cache["prompt_pass"] = prompt_pass
     out = {k: v for k, v in (("out_rate", out_rate), ("out_format", out_format)) if v is not None}
     s2_batch = int(s2_batch)
     if s2_batch < 1:
@@ -286,14 +289,14 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
 
 
 def synthesize_pcm(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs, out_rate=None,
-                   fragment_interval=0.3, kv_dtype=None, **stream_kwargs):
+                   fragment_interval=0.3, kv_dtype=None, prompt_pass=None, **stream_kwargs):
     """The non-streaming end of TTS.run (tts.py:878-908, audio_postprocess): -> (rate, int16 tensor on the host) holding the
     fragments in INPUT order, int(rate * fragment_interval) zeros behind each (the reference's zero_wav).  out_rate None:
     the model's rate.  It drains synthesize_stream(out_rate=rate, out_format="int16", **stream_kwargs) -- s2_batch, slots,
     fragment_speed, control ... as there --, so conversion and resampling happen on the device, one launch per group;
     fragments that come back cancelled (or preempted) are left out together with their interval.  The pieces are joined
     on the device and leave it in ONE device -> host copy.  fragment_style (one voice per fragment, refer_specs may be
-    empty) goes through as the other stream keywords do; kv_dtype is synthesize_stream's."""
+    empty) goes through as the other stream keywords do; kv_dtype and prompt_pass are synthesize_stream's."""
     rate = int(getattr(voice.model, "sampling_rate", 32000) if out_rate is None else out_rate)
     if fragment_interval < 0:
         raise ValueError(f"fragment_interval = {fragment_interval} must be >= 0")
@@ -302,7 +305,8 @@ def synthesize_pcm(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features,
             raise ValueError(f"synthesize_pcm sets {k} itself")
     got = {}
     for r, wav in synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_features, prompt_semantic, refer_specs,
-                                    out_rate=rate, out_format="int16", kv_dtype=kv_dtype, **stream_kwargs):
+                                    out_rate=rate, out_format="int16", kv_dtype=kv_dtype, prompt_pass=prompt_pass,
+                                    **stream_kwargs):
         if wav is not None:
             got[r] = wav
     if not got:

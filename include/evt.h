@@ -1050,6 +1050,31 @@ int evt_dec_attn_rows(int32_t cdtype, const float* qkv, void* kcache, void* vcac
 int evt_kv_pack_mx8_rows(int32_t dtype, const void* qkv, const int32_t* dst_row, const int32_t* src_row,
                          const int32_t* n_pos, uint8_t* kcodes, uint8_t* kscales, uint8_t* vcodes, uint8_t* vscales,
                          int32_t n, int32_t k, int32_t S, int32_t B, int32_t H, int32_t D, int32_t Lmax, void* stream);
+/* The prefix-LM attention of one layer's prompt pass on a PACKED token axis, forward only (no dropout, no lse), which also
+ * writes the layer's keys and values into a stream session's cache (csrc/attn_packed.hip).  D = 32 only (any other D:
+ * EVT_ENOTSUP).  qkv: [T][3 * H * 32] in dtype (EVT_DT_F32 or the build's 16-bit type), out: [T][H * 32] in dtype.
+ * Sequence s of k owns rows tok0[s] .. tok0[s] + x_lens[s] + y_lens[s] - 1, text rows first, then prompt rows; there is no
+ * padding.  Inside a sequence a text query sees every text key, the audio query at local index i the keys 0 .. i; nothing
+ * is read across a sequence boundary.  tiles: int32 [nt][2] = (sequence, first local query), EVT_ATTN_PACKED_QUERY_TILE
+ * queries each, counted from the sequence's own row 0 -- the grid is (nt, H); a sequence's output and cache bytes are those
+ * of the sequence packed alone.  A local row no tile covers gets no output and no cache write.
+ * Cache: the CSR row map dst_off int32 [k + 1], dst_slot int32 [n_dst] names the slots of sequence s,
+ * dst_slot[dst_off[s] .. dst_off[s + 1]) (offsets are clamped to n_dst).  Local text position i goes to cache position i
+ * (i < Xmax), local audio position i to Xmax + (i - x_lens[s]); a slot outside [0, B) or a position at or behind Lmax writes
+ * nothing, and no other byte of the cache is touched.  cache_fmt EVT_KV_FMT_SLAB: kcache / vcache [B][Lmax][H * 32] in
+ * cdtype, values copied exactly when cdtype == dtype, else converted (fp32 -> 16-bit: round to nearest even); kscales /
+ * vscales are ignored.  EVT_KV_FMT_MX8: the MXFP8 cache above, kcache / vcache the code buffers, kscales / vscales the scale
+ * bytes, the bytes evt_kv_pack_mx8_rows writes for the same values; cdtype is ignored.
+ * All descriptors are device memory, int32; a tile whose sequence, lengths or rows fall outside [0, k) / [0, T) does
+ * nothing.  Every sum is fp32 in an order fixed by the sequence's own lengths. */
+#define EVT_ATTN_PACKED_QUERY_TILE 64
+#define EVT_KV_FMT_SLAB 0
+#define EVT_KV_FMT_MX8 1
+int evt_attn_prefixlm_packed_fwd(int32_t dtype, const void* qkv, void* out, const int32_t* tok0, const int32_t* x_lens,
+                                 const int32_t* y_lens, const int32_t* tiles, const int32_t* dst_off, const int32_t* dst_slot,
+                                 int32_t cache_fmt, int32_t cdtype, void* kcache, void* vcache, uint8_t* kscales,
+                                 uint8_t* vscales, int32_t T, int32_t k, int32_t nt, int32_t n_dst, int32_t H, int32_t D,
+                                 int32_t B, int32_t Lmax, int32_t Xmax, void* stream);
 /* evt_dec_attn_rows on that cache (no cdtype: qkv and out are fp32, the cache is bytes): a RUNNING row with POS in
  * [0, Lmax) quantises its new key and value, appends codes and scale bytes at POS, and attends over positions 0..POS
  * except the padding x_lens[b] <= j < x_len, the new token taking part as its DEQUANTISED value; every other row is

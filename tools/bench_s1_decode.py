@@ -292,6 +292,69 @@ def run_slots(args, m, dev, x, bert, prompts):
     assert identical, "the slot counts did not produce identical tokens"
 
 
+def run_prompt_pass(args, m, dev, x, bert, prompts):
+    """--slots S [S ...] --prompt-pass {padded,packed,both}: the texts of --stream through one refilled session per slot
+    count, its admissions on the padded rectangle (decode_stream's default) or on the packed token axis
+    (prompt_pass="packed"); both = the two alternated inside every pass on the SAME session (the prompt pass is no part of
+    a session's key or of its step graph).  Per mode and slot count: useful tokens/s, us per step without the prompt
+    passes, their share of the seconds and their milliseconds per admitted text; the median pass of --reps, every pass's
+    seconds next to it.  Writes profiles/s1_decode_stream_packed.json."""
+    lives, xs, berts, pr, noise, kw, _g = _stream_workload(args, dev, x, bert, prompts)
+    N = args.stream_n
+    infer = m._infer()
+    modes = {"padded": [None], "packed": ["packed"], "both": [None, "packed"]}[args.prompt_pass]
+    name = {None: "padded", "packed": "packed"}
+    kv = None if args.kv_dtype == "none" else args.kv_dtype
+    infer.WIDE_SESSIONS = max(infer.WIDE_SESSIONS, len(args.slots))
+    reqs = [(xs[r], berts[r], pr[r]) for r in range(N)]
+    useful = sum(lives)
+    runs, first = {(pp, S): [] for pp in modes for S in args.slots}, {}
+    for rep in range(args.reps + 1):
+        for S in args.slots:                   # alternated: every slot count and mode sees the same state of the device
+            for pp in modes:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ys = [None] * N
+                for r, y, _i in m.decode_stream(reqs, slots=S, wide=S > 32, noise=noise, kv_dtype=kv, prompt_pass=pp, **kw):
+                    ys[r] = y
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+                st = infer.stream_stats
+                assert [y.numel() for y in ys] == [args.prompt + s for s in lives], (S, pp)
+                first.setdefault(pp, ys)
+                runs[pp, S].append(dict(seconds=t, steps=st["steps"], prefill_s=sum(st["prefill_s"]),
+                                        admissions=st["admissions"], texts=sum(st["prefill_rows"])))
+    outs = {name[pp]: {} for pp in modes}
+    for (pp, S), v in runs.items():
+        timed = v[1:]
+        med = sorted(timed, key=lambda e: e["seconds"])[len(timed) // 2]
+        t, pre = med["seconds"], med["prefill_s"]
+        outs[name[pp]][str(S)] = dict(
+            seconds=round(t, 4), steps=med["steps"], useful_tokens=useful, tokens_per_s=round(useful / t, 1),
+            us_per_step=round(1e6 * (t - pre) / med["steps"], 1), admissions=med["admissions"],
+            prefill_share=round(pre / t, 4), prefill_ms_per_text=round(1e3 * pre / med["texts"], 3),
+            seconds_all_runs=[round(e["seconds"], 4) for e in timed],
+            prefill_ms_per_text_all_runs=[round(1e3 * e["prefill_s"] / e["texts"], 3) for e in timed])
+    extra = {}
+    if len(modes) == 2:
+        extra["texts_with_the_padded_pass_tokens"] = sum(torch.equal(a, b) for a, b in zip(first[None], first["packed"]))
+        for S in args.slots:
+            a, b = outs["padded"][str(S)], outs["packed"][str(S)]
+            b["tokens_per_s_over_padded"] = round(b["tokens_per_s"] / a["tokens_per_s"], 3)
+            b["prefill_ms_per_text_over_padded"] = round(b["prefill_ms_per_text"] / a["prefill_ms_per_text"], 3)
+    lens = [int(t.numel()) for t in xs]
+    res = dict(workload=f"s1 decode stream, {N} texts living 64..512 steps, text lengths {min(lens)}..{max(lens)} (mean "
+                        f"{sum(lens) / N:.1f}) in a session of Xmax = {max(lens)}, prompt={args.prompt}, {args.dtype}, "
+                        f"kv_dtype={kv}, poll {kw['poll']}, slots {args.slots} and prompt passes alternated, median of "
+                        f"{args.reps}; us_per_step excludes the prompt passes, prefill_share is their share of the seconds",
+               note="random-init model: no claim about trained checkpoints or audio quality is made", **outs, **extra)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "s1_decode_stream_packed.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
 def run_stream(args, m, dev, x, bert, prompts):
     """grouped against refilled decoding of the same requests (see the module docstring)"""
     lives, xs, berts, pr, noise, kw, g = _stream_workload(args, dev, x, bert, prompts)
@@ -408,6 +471,10 @@ def main():
                     help="with --stream --slots: the sessions' cache format (decode_stream's kv_dtype); both = the session "
                          "dtype's cache and the MXFP8 cache alternated in every pass, with the cache bytes, the texts that "
                          "decode to the same tokens and |delta log-prob| of score_stream under both")
+    ap.add_argument("--prompt-pass", default=None, choices=["padded", "packed", "both"],
+                    help="with --stream --slots: the admissions' prompt pass (decode_stream's prompt_pass); both = the padded "
+                         "and the packed pass alternated in every pass.  --kv-dtype none / mxfp8 picks the cache; writes "
+                         "profiles/s1_decode_stream_packed.json (nothing else)")
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="with --stream: request r samples with parameter set r %% N; one session holding all sets "
                          "against N uniform streams run one after the other (nothing else)")
@@ -442,6 +509,10 @@ def main():
         os.environ["EVT_DECODE_GRAPH"] = "1"
         if args.slots:
             assert all(1 <= S <= 128 for S in args.slots), args.slots
+            if args.prompt_pass is not None:
+                assert args.kv_dtype != "both", "--prompt-pass runs one cache format per call"
+                run_prompt_pass(args, m, dev, x, bert, prompts)
+                return
             run_slots(args, m, dev, x, bert, prompts)
             return
         if args.mixed:
