@@ -210,7 +210,10 @@ ROW_IDLE, ROW_RUNNING, ROW_STOP_EOS, ROW_STOP_LIMIT = range(4)
 SAMPLE_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty")
 KV_DTYPES = (None, "mxfp8")      # cache formats of a stream session: the session dtype, or 33 bytes per head row
 MX_BLOCK = 32                    # the head width an MXFP8 cache serves: one scale byte per 32 codes
-PROMPT_PASSES = (None, "packed")  # prompt passes of a stream session: the padded rectangle, or the packed token axis
+# prompt passes: the padded rectangle, the packed token axis, or (score_stream alone) ONE packed pass over prompt and given
+# tokens with the log-probability head of csrc/s1_score.hip behind it, no stream session at all
+PROMPT_PASSES = (None, "packed", "teacher")
+SCORE_TILE = 16                  # EVT_SCORE_ROWS_TILE: scored positions per block, counted from a sequence's own index 0
 PACKED_QUERY_TILE = 64           # EVT_ATTN_PACKED_QUERY_TILE: queries per block, counted from a sequence's own row 0
 KV_FMT_SLAB, KV_FMT_MX8 = 0, 1   # EVT_KV_FMT_*
 
@@ -231,6 +234,16 @@ def packed_layout(x_lens, y_lens, slots):
         dst_off.append(len(dst_slot))
         t += xl + yl
     return tok0, tiles, dst_off, dst_slot
+
+
+def attn_packed_launch(qkv, out, desc, k, nt, n_dst, H, fmt, cdt, cache, B, Lmax, Xmax):
+    """evt_attn_prefixlm_packed_fwd (csrc/attn_packed.hip) of qkv [T][3E] into out [T][E]; desc: the int32 device vectors
+    (tok0, x_lens, y_lens, tiles, dst_off, dst_slot) of packed_layout; cache: (keys, values, key scales, value scales)"""
+    tok0, xl, yl, tiles, dst_off, dst_slot = desc
+    L.check(L.lib().evt_attn_prefixlm_packed_fwd(
+        L.dt_of(qkv), L.ptr(qkv), L.ptr(out), L.ptr(tok0), L.ptr(xl), L.ptr(yl), L.ptr(tiles), L.ptr(dst_off),
+        L.ptr(dst_slot), fmt, cdt, L.ptr(cache[0]), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cache[3]), qkv.size(0), k, nt,
+        n_dst, H, qkv.size(1) // (3 * H), B, Lmax, Xmax, L.stream_ptr()), "evt_attn_prefixlm_packed_fwd")
 
 
 # what decode_stream yields when log-probabilities or several candidates per request were asked for: candidate c of
@@ -321,11 +334,7 @@ class StreamSession(_Session):
             fmt, cdt, cache = KV_FMT_SLAB, L.dt_of(self.kc), (self.kc[i], self.vc[i], None, None)
         else:
             fmt, cdt, cache = KV_FMT_MX8, 0, (self.kq[i], self.vq[i], self.ks[i], self.vs[i])
-        tok0, xl, yl, tiles, dst_off, dst_slot = desc
-        L.check(L.lib().evt_attn_prefixlm_packed_fwd(
-            L.dt_of(qkv), L.ptr(qkv), L.ptr(out), L.ptr(tok0), L.ptr(xl), L.ptr(yl), L.ptr(tiles), L.ptr(dst_off),
-            L.ptr(dst_slot), fmt, cdt, L.ptr(cache[0]), L.ptr(cache[1]), L.ptr(cache[2]), L.ptr(cache[3]), qkv.size(0), k, nt,
-            n_dst, self.H, self.E // self.H, self.B, self.Lmax, self.Xmax, L.stream_ptr()), "evt_attn_prefixlm_packed_fwd")
+        attn_packed_launch(qkv, out, desc, k, nt, n_dst, self.H, fmt, cdt, cache, self.B, self.Lmax, self.Xmax)
 
     def _sample_embed(self, W, sp, noise, pe, dpos, mask=None):
         """sampling, append, EOS / limit test, next-input embedding and the row's counter update: one launch for all rows
@@ -620,8 +629,16 @@ class T2SInfer:
         packed_layout and are uploaded once.  The cache positions x_lens[s] <= j < Xmax of a slot, which _prompt_pass fills
         with the padding's keys, are left as they were: the step masks them.  Returns the activations of every
         sequence's last row [k, E] (step 0 reads them) and the text lengths on the device."""
+        xy, tok0, x_lens, y_lens, desc = self._packed_rows(S._attn_packed, S.dtype, S.device, W, xs, berts, prompts, slots)
+        last = torch.tensor([t + a + b - 1 for t, a, b in zip(tok0, x_lens, y_lens)], dtype=torch.long).to(S.device)
+        return xy[0, last], desc[1]
+
+    def _packed_rows(self, attn, cd, dev, W, xs, berts, prompts, slots):
+        """the packed pass itself, for _prompt_pass_packed and the teacher pass of score_stream: attn(i, qkv, out, desc, k,
+        nt, n_dst) is layer i's attention launch (a session's, which writes its cache, or one without a cache).  Returns
+        the activations of EVERY row after the last block xy [1][T][E] in cd, the lists tok0, x_lens, y_lens and the
+        descriptors on the device."""
         m = self.model
-        dev, cd = S.device, S.dtype
         dense = self.dense(cd, dev)
         parts, x_lens, y_lens = [], [int(x.numel()) for x in xs], [int(p.numel()) for p in prompts]
         for x, bert, pr in zip(xs, berts, prompts):
@@ -642,13 +659,12 @@ class T2SInfer:
             w = W.layers[i]
             qkv = dense(xy, lyr.self_attn.in_proj_weight).contiguous()
             o = torch.empty_like(xy)
-            S._attn_packed(i, qkv[0], o[0], desc, k, nt, n_dst)
+            attn(i, qkv[0], o[0], desc, k, nt, n_dst)
             sa = dense(o, lyr.self_attn.out_proj.weight)
             xy = AddLayerNormFn.apply(xy, sa, w["g1"], w["be1"], w["eps1"])
             ff = dense(dense(xy.contiguous(), lyr.linear1.weight, relu=True), lyr.linear2.weight)
             xy = AddLayerNormFn.apply(xy, ff, w["g2"], w["be2"], w["eps2"])
-        last = torch.tensor([t + a + b - 1 for t, a, b in zip(tok0, x_lens, y_lens)], dtype=torch.long).to(dev)
-        return xy[0, last], desc[1]
+        return xy, tok0, x_lens, y_lens, desc
 
     @torch.no_grad()
     def _decode(self, xs, berts, prompts, no_eos_steps, top_k, top_p, early_stop_num, temperature, repetition_penalty,
@@ -862,7 +878,8 @@ class T2SInfer:
         linear layers and LayerNorms see the live rows only, and the attention launch writes the cache (either format).
         Opt-in: sums run in another order than in the padded pass, so log-probabilities differ in the last bits (a row
         still is the row alone).  It composes with every other keyword; needs a head width of 32; any other value than
-        None or "packed" raises EvtError."""
+        None or "packed" raises EvtError -- "teacher", the third member of PROMPT_PASSES, included: it is score_stream's
+        one-pass scoring and decodes nothing."""
         if self.model.training:
             raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
         if kv_dtype not in KV_DTYPES:
@@ -872,6 +889,9 @@ class T2SInfer:
                              f"{self.model.model_dim // self.model.num_head}")
         if prompt_pass not in PROMPT_PASSES:
             raise L.EvtError(f"prompt_pass = {prompt_pass!r} is not one of {PROMPT_PASSES}")
+        if prompt_pass == "teacher":
+            raise L.EvtError("prompt_pass = 'teacher' scores GIVEN tokens in one pass and decodes nothing: it is "
+                             "score_stream's alone")
         if prompt_pass is not None and self.model.model_dim != MX_BLOCK * self.model.num_head:
             raise L.EvtError(f"prompt_pass = {prompt_pass!r} needs a head width of {MX_BLOCK}, the model's is "
                              f"{self.model.model_dim // self.model.num_head}")
@@ -911,9 +931,17 @@ class T2SInfer:
         Yields (r, logprobs) in completion order, logprobs fp32 [f, 2]: per given token the model's log-probability and
         the log of the probability the sampler would have drawn it from under the request's sampling values (-inf where
         the sampler cuts the token).  No noise value can change a forced row, so `seed` / `noise` do not matter; the
-        other keywords are decode_stream's (kv_dtype: the session's cache format; prompt_pass: its prompt pass).  A thin
-        wrapper over decode_stream: the sequence is scored by the decode steps themselves, one token per step, with the
-        sampler's own arithmetic."""
+        other keywords are decode_stream's (kv_dtype: the session's cache format; prompt_pass: its prompt pass).  With
+        prompt_pass None or "packed" this is a thin wrapper over decode_stream: the sequence is scored by the decode steps
+        themselves, one token per step, with the sampler's own arithmetic.
+
+        prompt_pass="teacher" scores in ONE packed pass per group of requests instead (_score_teacher): no stream session,
+        no cache, no step.  The given tokens are known, so prompt and tokens go through _packed_rows together and
+        evt_score_rows (csrc/s1_score.hip) turns the hidden state in front of every given token into the same two values.
+        Results come in request order.  Opt-in: the numbers come from other kernels than the steps' (the sums run in another
+        order), so they differ from the stepped path in the last bits; a request still is the request scored alone.
+        It takes top_k, top_p, temperature and repetition_penalty (and ignores seed, noise and poll); needs kv_dtype=None
+        and a head width of 32."""
         eos = self.model.EOS
 
         def forced_requests():
@@ -929,11 +957,86 @@ class T2SInfer:
                 opt.update(force=t, early_stop_num=max(0, t.numel() - 1))      # _limit: exactly t.numel() steps
                 yield (req[0], req[1], req[2], opt)
 
+        if prompt_pass == "teacher":
+            yield from self._score_teacher(forced_requests(), slots, wide, kv_dtype, sampling)
+            return
         lazy = not isinstance(requests, (list, tuple))
         reqs = forced_requests() if lazy else list(forced_requests())
         for o in self.decode_stream(reqs, slots=slots, logprobs=True, forced=True, wide=wide, kv_dtype=kv_dtype,
                                     prompt_pass=prompt_pass, **sampling):
             yield o.request, o.logprobs
+
+    TEACHER_ROWS = 8192  # packed rows (texts, prompts and given tokens) of one group of the teacher pass at most
+
+    @torch.no_grad()
+    def _score_teacher(self, forced, slots, wide, kv_dtype, sampling):
+        """score_stream(prompt_pass="teacher").  forced: the requests with their given tokens as "force", as the stepped
+        path would get them; they are parsed by the same _RequestParser.  Consecutive requests form a group while it has at
+        most `slots` of them and its packed rows stay within TEACHER_ROWS (a request longer than that is a group of one).
+        Per group: _packed_rows over text, prompt and given tokens of every request, with an attention launch that has no
+        cache to write, then ONE evt_score_rows launch over all of the group's positions."""
+        m = self.model
+        if m.training:
+            raise L.EvtError("decoding needs model.eval() (the reference decodes with dropout off)")
+        if kv_dtype is not None:
+            raise L.EvtError(f"prompt_pass = 'teacher' keeps no key/value cache: kv_dtype = {kv_dtype!r} must be None")
+        if m.model_dim != MX_BLOCK * m.num_head:
+            raise L.EvtError(f"prompt_pass = 'teacher' needs a head width of {MX_BLOCK}, the model's is "
+                             f"{m.model_dim // m.num_head}")
+        most = self.STREAM_ROWS if wide else self.WIDE_ROWS
+        if not 1 <= int(slots) <= most:
+            raise L.EvtError(f"slots must be 1..{most}, got {slots}")
+        unknown = sorted(set(sampling) - set(SAMPLE_KEYS) - {"seed", "noise", "poll"})
+        if unknown:
+            raise L.EvtError(f"prompt_pass = 'teacher' takes {list(SAMPLE_KEYS)} (and ignores seed, noise, poll), not {unknown}")
+        base = dict(top_k=-100, top_p=100, temperature=1.0, repetition_penalty=1.35)
+        base.update({k: v for k, v in sampling.items() if k in SAMPLE_KEYS})
+        parse = _RequestParser(m, base, 1, int(slots), -1, None, True, True, True)
+        group, rows = [], 0
+        for r, req in enumerate(forced):
+            q = parse(r, req)
+            n = q.x.numel() + q.prompt.numel() + q.force.numel()
+            if group and (len(group) == int(slots) or rows + n > self.TEACHER_ROWS):
+                yield from self._score_group(group)
+                group, rows = [], 0
+            group.append(q)
+            rows += n
+        if group:
+            yield from self._score_group(group)
+
+    def _score_group(self, group):
+        m = self.model
+        dev, cd = group[0].x.device, m.cd
+        L.set_half(cd)
+        W = self.weights(cd)
+        H, E, V = m.num_head, m.model_dim, m.vocab_size
+        none = torch.zeros(16, dtype=torch.uint8, device=dev)      # a valid address for the cache no slot maps to
+
+        def attn(i, qkv, out, desc, k, nt, n_dst):
+            attn_packed_launch(qkv, out, desc, k, nt, n_dst, H, KV_FMT_SLAB, L.dt_of(qkv), (none, none, None, None), 1, 1, 0)
+
+        seqs = [torch.cat([q.prompt.reshape(-1).cpu().long(), q.force]) for q in group]
+        xy, tok0, x_lens, _y, _desc = self._packed_rows(attn, cd, dev, W, [q.x for q in group], [q.bert for q in group],
+                                                         seqs, [[] for _q in group])
+        P, f = [int(q.prompt.numel()) for q in group], [int(q.force.numel()) for q in group]
+        hist0 = [sum(P[:s]) + sum(f[:s]) for s in range(len(group))]
+        row0 = [t + a + p - 1 for t, a, p in zip(tok0, x_lens, P)]
+        tiles = [v for s, n in enumerate(f) for i0 in range(0, n, SCORE_TILE) for v in (s, i0)]
+        tab = torch.tensor([[0.0, *q.sampling[1:]] for q in group], dtype=torch.float32)
+        tab.view(torch.int32)[:, 0] = torch.tensor([q.sampling[0] for q in group], dtype=torch.int32)
+        fields = (torch.cat(seqs).to(torch.int32), *(torch.tensor(v, dtype=torch.int32) for v in (hist0, row0, P, f, tiles)),
+                  tab.view(torch.int32).reshape(-1))
+        hist, d_hist0, d_row0, d_P, d_f, d_tiles, d_tab = torch.cat(fields).to(dev).split([v.numel() for v in fields])
+        logp = torch.full((sum(f), 2), float("nan"), dtype=torch.float32, device=dev)
+        h = xy[0]
+        L.check(L.lib().evt_score_rows(L.dt_of(h), L.ptr(h), L.ptr(W.wpred), L.ptr(hist), L.ptr(d_hist0), L.ptr(d_row0),
+                                       L.ptr(d_P), L.ptr(d_f), L.ptr(d_tab), L.ptr(d_tiles), L.ptr(logp), m.EOS, 1,
+                                       len(group), len(tiles) // 2, h.size(0), E, V, hist.numel(), logp.size(0),
+                                       L.stream_ptr()), "evt_score_rows")
+        at = 0
+        for q, n in zip(group, f):
+            yield q.r, logp[at:at + n].clone()
+            at += n
 
     @staticmethod
     def _fits(q, cap):
@@ -1169,6 +1272,8 @@ class T2SInfer:
         then checked by decode_stream: 1..32, with wide=True 1..128 -- so a larger value passes when there are no more
         texts than that, as slots=33 always did.  kv_dtype, prompt_pass: decode_stream's (the session's cache format and its
         prompt pass)."""
+        if prompt_pass == "teacher":      # refused here too: the branch below never reaches decode_stream
+            raise L.EvtError("prompt_pass = 'teacher' scores GIVEN tokens in one pass: it is score_stream's alone")
         if prompts is None:
             if logprobs:
                 raise L.EvtError("logprobs needs prompts (the refilled session)")

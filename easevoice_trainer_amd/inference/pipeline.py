@@ -166,6 +166,10 @@ def synthesize_stream(t2s, voice, batch_phones, all_phoneme_ids, all_bert_featur
     are then not those of the default cache).  prompt_pass: None, or "packed" for decode_stream's packed prompt pass (no
     padded rows in an admission)."""
     model, dev = t2s.model, t2s.device
+    if prompt_pass == "teacher":      # score_stream's one-pass scoring decodes nothing; refused before any tensor moves
+        from ..hip.lib import EvtError
+
+        raise EvtError("prompt_pass = 'teacher' scores GIVEN tokens in one pass: it is score_stream's alone")
     cache = {} if kv_dtype is None else {"kv_dtype": kv_dtype}      # the keywords reach decode_stream only when asked for
     if prompt_pass is not None:
         cache["prompt_pass"] = prompt_pass

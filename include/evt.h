@@ -1138,6 +1138,35 @@ int evt_dec_sample_embed_rows_f(const evt_sample_params* p, const evt_row_sample
                                 const int32_t* row_seed, const int32_t* row_mask, const float* emb, const float* pe,
                                 const float* alpha, float x_scale, float* x, float* row_logp, int32_t B, int32_t E,
                                 int32_t npos, int32_t dpos, void* stream);
+/* Teacher-forced scoring of GIVEN tokens for many positions at once (csrc/s1_score.hip): the log-probability head of
+ * score_stream(prompt_pass="teacher"), the two values evt_dec_sample_embed_rows_f reports per forced step, computed from
+ * the hidden states of one packed prompt pass instead of one decode step per token.
+ * h [T][E]: hidden states after the last block, Wp [V][E]: ar_predict_layer.weight (no bias), both in dtype (EVT_DT_F32 or
+ * the build's 16-bit type), 16-byte aligned.  E % 16 == 0, E <= 1024, 2 <= V <= 2048, eos == V - 1 (the column a step
+ * below no_eos_steps drops).  hist int32 [n_hist]: sequence s of k owns hist[hist0[s] .. hist0[s] + P[s] + f[s]), its
+ * prompt tokens followed by its given tokens.  row0[s]: the row of h that predicts its first given token; scored index i
+ * (0 <= i < f[s], the step index IDX of the stepped path) reads h[row0[s] + i] and the token hist[hist0[s] + P[s] + i].
+ * row_sample [k]: the sampling values of sequence s.  tiles int32 [nt][2] = (sequence, first scored index): 16 scored
+ * indices each, counted from the sequence's own index 0; the grid is nt.  logp fp32 [n_out][2], packed in sequence order:
+ * sequence s starts at pair f[0] + .. + f[s - 1].  For index i, with logits = Wp . h[row0[s] + i] (fp32 sums) and
+ * Ve = V - 1 while i < no_eos_steps, else V:
+ *   [0]  log_softmax of the raw logits over the columns [0, Ve) at the token; -inf for a token in [Ve, V);
+ *   [1]  the log of the probability the sampler draws the token from: repetition penalty over hist[hist0[s] ..
+ *        hist0[s] + P[s] + i), the nucleus on the sorted penalised logits (descending, first index among equals, first
+ *        entry always kept; top_p >= 1: off), division by max(temperature, 1e-5), the top-k pivot (top_k <= 0: off; every
+ *        value >= the k-th kept; no pivot when the nucleus cut the k-th) -- x - max - log(sum) over the survivors, -inf
+ *        for a token that was cut.
+ * A token outside [0, V) gives NaN in both.  All sums are fp32 in an order fixed by E, V and the sequence's own lengths:
+ * a sequence's pairs are those of the sequence scored alone.  The descriptors are device memory: a tile whose sequence,
+ * first index (not a multiple of 16, or outside [0, f[s])), rows (outside [0, T)), history (outside [0, n_hist)) or
+ * output pairs (outside [0, n_out)) are out of range does nothing.  A scored index no tile covers gets no output.
+ * EVT_EINVAL (nothing launched) for a NULL pointer, h / Wp / logp misaligned, k, nt, T, n_hist or n_out <= 0, eos != V - 1
+ * or a dtype code that is none; EVT_ENOTSUP for E or V outside the limits above or the other build's 16-bit code. */
+#define EVT_SCORE_ROWS_TILE 16
+int evt_score_rows(int32_t dtype, const void* h, const void* Wp, const int32_t* hist, const int32_t* hist0,
+                   const int32_t* row0, const int32_t* P, const int32_t* f, const evt_row_sample* row_sample,
+                   const int32_t* tiles, float* logp, int32_t eos, int32_t no_eos_steps, int32_t k, int32_t nt, int32_t T,
+                   int32_t E, int32_t V, int32_t n_hist, int32_t n_out, void* stream);
 
 /* ScaledAdam (src/easevoice/soundstorm/auto_reg/modules/optim.py:206-251,300-390,448-622) over a flat fp32 arena.
  * The reference stacks same-shaped tensors only to batch its torch ops; the arithmetic is per tensor, which is what

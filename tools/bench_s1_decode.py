@@ -355,6 +355,51 @@ def run_prompt_pass(args, m, dev, x, bert, prompts):
     print(json.dumps(res), flush=True)
 
 
+def run_score(args, m, dev, x, bert, prompts):
+    """--score: score_stream over the first 64 texts of --stream and the tokens a 32-slot stream decodes for them (the
+    scoring run_slots does), stepped (prompt_pass="packed": one graph replay per token) against the one-pass path
+    (prompt_pass="teacher"), alternated in one process; then 32 of the texts cut to 16, 64 and 256 given tokens each, to see
+    where the one pass stops paying.  Median pass of --reps after one untimed pass, every pass's seconds next to it.
+    Writes profiles/s1_score_teacher.json."""
+    lives, xs, berts, pr, noise, kw, _g = _stream_workload(args, dev, x, bert, prompts)
+    n = min(args.stream_n, 64)
+    reqs = [(xs[r], berts[r], pr[r]) for r in range(n)]
+    toks = [None] * n
+    for r, y, _i in m.decode_stream(reqs, slots=32, noise=noise, **kw):
+        toks[r] = y[args.prompt:].cpu()
+    sk = dict(slots=32, top_k=kw["top_k"], top_p=kw["top_p"], repetition_penalty=kw["repetition_penalty"])
+
+    def timed(rq, tk):
+        runs, got = {"packed": [], "teacher": []}, {}
+        for _rep in range(args.reps + 1):
+            for pp in runs:                       # alternated: both paths see the same state of the device
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got[pp] = dict(m.score_stream(rq, tk, prompt_pass=pp, **sk))
+                torch.cuda.synchronize()
+                runs[pp].append(time.perf_counter() - t0)
+        out = {pp: dict(seconds=round(sorted(v[1:])[len(v[1:]) // 2], 4), seconds_all_runs=[round(t, 4) for t in v[1:]])
+               for pp, v in runs.items()}
+        d = torch.cat([(got["teacher"][r] - got["packed"][r])[:, 0].abs().cpu() for r in range(len(rq))])
+        out["stepped_over_teacher"] = round(out["packed"]["seconds"] / out["teacher"]["seconds"], 2)
+        out["given_tokens"] = int(d.numel())
+        out["model_logprob_abs_delta_max"] = float(d.max())
+        return out
+
+    res = dict(workload=f"score_stream, {n} texts of --stream with the {sum(t.numel() for t in toks)} tokens a 32-slot stream "
+                        f"decodes for them (64..512 each), prompt={args.prompt}, {args.dtype}, 32 slots; stepped = "
+                        f"prompt_pass='packed', one replay per token; alternated, median of {args.reps}",
+               note="random-init model: no claim about trained checkpoints is made", all_texts=timed(reqs, toks))
+    for f in (16, 64, 256):
+        rows = [r for r in range(n) if toks[r].numel() >= f][:32]
+        res[f"{len(rows)}_texts_of_{f}_tokens"] = timed([reqs[r] for r in rows], [toks[r][:f] for r in rows])
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "s1_score_teacher.json"), "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res), flush=True)
+
+
 def run_stream(args, m, dev, x, bert, prompts):
     """grouped against refilled decoding of the same requests (see the module docstring)"""
     lives, xs, berts, pr, noise, kw, g = _stream_workload(args, dev, x, bert, prompts)
@@ -486,6 +531,9 @@ def main():
                          "sampler launch) against the plain stream; --logprobs turns them on for both (nothing else)")
     ap.add_argument("--logprobs", action="store_true",
                     help="with --stream: time per replay with per-token log-probabilities on against off (nothing else)")
+    ap.add_argument("--score", action="store_true",
+                    help="score_stream over 64 texts of --stream: the stepped path against prompt_pass='teacher', alternated; "
+                         "writes profiles/s1_score_teacher.json (nothing else)")
     args = ap.parse_args()
     from easevoice_trainer_amd.train.s1_engine import S1Engine
 
@@ -505,6 +553,10 @@ def main():
     noise = torch.empty(args.tokens + 2, 1025).exponential_(1, generator=g)
     noise[:, 1024] = 1e30
     noise = noise.to(dev)
+    if args.score:
+        os.environ["EVT_DECODE_GRAPH"] = "1"
+        run_score(args, m, dev, x, bert, prompts)
+        return
     if args.stream:
         os.environ["EVT_DECODE_GRAPH"] = "1"
         if args.slots:
